@@ -1,7 +1,7 @@
 """Benchmark of the hot path on N MI355X, one process per GPU, image batches sharded data-parallel with one RCCL all-reduce
 per optimizer.
 
-    python bench.py --gpus N --steps K --warmup W [--config {1..5}]
+    python bench.py --gpus N --steps K --warmup W [--config {1..5}] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Started WITHOUT a launcher and with --gpus N > 1, this script itself starts the N ranks (a torch.distributed.run child,
@@ -20,7 +20,17 @@ reference architecture at channels=16: what enhanced_train.py:18-21 trains).  We
 prints ONE JSON line.  An "image" is one input image pushed through the step; a train step consumes 2 * batch images (one per
 domain), so value = 2 * batch * N / step_time there, and batch * N / step_time for the generator-only configs.
 
-Besides the contract fields the line carries
+A plain run sets up, warms up, times the K steps and prints the line; `roofline` and `cpu_baseline` are null there.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed, as the caller of that path receives
+it, to DIR/<name>.npy (float32): train configs `losses` (the step's loss vector), `g_params` / `d_params` (the two optimizers'
+flat parameter buffers after the step's Adam updates); config 2 `loss`, `grads` (the flat gradient buffer); forward configs
+`mean_abs` and `output` (the generator's output).  An array of more than 4M elements is replaced by `<name>_sample`: 4M elements
+at indices drawn with a fixed seed (sorted, with replacement), so a dump stays well below 64 MB.  Inputs and weights are seeded,
+so two builds run with the same arguments can be compared array by array.
+
+--full adds what takes runs of its own beside the timed steps (each can still be switched off with --no-roofline /
+--no-cpu-baseline; --kernel-table needs it):
   roofline     : the kernel symbol with the largest share of GPU time among ALL launches of an instrumented step that follows the
                  timed region (same shapes, one stream).  The library itself brackets every kernel it launches with HIP events on
                  the launch stream (mstg_prof_*, csrc/runtime.hip), so a call that launches two kernels contributes two rows;
@@ -75,10 +85,16 @@ def parse():
     ap.add_argument("--dtype", choices=("f32", "f16"), default=None, help="forward-only configs: storage/MFMA type")
     ap.add_argument("--style-loss", action="store_true",
                     help="add the build-defined VGG/Gram multi-style loss (3 weighted references) to the train step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel table of the instrumented step to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the instrumented roofline step and the CPU baseline (off in a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the instrumented roofline step")
+    ap.add_argument("--kernel-table", action="store_true", help="with --full: print the per-kernel table of the instrumented step to stderr")
     args = ap.parse_args()
+    if args.kernel_table and not (args.full and not args.no_roofline):
+        ap.error("--kernel-table prints the instrumented step: it needs --full (and no --no-roofline)")
     cfg = CONFIGS[args.config]
     args.kind = cfg["kind"]
     args.batch = cfg["batch"] if args.batch is None else args.batch
@@ -254,6 +270,22 @@ def workload_label(args) -> str:
             f"{args.batch} images/GPU at {sz}, " + ("fp16 storage + fp16 MFMA, fp32 accumulate" if args.dtype == "f16" else "fp32"))
 
 
+DUMP_MAX_ELEMS = 1 << 22  # 16 MB of float32 per array
+
+
+def dump_outputs(out, path):
+    """DIR/<name>.npy in float32 for every array of the last timed step; one of more than DUMP_MAX_ELEMS elements becomes
+    DIR/<name>_sample.npy, its elements at DUMP_MAX_ELEMS sorted indices drawn (with replacement) from a fixed seed."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     rehearse = os.environ.get("MSTG_BENCH_REHEARSE", "0") == "1"
@@ -289,8 +321,9 @@ def main():
         real_B = (torch.rand(shape, generator=gen) * 2 - 1).to(dev)
         images_per_step = 2 * args.batch
 
-        def step():
-            return model.train_step_async(real_A, real_B)
+        def step():  # (values checked for finiteness, what the caller of the path receives)
+            losses = model.train_step_async(real_A, real_B)
+            return losses, {"losses": losses, "g_params": model.g_optimizer.flat, "d_params": model.d_optimizer.flat}
     else:
         import enhanced_generator
         from mstg_hip.optim import FlatAdam
@@ -304,7 +337,9 @@ def main():
 
             def step():
                 with torch.no_grad():
-                    return net(x).float().abs().mean().reshape(1)
+                    y = net(x)
+                    m = y.float().abs().mean().reshape(1)
+                    return m, {"mean_abs": m, "output": y}
         else:
             opt = FlatAdam(net.parameters(), lr=5e-5, betas=(0.5, 0.999))  # flat gradient buffer = what DP all-reduces
             for b_ in (opt.flat,):
@@ -316,7 +351,8 @@ def main():
                     loss = net(x).abs().mean()
                     loss.backward()
                 dp.allreduce_mean_(opt.grad)
-                return loss.detach().reshape(1)
+                loss = loss.detach().reshape(1)
+                return loss, {"loss": loss, "grads": opt.grad}
 
     def barrier():
         if world > 1:
@@ -324,11 +360,11 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        step()
+        losses, outputs = step()  # held across the next step as in the timed loop, so its memory pattern is warmed up too
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses = step()
+        losses, outputs = step()
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -340,13 +376,18 @@ def main():
     value = images_per_step * world / (dt / args.steps)
 
     roofline = None
-    if not args.no_roofline:
+    if args.dump_outputs and dp.rank() == 0:
+        dump_outputs(outputs, args.dump_outputs)  # before the instrumented step of --full moves parameters on
+    outputs = None
+
+    roofline_on = args.full and not args.no_roofline
+    if roofline_on:
         # EVERY rank runs the instrumented step (it contains the two gradient all-reduces); only rank 0 reports
         ops.KernelTimer.start()
         step()
         torch.cuda.synchronize()
         ops.KernelTimer.stop()
-    if not args.no_roofline and dp.rank() == 0:
+    if roofline_on and dp.rank() == 0:
         table = ops.KernelTimer.summary()              # per KERNEL symbol (what rocprofv3 --kernel-trace --stats ranks)
         calls = ops.KernelTimer.summary(by_call=True)  # per C-ABI call (an op; may launch several kernels)
         total_ms = sum(r["ms"] for r in table.values())
@@ -398,7 +439,7 @@ def main():
                             "tflops_over_wall": round(tot_fl / 1e12 / (ms / 1e3), 2), "gbs_over_wall": round(tot_by / 1e9 / (ms / 1e3), 1)}
 
     cpu = None
-    if dp.rank() == 0 and world == 1 and not args.no_cpu_baseline:
+    if dp.rank() == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if dp.rank() == 0:

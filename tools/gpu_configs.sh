@@ -6,7 +6,7 @@ out=$GRAFT_REPO_ROOT/gpurun_out
 cd $GRAFT_REPO_ROOT
 for k in 1 2 4 5; do
   steps=10; [ $k = 4 ] && steps=4
-  timeout -k 10 400 python bench.py --config $k --steps $steps --warmup 3 > $out/${tag}_cfg$k.log 2>&1 || { tail -5 $out/${tag}_cfg$k.log; exit $k; }
+  timeout -k 10 400 python bench.py --full --config $k --steps $steps --warmup 3 > $out/${tag}_cfg$k.log 2>&1 || { tail -5 $out/${tag}_cfg$k.log; exit $k; }
   grep '^{' $out/${tag}_cfg$k.log > $out/${tag}_cfg$k.json
   python - <<PY
 import json
