@@ -180,9 +180,10 @@ class EnhancedGenerator(nn.Module):
         ``load_state_dict``; call ``half_inference()`` again after changing weights in any other way."""
         if enable:  # fail here, not at the first forward: the fp16 kernels are built for the deployed width
             C0 = self.initial[0].out_channels
-            if C0 != 16:
-                raise RuntimeError(f"mstg_hip fp16 inference is built for channels=16 (stage widths 16/32/64, what every trainer and "
-                                   f"inference caller of the reference uses), got channels={C0}; the fp32 forward serves other widths")
+            if C0 not in (16, 32, 64):
+                raise RuntimeError(f"mstg_hip fp16 inference is built for channels=16, 32 or 64 (channels=16: what every trainer and "
+                                   f"inference caller of the reference uses; 32 / 64: stage widths up to 256), got channels={C0}; "
+                                   f"the fp32 forward serves other widths")
         self._half_enabled = bool(enable)
         self._half_plan = None
         if enable and not getattr(self, "_half_hook", False):

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "infer_f16_wide.h"
 
 typedef _Float16 h16;
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
@@ -731,7 +732,13 @@ __global__ __launch_bounds__(256) void f16_norm_finalize_kernel(const float* __r
     }
 }
 
-// y = relu((x - mean) * rstd) + residual   (the block's `+ x`, enhanced_generator.py:84), NHWC fp16, C in {16, 32, 64}
+int f16_norm_finalize(const float* partial, float* stats, int N, int rows, int CP, int C, float count, hipStream_t st) {
+    MSTG_LAUNCH(f16_norm_finalize_kernel, dim3(N), dim3(256), 0, st, partial, stats, rows, CP, C, count);
+    MSTG_CHECK_LAUNCH("f16_norm_finalize_kernel");
+    return MSTG_OK;
+}
+
+// y = relu((x - mean) * rstd) + residual   (the block's `+ x`, enhanced_generator.py:84), NHWC fp16, C in {16, 32, 64, 128, 256}
 __global__ __launch_bounds__(256) void f16_norm_residual_kernel(const h16* __restrict__ x, const h16* __restrict__ res,
                                                                 const float* __restrict__ stats, h16* __restrict__ y, size_t HW, int C,
                                                                 int blocks_per_image) {
@@ -1045,6 +1052,7 @@ static int launch_conv_npf(const F16ConvArgs& a, const F16Plan& p, int src, int 
 using namespace mstg;
 
 extern "C" size_t mstg_f16_conv_plan_bytes(const mstg_f16_conv_desc* d) {
+    if (d && f16w_conv_is_wide(d)) return f16w_conv_plan_bytes(d);  // more than 64 channels: csrc/infer_f16_wide.hip
     F16Plan p;
     PackTable* pt = new PackTable;
     const int rc = d ? build_plan(d, p, *pt) : MSTG_E_BADARG;
@@ -1056,6 +1064,11 @@ extern "C" int mstg_f16_conv_pack(const mstg_f16_conv_desc* d, const float* w0, 
                                   const float* w2, const float* b2, const float* w3, const float* b3, void* blob, size_t blob_bytes,
                                   void* stream) {
     if (!d || !w0 || !blob) return fail_arg(MSTG_E_BADARG, "f16 conv pack: null pointer");
+    if (f16w_conv_is_wide(d)) {
+        const float* const w[4] = {w0, w1, w2, w3};
+        const float* const b[4] = {b0, b1, b2, b3};
+        return f16w_conv_pack(d, w, b, blob, blob_bytes, (hipStream_t)stream);
+    }
     F16Plan p;
     PackTable* pt = new PackTable;
     if (int rc = build_plan(d, p, *pt)) { delete pt; return rc; }
@@ -1074,6 +1087,7 @@ extern "C" int mstg_f16_conv_pack(const mstg_f16_conv_desc* d, const float* w0, 
 }
 
 extern "C" size_t mstg_f16_conv_partial_bytes(const mstg_f16_conv_desc* d) {
+    if (d && f16w_conv_is_wide(d)) return f16w_conv_partial_bytes(d);
     F16Plan p;
     PackTable* pt = new PackTable;
     const int rc = d ? build_plan(d, p, *pt) : MSTG_E_BADARG;
@@ -1092,6 +1106,8 @@ extern "C" int mstg_f16_conv_fwd_res(const mstg_f16_conv_desc* d, const void* bl
                                      void* stream) {
     if (!d || !blob || !x || !y) return fail_arg(MSTG_E_BADARG, "f16 conv: null pointer");
     if (residual && (!in_stats || d->src_nchw_f32)) return fail_arg(MSTG_E_BADARG, "f16 conv: a residual operand needs NHWC input and its statistics");
+    if (f16w_conv_is_wide(d))
+        return f16w_conv_fwd(d, blob, x, in_stats, residual, y, out_stats, workspace, workspace_bytes, (hipStream_t)stream);
     F16Plan p;
     PackTable* pt = new PackTable;
     const int rc = build_plan(d, p, *pt);
@@ -1114,8 +1130,20 @@ extern "C" int mstg_f16_conv_fwd_res(const mstg_f16_conv_desc* d, const void* bl
     const long tiles = (long)a.N * a.tiles_x * a.tiles_y;
     if (tiles > 0x7fffffffL) return fail_arg(MSTG_E_UNSUPPORTED, "f16 conv: too many tiles");
     // the kernel divides tile indices by multiply-high: exact while index * divisor < 2^32
-    if ((unsigned long long)(tiles + 4096) * (unsigned long long)(a.tiles_x * a.tiles_y) >= (1ull << 32))
-        return fail_arg(MSTG_E_UNSUPPORTED, "f16 conv: batch x tiles too large for the tile-index arithmetic");
+    if ((unsigned long long)(tiles + 4096) * (unsigned long long)(a.tiles_x * a.tiles_y) >= (1ull << 32)) {
+        if (d->N < 2) return fail_arg(MSTG_E_UNSUPPORTED, "f16 conv: batch x tiles too large for the tile-index arithmetic");
+        // the 7x7 stem / head at 64 channels, batch 64, 1024 x 1024 (8-row tiles): two launches of half the batch each (images are
+        // independent; the statistics partials are reused in stream order)
+        const int n0 = d->N / 2;
+        mstg_f16_conv_desc lo = *d, hi = *d;
+        lo.N = n0;
+        hi.N = d->N - n0;
+        const size_t xb = (size_t)n0 * d->Cin * d->H * d->W * (d->src_nchw_f32 ? 4 : 2), yb = (size_t)n0 * d->Cout * d->Ho * d->Wo * 2;
+        if (int rc = mstg_f16_conv_fwd_res(&lo, blob, x, in_stats, residual, y, out_stats, workspace, workspace_bytes, stream)) return rc;
+        return mstg_f16_conv_fwd_res(&hi, blob, (const char*)x + xb, in_stats ? in_stats + (size_t)n0 * d->Cin * 2 : nullptr,
+                                     residual ? (const char*)residual + xb : nullptr, (char*)y + yb,
+                                     out_stats ? out_stats + (size_t)n0 * d->Cout * 2 : nullptr, workspace, workspace_bytes, stream);
+    }
     p.m_ntile = magic_u32((unsigned)(a.tiles_x * a.tiles_y));
     p.m_tx = magic_u32((unsigned)a.tiles_x);
     a.partial = nullptr;
@@ -1205,7 +1233,7 @@ extern "C" int mstg_f16_conv_fwd_res(const mstg_f16_conv_desc* d, const void* bl
 extern "C" int mstg_f16_norm_residual(const void* x, const void* residual, const float* stats, void* y, int N, int HW, int C,
                                       void* stream) {
     if (!x || !stats || !y) return fail_arg(MSTG_E_BADARG, "f16 norm_residual: null pointer");
-    if (C != 16 && C != 32 && C != 64) return fail_arg(MSTG_E_ALIGN, "f16 norm_residual: C must be 16, 32 or 64");
+    if (C != 16 && C != 32 && C != 64 && C != 128 && C != 256) return fail_arg(MSTG_E_ALIGN, "f16 norm_residual: C must be 16, 32, 64, 128 or 256");
     if (N <= 0 || HW <= 0) return fail_arg(MSTG_E_BADARG, "f16 norm_residual: empty tensor");
     const size_t chunks = (size_t)HW * (C / 8);
     int bpi = (int)((chunks + 256 * 8 - 1) / (256 * 8));  // ~8 chunks per thread
@@ -1615,14 +1643,14 @@ __global__ void f16_attn_pack_kernel(const float* __restrict__ wqkv, const float
 }
 
 extern "C" size_t mstg_f16_attn_plan_bytes(int C) {
-    if (C != 16 && C != 32 && C != 64) return 0;
+    if (C != 16 && C != 32 && C != 64 && C != 128 && C != 256) return mstg::fail_arg(MSTG_E_UNSUPPORTED, "f16 attn: C must be 16, 32, 64, 128 or 256"), 0;
     return (size_t)4 * C * sizeof(float) + (size_t)4 * C * C * sizeof(h16);
 }
 
 extern "C" int mstg_f16_attn_pack(const float* wqkv, const float* bqkv, const float* wproj, const float* bproj, int C, void* blob,
                                   size_t blob_bytes, void* stream) {
     if (!wqkv || !wproj || !blob) return mstg::fail_arg(MSTG_E_BADARG, "f16 attn pack: null pointer");
-    if (C != 16 && C != 32 && C != 64) return mstg::fail_arg(MSTG_E_UNSUPPORTED, "f16 attn: C must be 16, 32 or 64");
+    if (C != 16 && C != 32 && C != 64 && C != 128 && C != 256) return mstg::fail_arg(MSTG_E_UNSUPPORTED, "f16 attn: C must be 16, 32, 64, 128 or 256");
     if (blob_bytes < mstg_f16_attn_plan_bytes(C)) return mstg::fail_arg(MSTG_E_WORKSPACE, "f16 attn pack: blob too small");
     float* bias = (float*)blob;
     h16* wfrag = (h16*)((char*)blob + (size_t)4 * C * sizeof(float));
@@ -1676,6 +1704,8 @@ extern "C" int mstg_f16_attn_fwd(const void* x, const float* in_stats, const voi
         case 16: return launch_attn_f16<16>(x, in_stats, blob, y, N, H, W, st);
         case 32: return launch_attn_f16<32>(x, in_stats, blob, y, N, H, W, st);
         case 64: return launch_attn_f16<64>(x, in_stats, blob, y, N, H, W, st);
-        default: return fail_arg(MSTG_E_UNSUPPORTED, "f16 attn: C must be 16, 32 or 64");
+        case 128:
+        case 256: return f16w_attn_fwd(x, in_stats, blob, y, N, H, W, C, st);  // csrc/infer_f16_wide.hip
+        default: return fail_arg(MSTG_E_UNSUPPORTED, "f16 attn: C must be 16, 32, 64, 128 or 256");
     }
 }

@@ -7,9 +7,10 @@ of the convolution in front of the norm and applied (with the ReLU) by the consu
 stage only four tensors are written (conv, attention, branches, fusion) plus the residual sum.
 
 The filters are packed once (inference: weights are frozen) into device blobs; ``EnhancedGenerator.half_inference()`` builds a
-``HalfGeneratorPlan`` and re-builds it after a ``load_state_dict``.  Widths: the three stage widths must be 16 / 32 / 64 channels,
-i.e. ``channels=16`` -- what every trainer / inference caller of the reference builds (enhanced_train.py:18,
-batch_process_images.py:95, advanced_transform.py:12).
+``HalfGeneratorPlan`` and re-builds it after a ``load_state_dict``.  Widths: ``channels`` 16, 32 or 64 (stage widths up to 256).
+``channels=16`` -- what every trainer / inference caller of the reference builds (enhanced_train.py:18, batch_process_images.py:95,
+advanced_transform.py:12) -- runs entirely on the kernels of csrc/infer_f16.hip; the layers with more than 64 input or output
+channels (channels=32 / 64, the class default and generate_new_image.py's model) run on csrc/infer_f16_wide.hip.
 """
 from __future__ import annotations
 
@@ -21,6 +22,9 @@ import torch
 from . import _lib
 from ._lib import ACT_NONE, ACT_TANH, F16ConvDesc
 from .ops import KernelTimer, _p, _stream, _timed
+
+
+HALF_CHANNELS = (16, 32, 64)  # EnhancedGenerator widths the fp16 path serves
 
 
 def _desc(kind, N, H, W, Cin, Ho, Wo, Cout, K, stride, pad, dil=1, src_nchw_f32=0, dst_nchw=0, act=ACT_NONE) -> F16ConvDesc:
@@ -83,7 +87,9 @@ class _PackedConv:
         flops = 2.0 * pix * self.Cin * cout_eff * taps
         nbytes = x.numel() * x.element_size() * (2 if residual is not None else 1) + y.numel() * 2
         name = {0: "conv_f16_kernel", 1: "conv_f16_kernel<convT>", 2: "conv_f16_kernel<msblock>"}[self.kind]
-        if self.kind == 0 and self.K == 1 and self.stride == 1 and not self.src_nchw_f32 and not self.dst_nchw:
+        if self.Cin > 64 or self.Cout > 64:
+            name = "conv_f16w_kernel"  # csrc/infer_f16_wide.hip (every kind)
+        elif self.kind == 0 and self.K == 1 and self.stride == 1 and not self.src_nchw_f32 and not self.dst_nchw:
             name = "conv1x1_f16_kernel"  # the LDS-free streaming variant (unless MSTG_F16_DIRECT=0)
         if residual is not None:
             if residual.shape != x.shape or residual.dtype != torch.float16 or not residual.is_contiguous() or in_stats is None:
@@ -102,7 +108,7 @@ class _PackedAttention:
         lib = _lib.load()
         nbytes = lib.mstg_f16_attn_plan_bytes(self.C)
         if nbytes == 0:
-            raise RuntimeError(f"mstg_hip fp16 inference: LocalAttention with {self.C} channels is not supported (16 / 32 / 64)")
+            raise RuntimeError(f"mstg_hip fp16 inference: LocalAttention with {self.C} channels is not supported (16 / 32 / 64 / 128 / 256)")
         if attn.window_size != 4:
             raise RuntimeError("mstg_hip fp16 inference: LocalAttention window_size must be 4")
         t = [attn.qkv.weight, attn.qkv.bias, attn.proj.weight, attn.proj.bias]
@@ -113,7 +119,8 @@ class _PackedAttention:
     def __call__(self, x, in_stats=None):
         N, H, W, Cn = x.shape
         y = torch.empty_like(x)
-        _timed(f"attn_f16_kernel<{Cn}>", 12.0 * Cn * Cn * N * H * W, 2.0 * 2 * x.numel(), lambda: _lib.check(
+        name = f"attn_f16_kernel<{Cn}>" if Cn <= 64 else "attn_f16w_kernel"
+        _timed(name, 12.0 * Cn * Cn * N * H * W, 2.0 * 2 * x.numel(), lambda: _lib.check(
             _lib.load().mstg_f16_attn_fwd(_p(x), _p(in_stats), _p(self.blob), _p(y), N, H, W, Cn, _stream()), "mstg_f16_attn_fwd"),
             f"N{N} {H}x{W} C{Cn}")
         return y
@@ -132,8 +139,8 @@ class HalfGeneratorPlan:
 
     def __init__(self, gen):
         C0 = gen.initial[0].out_channels
-        if C0 != 16:
-            raise RuntimeError(f"mstg_hip fp16 inference is built for channels=16 (stage widths 16/32/64), got channels={C0}")
+        if C0 not in HALF_CHANNELS:
+            raise RuntimeError(f"mstg_hip fp16 inference is built for channels=16, 32 or 64 (stage widths up to 256), got channels={C0}")
         # StructuralTransformerBlocks (every inference caller of the reference builds num_transformer_blocks=1:
         # direct_transform.py:35, advanced_transform.py:29, batch_process_images.py:95) run on the fp32 kernels between down2 and up1:
         # that tensor is H/4 x W/4 x 64 channels, 1/16 of the activation traffic, and the block's LayerNorm / softmax statistics
