@@ -359,6 +359,31 @@ int mstg_f16_attn_fwd(const void* x, const float* in_stats /*nullable*/, const v
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * fp16 inference of the plain CycleGAN Generator in eval mode (csrc/infer_f16_plain.hip).  Replaces Generator.forward
+ * (pretrain.py:60-97 == batch_process_images.py:20-58) as batch_process_images.py:210-211 calls it under torch.no_grad():
+ * eight 4x4 stride-2 convolutions, fp16 NHWC activations between them, fp16 MFMA with fp32 accumulation, and every
+ * nn.BatchNorm2d (running statistics) folded by the caller into a per-channel fp32 scale / shift that the epilogue applies:
+ *     y = act(acc * scale[co] + shift[co]), rounded once to fp16
+ *     scale = gamma * rsqrt(running_var + eps), shift = beta + (conv_bias - running_mean) * scale   (no norm: 1, conv_bias)
+ * The scale is NOT multiplied into the fp16 filter.  Pixels are flattened over the batch: no per-image work, no workspace.
+ * Filters are packed ONCE per weight set into an opaque device blob.  Deterministic: fixed summation order, no atomics.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mstg_f16_plain_desc {
+    int32_t kind;         /* 0: nn.Conv2d(k4,s2,p1); 1: nn.ConvTranspose2d(k4,s2,p1) */
+    int32_t N, H, W, Cin; /* source (N,H,W,Cin) NHWC fp16 with Cin a multiple of 8 up to 512, or (N,3,H,W) NCHW fp32 (stem) */
+    int32_t Ho, Wo, Cout; /* destination (N,Ho,Wo,Cout) NHWC fp16 with Cout a multiple of 8 up to 512, or (N,Cout,Ho,Wo) NCHW fp16, Cout <= 4 (head) */
+    int32_t K;            /* 4 */
+    int32_t src_nchw_f32; /* 1: the 3-channel fp32 image at the module boundary (kind 0 only) */
+    int32_t dst_nchw;     /* 1: the output image */
+    int32_t act;          /* MSTG_ACT_NONE / _RELU / _LEAKY02 / _TANH */
+} mstg_f16_plain_desc;
+size_t mstg_f16_plain_plan_bytes(const mstg_f16_plain_desc* d); /* size of the blob (N, H, W, Ho, Wo are not read); 0 = unsupported */
+/* w: the layer's fp32 weight (OIHW, or IOHW for kind 1); scale / shift: fp32 [Cout] (nullable: 1 / 0) */
+int mstg_f16_plain_pack(const mstg_f16_plain_desc* d, const float* w, const float* scale, const float* shift, void* blob,
+                        size_t blob_bytes, void* stream);
+int mstg_f16_plain_fwd(const mstg_f16_plain_desc* d, const void* blob, const void* x, void* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Image pre/post-processing of the callers either side of the generator, on the device (8-bit RGB, HWC, 3 bytes per pixel).
  * Replaces PIL / torchvision / numpy work in MonetPhotoDataset (pretrain.py:32-57) and process_cyclegan
  * (batch_process_images.py:183-233).  Integer work: bit-exact against Pillow.

@@ -24,9 +24,16 @@ class F16ConvDesc(C.Structure):
         "kind", "N", "H", "W", "Cin", "Ho", "Wo", "Cout", "K", "stride", "pad", "dil", "src_nchw_f32", "dst_nchw", "act")]
 
 
+class F16PlainDesc(C.Structure):
+    """mirror of mstg_f16_plain_desc"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "kind", "N", "H", "W", "Cin", "Ho", "Wo", "Cout", "K", "src_nchw_f32", "dst_nchw", "act")]
+
+
 _vp, _fp, _sz, _i, _f = C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float
 _dp = C.POINTER(ConvDesc)
 _hp = C.POINTER(F16ConvDesc)
+_pp = C.POINTER(F16PlainDesc)
 
 # name -> (restype, argtypes); the test-suite checks that every symbol declared in include/mstg_hip.h is here
 SIGNATURES = {
@@ -118,6 +125,9 @@ SIGNATURES = {
     "mstg_f16_attn_plan_bytes": (_sz, [_i]),
     "mstg_f16_attn_pack": (_i, [_fp, _fp, _fp, _fp, _i, _vp, _sz, _vp]),
     "mstg_f16_attn_fwd": (_i, [_vp, _fp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mstg_f16_plain_plan_bytes": (_sz, [_pp]),
+    "mstg_f16_plain_pack": (_i, [_pp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "mstg_f16_plain_fwd": (_i, [_pp, _vp, _vp, _vp, _vp]),
     "mstg_add": (_i, [_fp, _fp, _fp, _sz, _vp]),
     "mstg_weighted_sum_fwd": (_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i, _i, _fp, _vp]),
     "mstg_weighted_sum_bwd": (_i, [_fp, C.POINTER(C.c_float), _i, _fp, _vp]),
