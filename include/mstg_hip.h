@@ -384,6 +384,32 @@ int mstg_f16_plain_pack(const mstg_f16_plain_desc* d, const float* w, const floa
 int mstg_f16_plain_fwd(const mstg_f16_plain_desc* d, const void* blob, const void* x, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * fp16 inference of StructuralTransformerBlock (structural_transformer.py:55-74), csrc/infer_f16_block.hip: fp16 storage and MFMA
+ * operands, fp32 accumulation / statistics / softmax, tokens (N, L, C) token-major.  Fixed summation order, no atomics: image i
+ * of a batch equals the same image run alone.
+ * ---------------------------------------------------------------------------------------------- */
+/* token GEMM, nn.Linear over N * L tokens (qkv :69, proj :71, fc1 :73, fc2 :74): y = epi(x W^T + b), x fp16 (N, L, Cin) with Cin in
+ * {64, 128, 256, 512}, Cout a multiple of 64 up to 768.  act: MSTG_ACT_NONE or MSTG_ACT_GELU (exact erf); residual (nullable):
+ * fp32 (N, L, Cout) added behind the activation; y fp16 (out_f16) or fp32.  The blob (fp32 bias + fp16 filter) is packed once. */
+size_t mstg_f16_linear_plan_bytes(int Cin, int Cout); /* 0 = unsupported (mstg_last_error says why) */
+int mstg_f16_linear_pack(const float* w /* (Cout, Cin) */, const float* b /*nullable*/, int Cin, int Cout, void* blob,
+                         size_t blob_bytes, void* stream);
+int mstg_f16_linear_fwd(const void* blob, const void* x, const float* residual /*nullable*/, void* y, int N, int L, int Cin,
+                        int Cout, int act, int out_f16, void* stream);
+/* u = (LayerNorm(h) * gamma + beta) * (1 + g[n]) + b[n] as fp16 (N, L, dim), dim in {64, 128, 256}, statistics in fp32 (:68, :72).
+ * h = x (fp16 if x_f16, else fp32), or with smap (N, L, 4) fp32: h = x + (sp_b + sp_w s) (struct_proj, :65), written to h_out
+ * (fp32, nullable).  gb (nullable): style_mod's fp32 output (N, 2 dim) = g | b. */
+int mstg_f16_ln_mod_fwd(const void* x, int x_f16, const float* smap /*nullable*/, const float* sp_w, const float* sp_b,
+                        const float* gamma, const float* beta, const float* gb /*nullable*/, float* h_out /*nullable*/, void* u,
+                        int N, int L, int dim, float eps, void* stream);
+/* out (N, dim) fp32 = mean over the L tokens of x fp16 (N, L, dim) (AdaptiveAvgPool2d(1) of the style encoder) */
+size_t mstg_f16_token_mean_workspace_bytes(int N, int L, int dim);
+int mstg_f16_token_mean(const void* x, float* out, int N, int L, int dim, void* workspace, size_t workspace_bytes, void* stream);
+/* softmax(q k^T / sqrt(D)) v per head over all L tokens (:70): qkv fp16 (N, L, 3 heads D) q | k | v, out fp16 (N, L, heads D);
+ * D in {16, 32, 64}; inference only (no log-sum-exp) */
+int mstg_f16_flash_attn_fwd(const void* qkv, void* out, int N, int L, int heads, int D, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Image pre/post-processing of the callers either side of the generator, on the device (8-bit RGB, HWC, 3 bytes per pixel).
  * Replaces PIL / torchvision / numpy work in MonetPhotoDataset (pretrain.py:32-57) and process_cyclegan
  * (batch_process_images.py:183-233).  Integer work: bit-exact against Pillow.

@@ -173,19 +173,29 @@ class EnhancedGenerator(nn.Module):
             m.requires_grad_(True)
         self.use_checkpointing = True
 
-    def half_inference(self, enable: bool = True):
+    def half_inference(self, enable: bool = True, fp16_blocks: bool = False):
         """Inference-only fast path (BASELINE config #5): fp16 storage, fp16 MFMA, fp32 accumulation / statistics / softmax.
         Under ``torch.no_grad()`` ``forward`` then runs csrc/infer_f16.hip (mstg_hip/infer.py) and returns an fp16 (N,3,H,W)
         tensor; with autograd enabled the fp32 training path still runs.  The packed fp16 filters are rebuilt lazily after a
-        ``load_state_dict``; call ``half_inference()`` again after changing weights in any other way."""
+        ``load_state_dict``; call ``half_inference()`` again after changing weights in any other way.
+        ``fp16_blocks`` (opt-in): the transformer blocks run on the fp16 kernels of csrc/infer_f16_block.hip too
+        (mstg_hip/infer_block.py) instead of the fp32 kernels; served head widths 16, 32 and 64 (channels 16 / 32 / 64)."""
         if enable:  # fail here, not at the first forward: the fp16 kernels are built for the deployed width
             C0 = self.initial[0].out_channels
             if C0 not in (16, 32, 64):
                 raise RuntimeError(f"mstg_hip fp16 inference is built for channels=16, 32 or 64 (channels=16: what every trainer and "
                                    f"inference caller of the reference uses; 32 / 64: stage widths up to 256), got channels={C0}; "
                                    f"the fp32 forward serves other widths")
+            if fp16_blocks:
+                from mstg_hip.infer_block import check_block
+                for b in self.transformer_blocks:
+                    if not getattr(b, "is_identity", False):
+                        check_block(b)
         self._half_enabled = bool(enable)
+        self._half_blocks = bool(enable and fp16_blocks)
         self._half_plan = None
+        if getattr(self, "_graphs", None):
+            self._graphs = {}  # a captured fp16 graph reads the buffers of the plan just dropped
         if enable and not getattr(self, "_half_hook", False):
             self.register_load_state_dict_post_hook(lambda module, incompatible: setattr(module, "_half_plan", None))
             self._half_hook = True
@@ -204,7 +214,7 @@ class EnhancedGenerator(nn.Module):
         return self
 
     def _graph_forward(self, x):
-        key = (tuple(x.shape), x.dtype, bool(getattr(self, "_half_enabled", False)))
+        key = (tuple(x.shape), x.dtype, bool(getattr(self, "_half_enabled", False)), bool(getattr(self, "_half_blocks", False)))
         entry = self._graphs.get(key)
         if entry is None:
             static_x = x.clone()
@@ -223,7 +233,7 @@ class EnhancedGenerator(nn.Module):
     def _half(self):
         if getattr(self, "_half_plan", None) is None:
             from mstg_hip.infer import HalfGeneratorPlan
-            self._half_plan = HalfGeneratorPlan(self)
+            self._half_plan = HalfGeneratorPlan(self, fp16_blocks=getattr(self, "_half_blocks", False))
         return self._half_plan
 
     def _run(self, fn, *args):

@@ -137,18 +137,23 @@ def norm_residual(x, residual, stats):
 class HalfGeneratorPlan:
     """Packed fp16 copy of an EnhancedGenerator's weights + the fused inference forward."""
 
-    def __init__(self, gen):
+    def __init__(self, gen, fp16_blocks=False):
         C0 = gen.initial[0].out_channels
         if C0 not in HALF_CHANNELS:
             raise RuntimeError(f"mstg_hip fp16 inference is built for channels=16, 32 or 64 (stage widths up to 256), got channels={C0}")
         # StructuralTransformerBlocks (every inference caller of the reference builds num_transformer_blocks=1:
         # direct_transform.py:35, advanced_transform.py:29, batch_process_images.py:95) run on the fp32 kernels between down2 and up1:
         # that tensor is H/4 x W/4 x 64 channels, 1/16 of the activation traffic, and the block's LayerNorm / softmax statistics
-        # want fp32 anyway.  The fp16 features are widened for it and narrowed again behind it.
+        # want fp32 anyway.  The fp16 features are widened for it and narrowed again behind it.  With fp16_blocks they run on the
+        # fp16 kernels of csrc/infer_f16_block.hip instead (mstg_hip/infer_block.py): fp16 in from down2, fp16 out to up1.
         self.blocks = [b for b in gen.transformer_blocks if not getattr(b, "is_identity", False)]
         self.style_vector = gen._style_vector
         if gen.initial[0].weight.device.type != "cuda":
             raise RuntimeError("mstg_hip fp16 inference: move the generator to the GPU first (no CPU path)")
+        self.block_plan = None
+        if fp16_blocks and self.blocks:
+            from .infer_block import HalfBlocksPlan
+            self.block_plan = HalfBlocksPlan(gen, self.blocks)
         c = gen.initial[0]
         self.stem = _PackedConv(0, [c.weight], [c.bias], 3, C0, 7, 1, 3, src_nchw_f32=1)
         self.stages = []
@@ -192,7 +197,9 @@ class HalfGeneratorPlan:
             stats = res = None
             if taps is not None:
                 taps[("down1", "down2", "up1", "up2")[si]] = h
-            if si == 1 and self.blocks:             # enhanced_generator.py:216-225: style vector, tokens, blocks, back
+            if si == 1 and self.block_plan is not None:
+                h = self.block_plan.forward(h, x)
+            elif si == 1 and self.blocks:           # enhanced_generator.py:216-225: style vector, tokens, blocks, back
                 hf = h.float()
                 N, H4, W4, C4 = hf.shape
                 style = self.style_vector(hf)
