@@ -384,6 +384,50 @@ int mstg_f16_plain_pack(const mstg_f16_plain_desc* d, const float* w, const floa
 int mstg_f16_plain_fwd(const mstg_f16_plain_desc* d, const void* blob, const void* x, void* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixed-precision training step of the plain Generator (csrc/train_f16_plain.hip): what pretrain.py:159-166 runs under
+ * torch.cuda.amp.autocast() on the layers of pretrain.py:60-97.  fp16 NHWC activations and activation gradients, fp16 MFMA,
+ * fp32 accumulation and statistics, fp32 master parameters and parameter gradients.  The forward convolutions and all input
+ * gradients are mstg_f16_plain_fwd launches (the input gradient of a k4 s2 p1 layer is the layer of the other kind on the same
+ * weight tensor); the entry points below are the rest.  Fixed summation order, no atomics.
+ * fstate: 2 floats on the device, {loss scale, 1 / loss scale}; istate: 3 ints, {skipped steps, good steps, last step ok}.
+ * Activation gradients carry the loss scale; every parameter gradient is written multiplied by fstate[1].
+ * P = N * H * W pixels of an NHWC fp16 tensor with C channels (a multiple of 8 up to 512).
+ * ---------------------------------------------------------------------------------------------- */
+/* (N,3,H,W) fp32 -> (N,H,W,8) fp16, channels 3..7 zero: the stem's input as its weight gradient reads it */
+int mstg_f16_train_image_nhwc8(const float* img, void* out, int N, int H, int W, void* stream);
+size_t mstg_f16_train_bn_workspace_bytes(size_t P, int C); /* for _bn_fwd, _bn_bwd and _bias_grad; 0 = unsupported */
+/* nn.BatchNorm2d in training mode + activation: mean / rstd [C] out (biased variance of z as stored, two-pass), running statistics
+ * (nullable) updated with the unbiased variance, y = act(gamma (z - mean) rstd + beta) rounded once to fp16 */
+int mstg_f16_train_bn_fwd(const void* z, const float* gamma, const float* beta, size_t P, int C, int act, float eps, float momentum,
+                          float* running_mean, float* running_var, float* mean, float* rstd, void* y, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* its backward: the activation mask is recomputed from z; dgamma / dbeta fp32 (times fstate[1]), dz fp16 */
+int mstg_f16_train_bn_bwd(const void* z, const void* dy, const float* gamma, const float* beta, const float* mean, const float* rstd,
+                          size_t P, int C, int act, const float* fstate, float* dgamma, float* dbeta, void* dz, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* dz = da * act'(a) from the OUTPUT a of a ReLU / LeakyReLU(0.2) (the stem has no norm); n fp16 elements, a multiple of 8 */
+int mstg_f16_train_act_bwd(const void* a, const void* da, void* dz, size_t n, int act, void* stream);
+size_t mstg_f16_train_loss_workspace_bytes(int N, int H, int W);
+/* y: the head's fp16 image (N,3,H,W); real, mask: fp32 (N,3,H,W); k = 1 - mask.  loss = mean |y k - real k| (unscaled, fp32);
+ * dz (N,H,W,8) fp16 = fstate[0] / numel * sign(y k - real k) * k * (1 - y^2), channels 3..7 zero */
+int mstg_f16_train_head_loss_bwd(const void* y, const float* real, const float* mask, int N, int H, int W, const float* fstate,
+                                 float* loss, void* dz, void* workspace, size_t workspace_bytes, void* stream);
+/* Weight gradient of a k4 s2 p1 layer of either kind.  S: the layer's small map (N,h,w,Cs), B: its big map (N,2h,2w,Cb), NHWC fp16;
+ * dW (Cs, CbOut, 4, 4) fp32 = fstate[1] * sum S[n][y][x][s] * B[n][2y+ky-1][2x+kx-1][b].  nn.Conv2d: S = dZ, B = X (dW is OIHW);
+ * nn.ConvTranspose2d: S = X, B = dZ (dW is IOHW).  CbOut <= Cb: channels of B that are padding (image / head: 3 of 8). */
+size_t mstg_f16_train_wgrad_workspace_bytes(int N, int h, int w, int Cs, int Cb, int CbOut); /* 0 = unsupported */
+int mstg_f16_train_wgrad(const void* S, const void* B, int N, int h, int w, int Cs, int Cb, int CbOut, const float* fstate, float* dW,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* out[c] = fstate[1] * sum over pixels of dz[p][c], c < Cvalid: the bias gradients of the stem and the head */
+int mstg_f16_train_bias_grad(const void* dz, size_t P, int C, int Cvalid, const float* fstate, float* out, void* workspace,
+                             size_t workspace_bytes, void* stream);
+/* norm: pre-clip gradient norm (device).  Finite: istate = {., +1, 1}.  Else istate = {+1, ., 0} and the loss scale is halved. */
+int mstg_f16_train_scale_update(const float* norm, float* fstate, int* istate, void* stream);
+/* mstg_adam_step_flat at step = step_base + istate[1]; does nothing when istate[2] == 0 */
+int mstg_f16_train_adam(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                        int step_base, const int* istate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * fp16 inference of StructuralTransformerBlock (structural_transformer.py:55-74), csrc/infer_f16_block.hip: fp16 storage and MFMA
  * operands, fp32 accumulation / statistics / softmax, tokens (N, L, C) token-major.  Fixed summation order, no atomics: image i
  * of a batch equals the same image run alone.

@@ -128,6 +128,18 @@ SIGNATURES = {
     "mstg_f16_plain_plan_bytes": (_sz, [_pp]),
     "mstg_f16_plain_pack": (_i, [_pp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "mstg_f16_plain_fwd": (_i, [_pp, _vp, _vp, _vp, _vp]),
+    "mstg_f16_train_image_nhwc8": (_i, [_fp, _vp, _i, _i, _i, _vp]),
+    "mstg_f16_train_bn_workspace_bytes": (_sz, [_sz, _i]),
+    "mstg_f16_train_bn_fwd": (_i, [_vp, _fp, _fp, _sz, _i, _i, _f, _f, _fp, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "mstg_f16_train_bn_bwd": (_i, [_vp, _vp, _fp, _fp, _fp, _fp, _sz, _i, _i, _fp, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "mstg_f16_train_act_bwd": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
+    "mstg_f16_train_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_f16_train_head_loss_bwd": (_i, [_vp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp, _vp, _sz, _vp]),
+    "mstg_f16_train_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "mstg_f16_train_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _fp, _fp, _vp, _sz, _vp]),
+    "mstg_f16_train_bias_grad": (_i, [_vp, _sz, _i, _i, _fp, _fp, _vp, _sz, _vp]),
+    "mstg_f16_train_scale_update": (_i, [_fp, _fp, _vp, _vp]),
+    "mstg_f16_train_adam": (_i, [_fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _i, _vp, _vp]),
     "mstg_f16_linear_plan_bytes": (_sz, [_i, _i]),
     "mstg_f16_linear_pack": (_i, [_fp, _fp, _i, _i, _vp, _sz, _vp]),
     "mstg_f16_linear_fwd": (_i, [_vp, _vp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -61,13 +61,18 @@ class PackedPlainConv:
         if nbytes == 0:
             raise RuntimeError(f"mstg_hip fp16 inference: unsupported layer (kind {kind}, {self.Cin}->{self.Cout}, k{self.K}): "
                                + lib.mstg_last_error().decode())
+        self.blob = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        self.repack(weight, scale, shift)
+
+    def repack(self, weight, scale, shift):
+        """Pack again from tensors of the shapes the layer was built with (training: once per optimizer step)."""
         from .ops import _p, _stream
-        dev = weight.device
+        dev = self.blob.device
         keep = [weight.detach().float().contiguous()]
         keep += [None if t is None else t.detach().float().contiguous().to(dev) for t in (scale, shift)]
-        self.blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mstg_f16_plain_pack(C.byref(d), _p(keep[0]), _p(keep[1]), _p(keep[2]), _p(self.blob), nbytes, _stream()),
-                   "mstg_f16_plain_pack")
+        d = self.desc(1, 16, 16)
+        _lib.check(_lib.load().mstg_f16_plain_pack(C.byref(d), _p(keep[0]), _p(keep[1]), _p(keep[2]), _p(self.blob),
+                                                   self.blob.numel(), _stream()), "mstg_f16_plain_pack")
         self._keep = keep  # the pack kernel reads them asynchronously
 
     def desc(self, N, H, W) -> F16PlainDesc:

@@ -34,7 +34,8 @@ class FlatAdam:
         self.grad = torch.zeros(off, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros(off, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.step_count = 0
+        self._step_base = 0
+        self._device_state = None
         with torch.no_grad():
             for p, o in zip(self.params, self.offsets):
                 view = self.flat[o:o + p.numel()].view_as(p)
@@ -42,6 +43,27 @@ class FlatAdam:
                 p.data = view
                 p._mstg_flat = self.flat  # ops' filter-pack cache watches this buffer's version counter too
         self._attach_grads()
+
+    # The step count is a host integer, plus -- once a mixed-precision step has attached its device state -- the good steps the
+    # device has counted since (a step whose gradient was not finite is skipped ON THE DEVICE, pretrain.PretrainStep(amp=True)).
+    @property
+    def step_count(self) -> int:
+        return self._step_base + (0 if self._device_state is None else int(self._device_state[1]))
+
+    @step_count.setter
+    def step_count(self, value: int):
+        self._step_base = int(value)
+        if self._device_state is not None:
+            self._device_state[1] = 0
+
+    @property
+    def step_base(self) -> int:
+        """The host part of ``step_count`` (no device read)."""
+        return self._step_base
+
+    def attach_device_state(self, istate):
+        """istate: int32 device tensor {skipped steps, good steps, last step ok} of train_plain; its good steps count from now."""
+        self._device_state = istate
 
     def _attach_grads(self):
         for p, o in zip(self.params, self.offsets):

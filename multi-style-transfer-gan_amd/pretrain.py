@@ -10,8 +10,11 @@ What differs, deliberately:
   * ``train`` keeps the reference's loop (two domains per epoch, Adam 2e-4 / (0.5, 0.999), CosineAnnealingLR(T_max=num_epochs,
     eta_min=1e-6), clip_grad_norm_(1.0), checkpoint every 50 epochs with the reference's keys) but steps through
     ``PretrainStep``: HIP forward / backward, masked L1 loss, gradient clipping and Adam on one flat buffer.  Arithmetic is fp32
-    (the reference's ``autocast`` is a no-op on its CPU path, the parity target); errors propagate instead of being swallowed
-    by the reference's blanket ``except`` (pretrain.py:221-225).
+    by default (the reference's ``autocast`` is a no-op on its CPU path, the parity target); ``amp=True`` is what the
+    reference's ``torch.cuda.amp.autocast()`` loop (pretrain.py:160-166) is on a GPU: fp16 activations and fp16 MFMA with fp32
+    accumulation, fp32 master weights, plus a loss scale (mstg_hip/train_plain.py -- the reference's loop has none and its
+    gradient underflows at realistic batch sizes).  Errors propagate instead of being swallowed by the reference's blanket
+    ``except`` (pretrain.py:221-225).
 """
 from __future__ import annotations
 
@@ -137,15 +140,77 @@ class CosineLR:
 
 class PretrainStep:
     """One optimisation step of pretrain.py:154-166: zero_grad, forward, L1(gen * (1 - mask), real * (1 - mask)), backward,
-    clip_grad_norm_(1.0), Adam step.  Returns the loss as a 0-dim device tensor (no host sync)."""
+    clip_grad_norm_(1.0), Adam step.  Returns the loss as a 0-dim device tensor (no host sync).
 
-    def __init__(self, generator, lr=2e-4, max_norm=1.0):
+    ``amp=True`` runs forward and backward on the fp16 kernels (mstg_hip/train_plain.py): parameters stay the module's fp32
+    tensors, gradients are written unscaled in fp32 into the optimizer's flat buffer.  ``loss_scale``: ``"auto"`` =
+    2 ** ceil(log2(numel of the loss)), or a power of two (1.0: the reference's literal behaviour).  A step whose pre-clip gradient
+    norm is not finite is skipped on the device (parameters and Adam state untouched), counted in ``skipped_steps``, and halves
+    the scale; ``loss_scale`` shows the current value.  Reading either attribute waits for the device; the step does not."""
+
+    def __init__(self, generator, lr=2e-4, max_norm=1.0, amp=False, loss_scale="auto"):
+        self.amp = bool(amp)
+        if self.amp:
+            from mstg_hip import train_plain
+            train_plain.check_generator(generator)  # before anything touches a device
+            if loss_scale != "auto":
+                loss_scale = train_plain.check_loss_scale(loss_scale)
+            if not generator.training:
+                raise RuntimeError("PretrainStep(amp=True) needs the generator in training mode (BatchNorm runs on batch statistics)")
+        self._loss_scale_arg = loss_scale
         self.generator = generator
         self.optimizer = FlatAdam(generator.parameters(), lr=lr, betas=(0.5, 0.999))
         self.max_norm = max_norm
         self.last_grad_norm = None
+        self._plan = self._state = None
+        self._stale = False
+
+    @property
+    def loss_scale(self):
+        """The current loss scale (None before the first ``amp=True`` step of an ``"auto"`` scale)."""
+        if self._state is None:
+            return None if self._loss_scale_arg == "auto" else self._loss_scale_arg
+        return float(self._state[0][0])
+
+    @loss_scale.setter
+    def loss_scale(self, value):
+        from mstg_hip import train_plain
+        value = train_plain.check_loss_scale(value)
+        self._loss_scale_arg = value
+        if self._state is not None:
+            self._state[0].copy_(torch.tensor([value, 1.0 / value], dtype=torch.float32))
+
+    @property
+    def skipped_steps(self) -> int:
+        return 0 if self._state is None else int(self._state[1][0])
+
+    def _amp_step(self, masked_imgs, real_imgs, masks):
+        from mstg_hip import train_plain
+        if not self.generator.training:
+            raise RuntimeError("PretrainStep(amp=True) needs the generator in training mode (BatchNorm runs on batch statistics)")
+        if self._state is None:
+            scale = self._loss_scale_arg
+            if scale == "auto":
+                scale = train_plain.auto_loss_scale(masked_imgs.numel())
+            self._state = train_plain.make_state(scale, masked_imgs.device)
+            self.optimizer.attach_device_state(self._state[1])
+        if self._plan is None:
+            self._plan = train_plain.PlainGeneratorTrainPlan(self.generator)
+        elif self._stale:
+            self._plan.repack()
+        fstate, istate = self._state
+        self.optimizer.zero_grad()
+        self.optimizer.check_views()
+        loss = self._plan.forward_backward(masked_imgs, real_imgs, masks, fstate)
+        self.last_grad_norm = ops.clip_grad_norm_flat_(self.optimizer.grad, self.max_norm)
+        train_plain.scale_update(self.last_grad_norm, fstate, istate)
+        train_plain.guarded_adam_step(self.optimizer, istate)
+        self._stale = True
+        return loss
 
     def __call__(self, masked_imgs, real_imgs, masks):
+        if self.amp:
+            return self._amp_step(masked_imgs, real_imgs, masks)
         self.optimizer.zero_grad()
         with ops.direct_param_grads():
             generated = self.generator(masked_imgs)
@@ -173,11 +238,11 @@ def load_checkpoint(path, generator, optimizer=None, scheduler=None, device=None
 
 
 def train(data_root, save_dir, num_epochs=200, batch_size=1, lr=2e-4, channels=64, datasets=None, log_every=10, resume_path=None,
-          continue_epochs=False, save_every=50):
+          continue_epochs=False, save_every=50, amp=False, loss_scale="auto"):
     """pretrain.py:99-230, and with ``resume_path`` pretrain_resume.py:134-157.  ``datasets`` = (monet_dataset, photo_dataset)
     overrides the directory-backed ones.  As in the reference, a resumed run restores model / optimizer / scheduler and reports
     ``start_epoch`` but its loop still counts from 0 (pretrain_resume.py:166); ``continue_epochs=True`` starts the loop at
-    ``start_epoch`` instead."""
+    ``start_epoch`` instead.  ``amp`` / ``loss_scale``: see ``PretrainStep``; the step object is kept as ``generator.pretrain_step``."""
     set_seed()
     if not torch.cuda.is_available():
         raise RuntimeError("pretrain.train (MI355X build) needs a GPU: there is no CPU path")
@@ -188,7 +253,8 @@ def train(data_root, save_dir, num_epochs=200, batch_size=1, lr=2e-4, channels=6
     monet_loader = DeviceLoader(datasets[0], batch_size=batch_size, shuffle=True, drop_last=True)
     photo_loader = DeviceLoader(datasets[1], batch_size=batch_size, shuffle=True, drop_last=True)
     generator = Generator(channels=channels).to(device)
-    step = PretrainStep(generator, lr=lr)
+    step = PretrainStep(generator, lr=lr, amp=amp, loss_scale=loss_scale)
+    generator.pretrain_step = step
     scheduler = CosineLR(step.optimizer, T_max=num_epochs, eta_min=1e-6)
     start_epoch = 0
     if resume_path is not None and os.path.exists(resume_path):
