@@ -49,6 +49,14 @@ def _flags() -> str:
     return " ".join(os.environ.get("MSTG_HIPCC_FLAGS", "").split())
 
 
+def compile_cmd(src: str) -> list:
+    """hipcc command line of one source, up to (not including) the output switches; tools/kernel_asm.py uses it too."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    extra = os.environ.get("MSTG_HIPCC_FLAGS", "").split()  # e.g. -DMSTG_STAMPS for tools/diag_stamps.py
+    base = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", *extra, "-I", INCLUDE, "-I", CSRC]
+    return base + PER_SOURCE_FLAGS.get(os.path.basename(src), [])
+
+
 def needs_build() -> bool:
     flags_file = os.path.join(OBJ, "flags.txt")
     if os.path.exists(flags_file) and open(flags_file).read() != _flags():
@@ -60,18 +68,16 @@ def build(force: bool = False, verbose: bool = True) -> str:
     if not force and not needs_build():
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    extra = os.environ.get("MSTG_HIPCC_FLAGS", "").split()  # e.g. -DMSTG_STAMPS for tools/diag_stamps.py
     os.makedirs(OBJ, exist_ok=True)
     flags_file = os.path.join(OBJ, "flags.txt")
-    flags = " ".join(extra)
+    flags = _flags()
     if not os.path.exists(flags_file) or open(flags_file).read() != flags:
         force = True
         open(flags_file, "w").write(flags)
-    base = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", *extra, "-I", INCLUDE, "-I", CSRC]
     todo = [s for s in sources() if force or _stale(_obj(s), [s] + headers())]
 
     def compile_one(src):
-        cmd = base + PER_SOURCE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", _obj(src)]
+        cmd = compile_cmd(src) + ["-c", src, "-o", _obj(src)]
         if verbose:
             print("[mstg_hip.build]", " ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)

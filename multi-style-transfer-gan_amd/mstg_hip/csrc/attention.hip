@@ -8,7 +8,7 @@
 //
 // Reference site replaced: enhanced_generator.py:22-35,39-42 (view/permute/contiguous window partition, two
 // F.normalize, two batched matmuls, softmax, inverse permute).
-#include "common.h"
+#include "lanes.h"
 
 namespace mstg {
 
@@ -49,29 +49,6 @@ __device__ __forceinline__ void tile_store(const f32x4 (&acc)[MF][NF], float* Dp
         for (int nf = 0; nf < NF; ++nf)
 #pragma unroll
             for (int r = 0; r < 4; ++r) Dp[(16 * mf + 4 * g + r) * d_sm + (16 * nf + i) * d_sn] = acc[mf][nf][r];
-}
-
-// Reductions over the 16 lanes that share lane >> 4 (one accumulator row lives in 16 lanes).  Written with DPP row operations
-// (quad_perm, row_half_mirror, row_mirror: VALU-speed cross-lane moves inside a row of 16): __shfl_xor compiles to
-// ds_bpermute_b32 here, a ~100-cycle LDS round trip per step, and the softmax / normalisation chains are four dependent
-// steps deep -- time stamps showed them to be 60 % of a 32-channel window's forward cycles.  Every lane ends with the result.
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_move<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_move<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_move<0x141>(v);  // row_half_mirror
-    v += dpp_move<0x140>(v);  // row_mirror
-    return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-    v = fmaxf(v, dpp_move<0xB1>(v));
-    v = fmaxf(v, dpp_move<0x4E>(v));
-    v = fmaxf(v, dpp_move<0x141>(v));
-    v = fmaxf(v, dpp_move<0x140>(v));
-    return v;
 }
 
 #ifdef MSTG_STAMPS
@@ -191,8 +168,8 @@ __device__ __forceinline__ void attn_forward_tiles(float* sm, int C, int lane) {
                 sk = fmaf(ka[v][e], ka[v][e], sk);
             }
         }
-        sq += dpp_move<0xB1>(sq); sq += dpp_move<0x4E>(sq);
-        sk += dpp_move<0xB1>(sk); sk += dpp_move<0x4E>(sk);
+        sq += dpp_mov<0xB1>(sq); sq += dpp_mov<0x4E>(sq);
+        sk += dpp_mov<0xB1>(sk); sk += dpp_mov<0x4E>(sk);
         const float iq = 1.f / fmaxf(sqrtf(sq), 1e-12f), ik = 1.f / fmaxf(sqrtf(sk), 1e-12f);
 #pragma unroll
         for (int v = 0; v < NV; ++v) {

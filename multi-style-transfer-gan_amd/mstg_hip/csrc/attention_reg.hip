@@ -23,39 +23,13 @@
 // b128 / b32 lane grouping of gfx950) and re-reads x and dy in their second layout with 4-byte loads (L1 hits).  Weight
 // gradients stay in MFMA accumulators across all windows of a wave; the four waves of a workgroup add their slabs in LDS in a
 // fixed order, so the second-stage reduce reads 1/16 of what the one-wave kernels produced.  tools/sim_attn_layout.py is the
-// lane-level model this data flow was checked with.
-#include "common.h"
+// lane-level model this data flow was checked with (its xg_sum is col4_sum of lanes.h, its row sums row16_sum).
+#include "lanes.h"
 #include <stdlib.h>
 
 namespace mstg {
 
 namespace {
-
-template <int CTRL>
-__device__ __forceinline__ float dppm(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// sum over the 16 lanes of a DPP row (= the lanes sharing g); every lane ends with the result
-__device__ __forceinline__ float row_sum(float v) {
-    v += dppm<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dppm<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dppm<0x141>(v);  // row_half_mirror
-    v += dppm<0x140>(v);  // row_mirror
-    return v;
-}
-// sum over the 4 lanes sharing i = lane & 15 (lanes i, i+16, i+32, i+48); every lane ends with the result.
-// v_permlane16_swap exchanges the odd rows of its first operand with the even rows of its second, v_permlane32_swap the upper
-// half of the first with the lower half of the second: with both operands holding v, first + second is the xor-16 / xor-32 sum.
-// (Inline asm: the builtin's second result is mis-lowered by this hipcc; the s_nop covers the VALU-write -> permlane hazard.)
-__device__ __forceinline__ float xg_sum(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    v = a + b;
-    a = v;
-    b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-    return a + b;
-}
 
 __device__ __forceinline__ f32x4 splat(float v) { return f32x4{v, v, v, v}; }
 // 1 / max(sqrt(s), 1e-12) (F.normalize's denominator) and 1 / z as single v_rsq_f32 / v_rcp_f32 instructions (1 ulp): the IEEE-exact
@@ -208,8 +182,8 @@ __device__ __forceinline__ void softmax_chain(Chain<C>& ch) {
     f32x4 iq, ik;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        iq[r] = inv_norm(row_sum(sq[r]));
-        ik[r] = inv_norm(row_sum(sk[r]));
+        iq[r] = inv_norm(row16_sum(sq[r]));
+        ik[r] = inv_norm(row16_sum(sk[r]));
     }
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
@@ -237,7 +211,7 @@ __device__ __forceinline__ void softmax_chain(Chain<C>& ch) {
             for (int r = 0; r < 4; ++r) st[m][n][r] = __expf(st[m][n][r]);
             z += hsum(st[m][n]);
         }
-        const float inv = fast_rcp(xg_sum(z));
+        const float inv = fast_rcp(col4_sum(z));
 #pragma unroll
         for (int m = 0; m < NF; ++m) ch.pt[m][n] = st[m][n] * inv;
     }
@@ -566,7 +540,7 @@ __global__ __launch_bounds__(64 * WAVES, C == 16 ? 4 : WAVES / 4) void attn_reg_
             float d = 0.f;
 #pragma unroll
             for (int m = 0; m < NF; ++m) d += hsum(dSt[m][n1] * ch.pt[m][n1]);
-            d = xg_sum(d);
+            d = col4_sum(d);
 #pragma unroll
             for (int m = 0; m < NF; ++m) dSt[m][n1] = ch.pt[m][n1] * (dSt[m][n1] - splat(d));
         }
@@ -598,8 +572,8 @@ __global__ __launch_bounds__(64 * WAVES, C == 16 ? 4 : WAVES / 4) void attn_reg_
                 sq += hsum(qh_cp[f] * qh_cp[f]);
                 sk += hsum(kh_cp[f] * kh_cp[f]);
             }
-            iq2 = inv_norm(xg_sum(sq));
-            ik2 = inv_norm(xg_sum(sk));
+            iq2 = inv_norm(col4_sum(sq));
+            ik2 = inv_norm(col4_sum(sk));
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 qh_cp[f] *= iq2;
@@ -635,8 +609,8 @@ __global__ __launch_bounds__(64 * WAVES, C == 16 ? 4 : WAVES / 4) void attn_reg_
                 dq_dot += hsum(qh_cp[f] * dqh[f]);
                 dk_dot += hsum(kh_cp[f] * dkh[f]);
             }
-            dq_dot = xg_sum(dq_dot);
-            dk_dot = xg_sum(dk_dot);
+            dq_dot = col4_sum(dq_dot);
+            dk_dot = col4_sum(dk_dot);
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
                 dqkv[f] = (dqh[f] - qh_cp[f] * dq_dot) * iq2;
@@ -705,8 +679,8 @@ __global__ __launch_bounds__(64 * WAVES, C == 16 ? 4 : WAVES / 4) void attn_reg_
                     f32x4 a, b;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        a[e] = row_sum(ns1[cf][e]);
-                        b[e] = row_sum(ns2[cf][e]);
+                        a[e] = row16_sum(ns1[cf][e]);
+                        b[e] = row16_sum(ns2[cf][e]);
                     }
                     if (i == 0) {
                         *reinterpret_cast<f32x4*>(row + 16 * cf + 4 * g) = a;
@@ -746,7 +720,7 @@ __global__ __launch_bounds__(64 * WAVES, C == 16 ? 4 : WAVES / 4) void attn_reg_
                     }
 #pragma unroll
             for (int jf = 0; jf < 3 * NF; ++jf) {
-                const float v = xg_sum(gb[jf]);
+                const float v = col4_sum(gb[jf]);
                 if (g == 0) {
                     float* p = &sm[4 * C * C + 16 * jf + i];
                     *p = first ? v : *p + v;
@@ -754,7 +728,7 @@ __global__ __launch_bounds__(64 * WAVES, C == 16 ? 4 : WAVES / 4) void attn_reg_
             }
 #pragma unroll
             for (int f = 0; f < NF; ++f) {
-                const float v = xg_sum(gbp[f]);
+                const float v = col4_sum(gbp[f]);
                 if (g == 0) {
                     float* p = &sm[4 * C * C + 3 * C + 16 * f + i];
                     *p = first ? v : *p + v;
@@ -1018,7 +992,7 @@ __global__ __launch_bounds__(256, 1) void attn_big_bwd_kernel(const float* __res
                 float d = 0.f;
 #pragma unroll
                 for (int m = 0; m < NF; ++m) d += hsum(dSt[m][n1] * ch.pt[m][n1]);
-                d = xg_sum(d);
+                d = col4_sum(d);
 #pragma unroll
                 for (int m = 0; m < NF; ++m) dSt[m][n1] = ch.pt[m][n1] * (dSt[m][n1] - splat(d));
                 __builtin_amdgcn_sched_barrier(0);
@@ -1035,8 +1009,8 @@ __global__ __launch_bounds__(256, 1) void attn_big_bwd_kernel(const float* __res
                     sq += hsum(qh_cp[f] * qh_cp[f]);
                     sk += hsum(kh_cp[f] * kh_cp[f]);
                 }
-                iq2 = inv_norm(xg_sum(sq));
-                ik2 = inv_norm(xg_sum(sk));
+                iq2 = inv_norm(col4_sum(sq));
+                ik2 = inv_norm(col4_sum(sk));
 #pragma unroll
                 for (int f = 0; f < NF; ++f) {
                     qh_cp[f] *= iq2;
@@ -1077,8 +1051,8 @@ __global__ __launch_bounds__(256, 1) void attn_big_bwd_kernel(const float* __res
                     dq_dot += hsum(qh_cp[f] * dqh[f]);
                     dk_dot += hsum(kh_cp[f] * dkh[f]);
                 }
-                dq_dot = xg_sum(dq_dot);
-                dk_dot = xg_sum(dk_dot);
+                dq_dot = col4_sum(dq_dot);
+                dk_dot = col4_sum(dk_dot);
 #pragma unroll
                 for (int f = 0; f < NF; ++f) {
                     dqkv[f] = (dqh[f] - qh_cp[f] * dq_dot) * iq2;
@@ -1130,7 +1104,7 @@ __global__ __launch_bounds__(256, 1) void attn_big_bwd_kernel(const float* __res
                     float* row = nsum + (size_t)run * 2 * C;
 #pragma unroll
                     for (int cf = 0; cf < NF; ++cf) {
-                        const float a = xg_sum(ns1[cf]), b = xg_sum(ns2[cf]);
+                        const float a = col4_sum(ns1[cf]), b = col4_sum(ns2[cf]);
                         if (g == 0) {
                             row[16 * cf + i] = a;
                             row[C + 16 * cf + i] = b;
@@ -1224,7 +1198,7 @@ __global__ __launch_bounds__(256, 1) void attn_big_bwd_kernel(const float* __res
             for (int cf = 0; cf < NF; ++cf)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) out[(16 * jf + 4 * g + r) * C + 16 * cf + i] = gW[k][cf][r];
-            const float v = xg_sum(gb[k]);
+            const float v = col4_sum(gb[k]);
             if (g == 0) out[4 * C * C + 16 * jf + i] = v;
         }
     }
@@ -1236,24 +1210,13 @@ __global__ __launch_bounds__(256, 1) void attn_big_bwd_kernel(const float* __res
             for (int n1 = 0; n1 < NF; ++n1)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) out[3 * C * C + (16 * f + 4 * g + r) * C + 16 * n1 + i] = gWp[k][n1][r];
-            const float v = xg_sum(gbp[k]);
+            const float v = col4_sum(gbp[k]);
             if (g == 0) out[4 * C * C + 3 * C + 16 * f + i] = v;
         }
     }
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-static int reg_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 // C = 32 through the C = 64 code path (test switch: the two implementations of one chain check each other)
 static bool big32() {
     const char* e = env_get(ENV_ATTN_BIG32);
@@ -1265,14 +1228,14 @@ static bool use_big(int C) { return C == 64 || (C == 32 && big32()); }
 constexpr int bwd_waves(int C) { return C == 16 ? 4 : 8; }
 constexpr int bwd_wgs_per_cu(int C) { return C == 16 ? 4 : 1; }
 // most workgroups the backward uses (= slabs in its workspace)
-int attn_reg_bwd_blocks(int C) { return use_big(C) ? reg_cus() : reg_cus() * bwd_wgs_per_cu(C); }
+int attn_reg_bwd_blocks(int C) { return use_big(C) ? cu_count() : cu_count() * bwd_wgs_per_cu(C); }
 int attn_reg_bwd_waves(int C) { return use_big(C) ? 4 : bwd_waves(C); }
 
 template <int C>
 static int reg_fwd(const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* bp, float* y,
                    int N, int H, int W, hipStream_t st) {
     const int nwin = N * (H / 4) * (W / 4);
-    int nb = reg_cus() * fwd_waves_per_simd<C>();
+    int nb = cu_count() * fwd_waves_per_simd<C>();
     if (nb * 4 > nwin) nb = cdiv(nwin, 4);
     if (in_stats)
         MSTG_LAUNCH((attn_reg_fwd_kernel<C, true>), dim3(nb), dim3(256), 0, st, x, wqkv, bqkv, wp, bp, y, N, H, W, in_stats);
@@ -1313,7 +1276,7 @@ static int big_fwd(const float* x, const float* in_stats, const float* wqkv, con
     typedef BigLds<C> S;
     const size_t lds = (size_t)S::FWD_FLOATS * sizeof(float);
     const int nwin = N * (H / 4) * (W / 4);
-    int nb = reg_cus() * 2;
+    int nb = cu_count() * 2;
     if (nb * 4 > nwin) nb = cdiv(nwin, 4);
     static bool ready = false;
     if (!ready) {

@@ -65,6 +65,19 @@ enum EnvKnob {
 };
 const char* env_get(EnvKnob k);  // value as of the last refresh, nullptr when unset (runtime.hip)
 
+// ---- launch sizing (runtime.hip) -------------------------------------------------------------------------------------
+// Compute units of the current device as of the first call (256 when the query fails), cached for the life of the process.
+int cu_count();
+// Workgroups of 256 threads per CU a persistent kernel is launched with: what the CU holds of `kern` with `lds` bytes of
+// dynamic LDS (registers, LDS), clamped to 1..4; above 64 KB the kernel is first opted in to 160 KB of dynamic LDS.  The caller
+// keeps one static OccCache per launch site (or per slot of its kernel table), so a repeated launch costs two compares.
+struct OccCache {
+    const void* kern = nullptr;
+    size_t lds = 0;
+    int occ = 1;
+};
+int persistent_occupancy(OccCache& c, const void* kern, size_t lds);
+
 constexpr int WAVE = 64;
 
 // fp32-in / fp32-accumulate MFMA, 16x16 tile, K = 4 per instruction (v_mfma_f32_16x16x4_f32).

@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "igemm_args.h"
+#include "lanes.h"
 
 namespace mstg {
 
@@ -104,18 +105,6 @@ __device__ __forceinline__ void p32_fetch(const P32Args& a, const P32Plan& p, in
     }
 }
 
-template <int CTRL>
-__device__ __forceinline__ float p32_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float p32_row16_sum(float v) {
-    v += p32_dpp<0xB1>(v);
-    v += p32_dpp<0x4E>(v);
-    v += p32_dpp<0x141>(v);
-    v += p32_dpp<0x140>(v);
-    return v;
-}
-
 // STATS: the epilogue also sums what it stores (InstanceNorm statistics of the output without another pass over it); a.in_stats:
 // the source is the RAW tensor in front of an InstanceNorm + ReLU, normalised while the patch is committed to LDS (zero padding
 // applies to the normalised tensor, as in the reference where the convolution pads what the norm produced).
@@ -176,7 +165,7 @@ __global__ __launch_bounds__(256) void conv_p32_kernel(const P32Args a, const P3
         for (int f = 0; f < (STATS ? NF : 1); ++f)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float s1 = p32_row16_sum(ssum[f][q]), s2 = p32_row16_sum(ssq[f][q]);
+                const float s1 = row16_sum(ssum[f][q]), s2 = row16_sum(ssq[f][q]);
                 if (nl == 0) {
                     red[(wv * 2 + 0) * 16 * NF + 16 * f + 4 * g + q] = s1;
                     red[(wv * 2 + 1) * 16 * NF + 16 * f + 4 * g + q] = s2;
@@ -761,16 +750,8 @@ static void p32d_plan(const IGemmArgs& a, P32dPlan& p, int TH) {
 template <int RPW, int NPF>
 static int p32d_launch_t(const P32Args& a, const P32dPlan& p, int act, size_t lds, long tiles, hipStream_t st) {
     auto kern = conv_p32d_kernel<RPW, NPF>;
-    static int occ = 0;
-    static size_t occ_lds = 0;
-    if (!occ || occ_lds != lds) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int nb = 1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 256, lds) != hipSuccess || nb < 1) nb = 1;
-        occ = nb > 4 ? 4 : nb;
-        occ_lds = lds;
-    }
-    long g_ = 256L * occ;
+    static OccCache occ;
+    long g_ = 256L * persistent_occupancy(occ, reinterpret_cast<const void*>(kern), lds);
     if (g_ > tiles) g_ = (tiles + 7) & ~7L;
     MSTG_LAUNCH(kern, dim3((unsigned)g_), dim3(256), lds, st, a, p, act);
     MSTG_CHECK_LAUNCH("conv_p32d_kernel");
@@ -904,15 +885,8 @@ static int launch_p32i(const IGemmArgs& g, void* workspace, size_t workspace_byt
     MSTG_PACK_LAUNCH(p32i_pack_kernel, dim3(16), dim3(256), 0, st, p, g.w, g.bias, g.w_so, g.w_sr, g.Cr, (float*)a.wpk, (float*)a.bias);
     MSTG_CHECK_LAUNCH("p32i_pack_kernel");
     const size_t lds = (size_t)P32I_MAX_STEPS * 16 + (size_t)p.nsteps * 1024 + (size_t)p.PH * p.PW * 16;
-    static int occ = 0;
-    static size_t occ_lds = 0;
-    if (!occ || occ_lds != lds) {
-        int nb = 1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(conv_p32i_kernel), 256, lds) != hipSuccess || nb < 1) nb = 1;
-        occ = nb > 4 ? 4 : nb;
-        occ_lds = lds;
-    }
-    int occ_ = occ;
+    static OccCache occ;  // lds <= 16 * 16 + 16 * 1024 + 256 * P32I_NPX * 16 = 24832 bytes (p32i_eligible): never the opt-in above 64 KB
+    int occ_ = persistent_occupancy(occ, reinterpret_cast<const void*>(conv_p32i_kernel), lds);
     { const char* e = env_get(ENV_P32_OCC); if (e && atoi(e) >= 1 && atoi(e) < occ_) occ_ = atoi(e); }
     long g_ = 256L * occ_;
     if (g_ > tiles) g_ = (tiles + 7) & ~7L;
@@ -1034,20 +1008,10 @@ static int p32_launch_t(P32Args& a, const P32Plan& p, size_t lds, long tiles, hi
     auto kern = mode == 2 ? (p.wlds ? conv_p32_kernel<RPW, NF, NPF, true, 2> : conv_p32_kernel<RPW, NF, NPF, false, 2>)
               : mode == 1 ? (p.wlds ? conv_p32_kernel<RPW, NF, NPF, true, 1> : conv_p32_kernel<RPW, NF, NPF, false, 1>)
                           : (p.wlds ? conv_p32_kernel<RPW, NF, NPF, true, 0> : conv_p32_kernel<RPW, NF, NPF, false, 0>);
-    const void* kptr = reinterpret_cast<const void*>(kern);
     // persistent workgroups: what a CU really holds of this kernel at this LDS size (registers, LDS), at most 4.  One slot per
     // (filter in LDS, statistics) variant; a race between threads recomputes the same value.
-    static size_t c_lds_tab[6] = {0, 0, 0, 0, 0, 0};
-    static int c_occ_tab[6] = {0, 0, 0, 0, 0, 0};
-    const int slot = (p.wlds ? 1 : 0) + 2 * mode;
-    if (!c_occ_tab[slot] || c_lds_tab[slot] != lds) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(kptr, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int nb = 1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kptr, 256, lds) != hipSuccess || nb < 1) nb = 1;
-        c_lds_tab[slot] = lds;
-        c_occ_tab[slot] = nb > 4 ? 4 : nb;
-    }
-    int c_occ = c_occ_tab[slot];
+    static OccCache occ_tab[6];
+    int c_occ = persistent_occupancy(occ_tab[(p.wlds ? 1 : 0) + 2 * mode], reinterpret_cast<const void*>(kern), lds);
     { const char* e = env_get(ENV_P32_OCC); if (e && atoi(e) >= 1 && atoi(e) < c_occ) c_occ = atoi(e); }  // experiments: leave room for the other stream
     long g_ = 256L * c_occ;
     if (g_ > tiles) g_ = (tiles + 7) & ~7L;

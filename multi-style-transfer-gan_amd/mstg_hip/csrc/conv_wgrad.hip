@@ -967,21 +967,12 @@ __global__ __launch_bounds__(256, (MF * NW == 1 ? 4 : 1)) void wgrad_1x1_kernel(
 
 // *S in: the slabs the workspace holds (<= 1024); out: the workgroups launched = what the CUs hold at once (a persistent kernel with
 // 1024 workgroups at three per CU ran one full wave of 768 and a tail of 256: 16 -> 16 channels 3.5 -> 5.3 TB/s with the tail gone)
-static int w11_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return cus;
-}
-
 template <int MF, int NW>
 static int launch_wgrad_1x1(const WGradArgs& a, long P, int* S, hipStream_t st, const float* in_stats = nullptr) {
     const int NF = cdiv(a.Ch, 16), P1 = wgrad_1x1_tile(a.Cg, a.Ch);
     const size_t lds = (size_t)P1 * (w1x1_ld(MF) + w1x1_ld(NF)) * sizeof(float);
     {
+        // (not persistent_occupancy(): this site never opted in to more than 64 KB of dynamic LDS, and 20 -> 20 channels asks for 76.5 KB)
         static size_t c_lds = 0;
         static int c_occ = 0;
         if (c_lds != lds || !c_occ) {
@@ -990,7 +981,7 @@ static int launch_wgrad_1x1(const WGradArgs& a, long P, int* S, hipStream_t st, 
             c_occ = nb > 4 ? 4 : nb;
             c_lds = lds;
         }
-        const int fit = w11_cus() * c_occ;
+        const int fit = cu_count() * c_occ;
         if (*S > fit) *S = fit;
     }
     MSTG_LAUNCH((wgrad_1x1_kernel<MF, NW>), dim3(*S), dim3(256), lds, st, a.g, a.h, a.partial, P, a.Cg, a.g_ctot, a.g_coff, a.Ch,
@@ -1232,17 +1223,8 @@ static WpPlan wp_plan(const WGradArgs& a) {  // a: after plan_ts (tiles for TH =
     return p;
 }
 static int launch_wp(WGradArgs& a, WpPlan& p, hipStream_t st) {
-    static int occ = 0;
-    static size_t occ_lds = 0;
-    if (!occ || occ_lds != p.lds) {
-        const void* kptr = reinterpret_cast<const void*>(&wgrad_p32_kernel);
-        if (p.lds > 64 * 1024) (void)hipFuncSetAttribute(kptr, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int nb = 1;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kptr, 256, p.lds) != hipSuccess || nb < 1) nb = 1;
-        occ = nb > 4 ? 4 : nb;
-        occ_lds = p.lds;
-    }
-    int occ_ = occ;
+    static OccCache occ;
+    int occ_ = persistent_occupancy(occ, reinterpret_cast<const void*>(&wgrad_p32_kernel), p.lds);
     { const char* e = env_get(ENV_P32_OCC); if (e && atoi(e) >= 1 && atoi(e) < occ_) occ_ = atoi(e); }
     int S = (256 * occ_) / p.ny;
     if (S > p.S) S = p.S;

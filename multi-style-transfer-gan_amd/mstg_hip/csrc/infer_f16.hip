@@ -18,12 +18,8 @@
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "lanes.h"
 #include "infer_f16_wide.h"
-
-typedef _Float16 h16;
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 
 namespace mstg {
 
@@ -77,18 +73,6 @@ struct F16ConvArgs {
     int act;
     int dbg;  // experiments (MSTG_F16_DBG): 1 skip K-steps, 2 skip stores, 4 skip patch fetch, 8 skip commit
 };
-
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum_f(float v) {
-    v += dppf<0xB1>(v);
-    v += dppf<0x4E>(v);
-    v += dppf<0x141>(v);
-    v += dppf<0x140>(v);
-    return v;
-}
 
 // -------------------------------------------------------------------------------------------------------------------------
 // filter packing: fp32 PyTorch layouts -> [step][frag][lane][8] fp16, + fp32 bias vector padded to 16 * NF
@@ -343,7 +327,7 @@ __global__ __launch_bounds__(256, (NF == 1 && RPW <= 4 && NPF <= (SRC == 2 ? 4 :
         for (int f = 0; f < NF; ++f)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float s1 = row16_sum_f(ssum[f][q]), s2 = row16_sum_f(ssq[f][q]);
+                const float s1 = row16_sum(ssum[f][q]), s2 = row16_sum(ssq[f][q]);
                 if (nl == 0) {
                     red[(wv * 2 + 0) * 16 * NF + 16 * f + 4 * g + q] = s1;
                     red[(wv * 2 + 1) * 16 * NF + 16 * f + 4 * g + q] = s2;
@@ -420,7 +404,7 @@ __global__ __launch_bounds__(256, (NF == 1 && RPW <= 4 && NPF <= (SRC == 2 ? 4 :
                         if ((MASK >> f) & 1) {
 #pragma unroll
                             for (int r = 0; r < RPW; ++r)
-                                acc[r][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[f], bf[r], decltype(from_bias)::value ? b4[f] : acc[r][f], 0, 0, 0);
+                                acc[r][f] = mfma16x16x32_f16(af[f], bf[r], decltype(from_bias)::value ? b4[f] : acc[r][f]);
                         }
                 };
                 auto clip = [&](int s) { return s < s1 ? s : s1 - 1; };  // past the end: re-read the last step (loaded, never used)
@@ -589,7 +573,7 @@ __global__ __launch_bounds__(256) void conv1x1_f16_kernel(const F16ConvArgs a, c
         for (int f = 0; f < NF; ++f)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float s1 = row16_sum_f(ssum[f][q]), s2 = row16_sum_f(ssq[f][q]);
+                const float s1 = row16_sum(ssum[f][q]), s2 = row16_sum(ssq[f][q]);
                 if (nl == 0) {
                     red[(wv * 2 + 0) * 16 * NF + 16 * f + 4 * g + q] = s1;
                     red[(wv * 2 + 1) * 16 * NF + 16 * f + 4 * g + q] = s2;
@@ -664,7 +648,7 @@ __global__ __launch_bounds__(256) void conv1x1_f16_kernel(const F16ConvArgs a, c
 #pragma unroll
             for (int f = 0; f < NF; ++f)
 #pragma unroll
-                for (int r = 0; r < RPW; ++r) acc[r][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[s][f], bf[r][s], s == 0 ? b4[f] : acc[r][f], 0, 0, 0);
+                for (int r = 0; r < RPW; ++r) acc[r][f] = mfma16x16x32_f16(af[s][f], bf[r][s], s == 0 ? b4[f] : acc[r][f]);
         char* yimg = reinterpret_cast<char*>(a.y) + (size_t)n * a.Ho * a.Wo * a.Cout * 2;
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
@@ -1002,40 +986,29 @@ static int build_plan(const mstg_f16_conv_desc* d, F16Plan& p, PackTable& pt) {
 
 static size_t plan_blob_bytes(const F16Plan& p) { return 256 + (size_t)p.nwfrag * 64 * 16; }
 
-template <int RPW, int NF, int NPF>
-static int launch_conv(const F16ConvArgs& a, const F16Plan& p, int src, int dst, size_t lds, long grid /* tiles */, hipStream_t st, int* grid_out) {
-#define MSTG_F16_LAUNCH(SRC, DST)                                                                                          \
-    do {                                                                                                                  \
-        auto kern = p.wlds ? conv_f16_kernel<RPW, NF, SRC, DST, NPF, true> : conv_f16_kernel<RPW, NF, SRC, DST, NPF, false>;      \
-        const void* kptr = reinterpret_cast<const void*>(kern);                                                           \
-        /* persistent workgroups: what the CU really holds (registers, LDS), at most 4, a multiple of 8 in all */       \
-        static const void* c_kern = nullptr;                                                                              \
-        static size_t c_lds = 0;                                                                                          \
-        static int c_occ = 1;                                                                                             \
-        if (c_kern != kptr || c_lds != lds) {                                                                             \
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute(kptr, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            int nb = 1;                                                                                                   \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kptr, 256, lds) != hipSuccess || nb < 1) nb = 1;        \
-            c_occ = nb > 4 ? 4 : nb;                                                                                      \
-            c_kern = kptr;                                                                                                \
-            c_lds = lds;                                                                                                  \
-        }                                                                                                                 \
-        long g_ = 256L * c_occ;                                                                                           \
-        if (g_ > grid) g_ = (grid + 7) & ~7L;                                                                             \
-        if (a.partial && hipMemsetAsync(a.partial, 0, (size_t)a.N * g_ * 2 * 16 * NF * sizeof(float), st) != hipSuccess)   \
-            return fail_arg(MSTG_E_LAUNCH, "f16 conv: clearing the statistics partials failed");                           \
-        *grid_out = (int)g_;                                                                                              \
-        MSTG_LAUNCH(kern, dim3((unsigned)g_), dim3(256), lds, st, a, p);                                           \
-    } while (0)
-    if (src == 0 && dst == 0) MSTG_F16_LAUNCH(0, 0);
-    else if (src == 1 && dst == 0) MSTG_F16_LAUNCH(1, 0);
-    else if (src == 0 && dst == 1) MSTG_F16_LAUNCH(0, 1);
-    else if (src == 2 && dst == 0) MSTG_F16_LAUNCH(2, 0);
-    else if (src == 2 && dst == 1) MSTG_F16_LAUNCH(2, 1);
-    else return fail_arg(MSTG_E_UNSUPPORTED, "f16 conv: NCHW source and destination in one layer");
-#undef MSTG_F16_LAUNCH
+template <int RPW, int NF, int NPF, int SRC, int DST>
+static int launch_conv_sd(const F16ConvArgs& a, const F16Plan& p, size_t lds, long grid /* tiles */, hipStream_t st, int* grid_out) {
+    auto kern = p.wlds ? conv_f16_kernel<RPW, NF, SRC, DST, NPF, true> : conv_f16_kernel<RPW, NF, SRC, DST, NPF, false>;
+    // persistent workgroups: what the CU really holds (registers, LDS), at most 4, a multiple of 8 in all
+    static OccCache occ;
+    long g_ = 256L * persistent_occupancy(occ, reinterpret_cast<const void*>(kern), lds);
+    if (g_ > grid) g_ = (grid + 7) & ~7L;
+    if (a.partial && hipMemsetAsync(a.partial, 0, (size_t)a.N * g_ * 2 * 16 * NF * sizeof(float), st) != hipSuccess)
+        return fail_arg(MSTG_E_LAUNCH, "f16 conv: clearing the statistics partials failed");
+    *grid_out = (int)g_;
+    MSTG_LAUNCH(kern, dim3((unsigned)g_), dim3(256), lds, st, a, p);
     MSTG_CHECK_LAUNCH("conv_f16_kernel");
     return MSTG_OK;
+}
+
+template <int RPW, int NF, int NPF>
+static int launch_conv(const F16ConvArgs& a, const F16Plan& p, int src, int dst, size_t lds, long grid, hipStream_t st, int* grid_out) {
+    if (src == 0 && dst == 0) return launch_conv_sd<RPW, NF, NPF, 0, 0>(a, p, lds, grid, st, grid_out);
+    if (src == 1 && dst == 0) return launch_conv_sd<RPW, NF, NPF, 1, 0>(a, p, lds, grid, st, grid_out);
+    if (src == 0 && dst == 1) return launch_conv_sd<RPW, NF, NPF, 0, 1>(a, p, lds, grid, st, grid_out);
+    if (src == 2 && dst == 0) return launch_conv_sd<RPW, NF, NPF, 2, 0>(a, p, lds, grid, st, grid_out);
+    if (src == 2 && dst == 1) return launch_conv_sd<RPW, NF, NPF, 2, 1>(a, p, lds, grid, st, grid_out);
+    return fail_arg(MSTG_E_UNSUPPORTED, "f16 conv: NCHW source and destination in one layer");
 }
 
 template <int RPW, int NF>
@@ -1167,11 +1140,12 @@ extern "C" int mstg_f16_conv_fwd_res(const mstg_f16_conv_desc* d, const void* bl
         if (direct) {
             const int KS = (d->Cin + 31) / 32;
             auto go = [&](auto kern) -> int {
+                // ONE cache for the six kernels (they share a pointer type, so this lambda is instantiated once): the first one launched
+                // sizes the grid of all.  Kept as it is: the grid decides the summation order of the statistics partials.
                 static int occ = 0;
                 if (!occ) {
-                    int nb = 1;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 256, 0) != hipSuccess || nb < 1) nb = 1;
-                    occ = nb > 4 ? 4 : nb;
+                    OccCache c;
+                    occ = persistent_occupancy(c, reinterpret_cast<const void*>(kern), 0);
                 }
                 long g_ = 256L * occ;
                 if (g_ > grid) g_ = (grid + 7) & ~7L;
@@ -1260,8 +1234,6 @@ extern "C" int mstg_f16_norm_residual(const void* x, const void* residual, const
 //                    and the four lane groups; scores are bounded by +-16 (unit vectors over 16 pixels): no max subtraction
 //   P  [c1][c2]     probabilities, c2 contiguous;   O [pixel][c1] = P V;   Y = Wproj O + b -> 8-byte NHWC stores
 // -------------------------------------------------------------------------------------------------------------------------
-typedef _Float16 h16x4v __attribute__((ext_vector_type(4)));
-
 template <int C>
 struct AttnF16 {
     static constexpr int NB = C / 16;
@@ -1271,8 +1243,6 @@ struct AttnF16 {
     static constexpr bool WLDS = C > 32;       // weights in LDS (shared by the workgroup) instead of registers
 };
 constexpr int ATT_WPW = 16;  // windows per wave
-
-__device__ __forceinline__ f32x4 mfma16h(h16x4v a, h16x4v b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
 
 template <int C>
 __global__ __launch_bounds__(256) void attn_f16_kernel(const h16* __restrict__ x, const float* __restrict__ in_stats,
@@ -1286,17 +1256,17 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const h16* __restrict__ x
     h16* wl = reinterpret_cast<h16*>(smem);
     h16* tile = reinterpret_cast<h16*>(smem + (T::WLDS ? (size_t)T::NFRAG * 64 * 8 : 0)) + (size_t)wv * T::END;
     // ---- weights: registers (C <= 32) or LDS (C = 64) --------------------------------------------------------------------------
-    h16x4v wr[T::WLDS ? 1 : T::NFRAG];
+    h16x4 wr[T::WLDS ? 1 : T::NFRAG];
     if (T::WLDS) {
-        for (int e = tid; e < T::NFRAG * 64; e += 256) reinterpret_cast<h16x4v*>(wl)[e] = reinterpret_cast<const h16x4v*>(wfrag)[e];
+        for (int e = tid; e < T::NFRAG * 64; e += 256) reinterpret_cast<h16x4*>(wl)[e] = reinterpret_cast<const h16x4*>(wfrag)[e];
         __syncthreads();
     } else {
 #pragma unroll
-        for (int f = 0; f < T::NFRAG; ++f) wr[f] = reinterpret_cast<const h16x4v*>(wfrag)[f * 64 + l];
+        for (int f = 0; f < T::NFRAG; ++f) wr[f] = reinterpret_cast<const h16x4*>(wfrag)[f * 64 + l];
     }
-    auto wget = [&](int part, int f, int ks) -> h16x4v {
+    auto wget = [&](int part, int f, int ks) -> h16x4 {
         const int idx = (part * NB + f) * NB + ks;
-        if (T::WLDS) return reinterpret_cast<const h16x4v*>(wl)[idx * 64 + l];
+        if (T::WLDS) return reinterpret_cast<const h16x4*>(wl)[idx * 64 + l];
         return wr[T::WLDS ? 0 : idx];
     };
     float bq[NB], bk[NB];
@@ -1340,9 +1310,9 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const h16* __restrict__ x
             }
             *reinterpret_cast<h16x8*>(&Xs[p * T::LDX + 8 * o]) = v;
         }
-        h16x4v xa[NB];
+        h16x4 xa[NB];
 #pragma unroll
-        for (int ks = 0; ks < NB; ++ks) xa[ks] = *reinterpret_cast<const h16x4v*>(&Xs[i * T::LDX + 16 * ks + 4 * g]);
+        for (int ks = 0; ks < NB; ++ks) xa[ks] = *reinterpret_cast<const h16x4*>(&Xs[i * T::LDX + 16 * ks + 4 * g]);
         // (1) q^T, k^T: D[pixel 4g+r][channel 16nf+i], normalised per pixel over channels, stored channel-major
 #pragma unroll
         for (int part = 0; part < 2; ++part) {
@@ -1352,21 +1322,21 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const h16* __restrict__ x
             for (int nf = 0; nf < NB; ++nf) {
                 acc[nf] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ks = 0; ks < NB; ++ks) acc[nf] = mfma16h(xa[ks], wget(part, nf, ks), acc[nf]);
+                for (int ks = 0; ks < NB; ++ks) acc[nf] = mfma16x16x16_f16(xa[ks], wget(part, nf, ks), acc[nf]);
                 const float b = part == 0 ? bq[nf] : bk[nf];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { acc[nf][r] += b; ss[r] += acc[nf][r] * acc[nf][r]; }
             }
             f32x4 inv;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) inv[r] = fminf(__builtin_amdgcn_rsqf(row16_sum_f(ss[r])), 1e12f);  // 1 / max(||.||, 1e-12)
+            for (int r = 0; r < 4; ++r) inv[r] = fminf(__builtin_amdgcn_rsqf(row16_sum(ss[r])), 1e12f);  // 1 / max(||.||, 1e-12)
             h16* dst = part == 0 ? QTs : KTs;
 #pragma unroll
             for (int nf = 0; nf < NB; ++nf) {
-                h16x4v hv;
+                h16x4 hv;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) hv[r] = (h16)(acc[nf][r] * inv[r]);
-                *reinterpret_cast<h16x4v*>(&dst[(16 * nf + i) * T::LDT + 4 * g]) = hv;
+                *reinterpret_cast<h16x4*>(&dst[(16 * nf + i) * T::LDT + 4 * g]) = hv;
             }
         }
         // (2) v: D[channel 16mf+4g+r][pixel i], stored pixel-major
@@ -1374,24 +1344,24 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const h16* __restrict__ x
         for (int mf = 0; mf < NB; ++mf) {
             f32x4 acc = bv[mf];
 #pragma unroll
-            for (int ks = 0; ks < NB; ++ks) acc = mfma16h(wget(2, mf, ks), xa[ks], acc);
-            h16x4v hv;
+            for (int ks = 0; ks < NB; ++ks) acc = mfma16x16x16_f16(wget(2, mf, ks), xa[ks], acc);
+            h16x4 hv;
 #pragma unroll
             for (int r = 0; r < 4; ++r) hv[r] = (h16)acc[r];
-            *reinterpret_cast<h16x4v*>(&Vs[i * T::LDX + 16 * mf + 4 * g]) = hv;
+            *reinterpret_cast<h16x4*>(&Vs[i * T::LDX + 16 * mf + 4 * g]) = hv;
         }
         // (3) S^T[c2][c1] and the softmax over c2, column block by column block
-        h16x4v ka[NB];
+        h16x4 ka[NB];
 #pragma unroll
-        for (int mf = 0; mf < NB; ++mf) ka[mf] = *reinterpret_cast<const h16x4v*>(&KTs[(16 * mf + i) * T::LDT + 4 * g]);
+        for (int mf = 0; mf < NB; ++mf) ka[mf] = *reinterpret_cast<const h16x4*>(&KTs[(16 * mf + i) * T::LDT + 4 * g]);
 #pragma unroll
         for (int nf = 0; nf < NB; ++nf) {
-            const h16x4v qb = *reinterpret_cast<const h16x4v*>(&QTs[(16 * nf + i) * T::LDT + 4 * g]);
+            const h16x4 qb = *reinterpret_cast<const h16x4*>(&QTs[(16 * nf + i) * T::LDT + 4 * g]);
             f32x4 s[NB];
             float sum = 0.f;
 #pragma unroll
             for (int mf = 0; mf < NB; ++mf) {
-                s[mf] = mfma16h(ka[mf], qb, f32x4{0.f, 0.f, 0.f, 0.f});
+                s[mf] = mfma16x16x16_f16(ka[mf], qb, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { s[mf][r] = __expf(s[mf][r]); sum += s[mf][r]; }
             }
@@ -1400,42 +1370,42 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const h16* __restrict__ x
             const float inv = __builtin_amdgcn_rcpf(sum);
 #pragma unroll
             for (int mf = 0; mf < NB; ++mf) {
-                h16x4v hv;
+                h16x4 hv;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) hv[r] = (h16)(s[mf][r] * inv);
-                *reinterpret_cast<h16x4v*>(&Ps[(16 * nf + i) * T::LDP + 16 * mf + 4 * g]) = hv;
+                *reinterpret_cast<h16x4*>(&Ps[(16 * nf + i) * T::LDP + 16 * mf + 4 * g]) = hv;
             }
         }
         // (4) O[pixel][c1] = sum_c2 P[c1][c2] V[pixel][c2]   (into the X tile: its fragments are in registers)
-        h16x4v vb[NB];
+        h16x4 vb[NB];
 #pragma unroll
-        for (int ks = 0; ks < NB; ++ks) vb[ks] = *reinterpret_cast<const h16x4v*>(&Vs[i * T::LDX + 16 * ks + 4 * g]);
+        for (int ks = 0; ks < NB; ++ks) vb[ks] = *reinterpret_cast<const h16x4*>(&Vs[i * T::LDX + 16 * ks + 4 * g]);
 #pragma unroll
         for (int mf = 0; mf < NB; ++mf) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < NB; ++ks)
-                acc = mfma16h(*reinterpret_cast<const h16x4v*>(&Ps[(16 * mf + i) * T::LDP + 16 * ks + 4 * g]), vb[ks], acc);
-            h16x4v hv;
+                acc = mfma16x16x16_f16(*reinterpret_cast<const h16x4*>(&Ps[(16 * mf + i) * T::LDP + 16 * ks + 4 * g]), vb[ks], acc);
+            h16x4 hv;
 #pragma unroll
             for (int r = 0; r < 4; ++r) hv[r] = (h16)acc[r];
-            *reinterpret_cast<h16x4v*>(&Xs[i * T::LDX + 16 * mf + 4 * g]) = hv;
+            *reinterpret_cast<h16x4*>(&Xs[i * T::LDX + 16 * mf + 4 * g]) = hv;
         }
         // (5) y = Wproj O + b
-        h16x4v ob[NB];
+        h16x4 ob[NB];
 #pragma unroll
-        for (int ks = 0; ks < NB; ++ks) ob[ks] = *reinterpret_cast<const h16x4v*>(&Xs[i * T::LDX + 16 * ks + 4 * g]);
+        for (int ks = 0; ks < NB; ++ks) ob[ks] = *reinterpret_cast<const h16x4*>(&Xs[i * T::LDX + 16 * ks + 4 * g]);
         const int yy = 4 * wy + (i >> 2), xx = 4 * wx + (i & 3);
         h16* yp = y + img + ((size_t)yy * W + xx) * C + 4 * g;
 #pragma unroll
         for (int mf = 0; mf < NB; ++mf) {
             f32x4 acc = bp[mf];
 #pragma unroll
-            for (int ks = 0; ks < NB; ++ks) acc = mfma16h(wget(3, mf, ks), ob[ks], acc);
-            h16x4v hv;
+            for (int ks = 0; ks < NB; ++ks) acc = mfma16x16x16_f16(wget(3, mf, ks), ob[ks], acc);
+            h16x4 hv;
 #pragma unroll
             for (int r = 0; r < 4; ++r) hv[r] = (h16)acc[r];
-            *reinterpret_cast<h16x4v*>(yp + 16 * mf) = hv;
+            *reinterpret_cast<h16x4*>(yp + 16 * mf) = hv;
         }
     }
 }
@@ -1451,7 +1421,6 @@ __global__ __launch_bounds__(256) void attn_f16_kernel(const h16* __restrict__ x
 // ranges, the next window's pixels in flight behind the current chain.  Rounding points are attn_f16_kernel's (q^, k^, v, P, O in fp16;
 // accumulation, norms and softmax in fp32).
 // -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ h16x4v cvt4(f32x4 v) { return h16x4v{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]}; }
 __device__ __forceinline__ float xg_sum_f(float v) {  // sum over the four lanes sharing i = lane & 15
     v += __shfl_xor(v, 16, 64);
     v += __shfl_xor(v, 32, 64);
@@ -1466,17 +1435,17 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
     constexpr bool WLDS = C > 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, l = tid & 63, i = l & 15, g = l >> 4;
-    h16x4v wr[WLDS ? 1 : NFRAG];
+    h16x4 wr[WLDS ? 1 : NFRAG];
     if (WLDS) {
-        for (int e = tid; e < NFRAG * 64; e += 256) reinterpret_cast<h16x4v*>(smem)[e] = reinterpret_cast<const h16x4v*>(wfrag)[e];
+        for (int e = tid; e < NFRAG * 64; e += 256) reinterpret_cast<h16x4*>(smem)[e] = reinterpret_cast<const h16x4*>(wfrag)[e];
         __syncthreads();
     } else {
 #pragma unroll
-        for (int f = 0; f < NFRAG; ++f) wr[f] = reinterpret_cast<const h16x4v*>(wfrag)[f * 64 + l];
+        for (int f = 0; f < NFRAG; ++f) wr[f] = reinterpret_cast<const h16x4*>(wfrag)[f * 64 + l];
     }
-    auto wget = [&](int part, int f, int ks) -> h16x4v {  // lane (i, g): W[part * C + 16 f + i][16 ks + 4 g + j]
+    auto wget = [&](int part, int f, int ks) -> h16x4 {  // lane (i, g): W[part * C + 16 f + i][16 ks + 4 g + j]
         const int idx = (part * NB + f) * NB + ks;
-        if (WLDS) return reinterpret_cast<const h16x4v*>(smem)[idx * 64 + l];
+        if (WLDS) return reinterpret_cast<const h16x4*>(smem)[idx * 64 + l];
         return wr[WLDS ? 0 : idx];
     };
     const int nwx = W / 4, nwy = H / 4, nwin = N * nwx * nwy;
@@ -1506,10 +1475,10 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
     // address = wave-uniform window offset (scalar registers) + this lane's constant offset inside a window: no vector arithmetic per window
     const unsigned lane_off = (unsigned)(((i >> 2) * W + (i & 3)) * C + 4 * g);
     auto win_off = [&](const Walk& c) -> size_t { return (((size_t)c.n * H + 4 * c.wy) * W + 4 * c.wx) * C; };
-    auto fetch = [&](h16x4v (&t)[NB], const Walk& c) {
+    auto fetch = [&](h16x4 (&t)[NB], const Walk& c) {
         const h16* p = x + win_off(c) + lane_off;
 #pragma unroll
-        for (int h = 0; h < NB; ++h) t[h] = *reinterpret_cast<const h16x4v*>(p + 16 * h);
+        for (int h = 0; h < NB; ++h) t[h] = *reinterpret_cast<const h16x4*>(p + 16 * h);
     };
     // normalise-on-load constants of the current image: (x - mean) * rstd = x * sc + nb for this lane's 4 channels per fragment
     f32x4 sc[NB], nbv[NB];
@@ -1518,13 +1487,13 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
     // costs 12 % at C = 32 (a wave per SIMD less) -- at 155 / 240 VALU instructions per window against 6 / 24 MFMAs the kernel is bound
     // by the vector pipe (row sums of the two F.normalize, conversions, softmax), not by loads in flight.
     constexpr int DEPTH = 1;
-    h16x4v nxt[DEPTH][NB];
+    h16x4 nxt[DEPTH][NB];
     int fwin = w0;
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d)
         if (fwin < w1) { fetch(nxt[d], fw); fw.next(nwx, nwy); ++fwin; }
     for (int win = w0; win < w1; win += DEPTH) {
-        h16x4v cur[DEPTH][NB];
+        h16x4 cur[DEPTH][NB];
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d)
 #pragma unroll
@@ -1537,7 +1506,7 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
         if (win + d >= w1) break;
         const int cn = pw.n, cwy = pw.wy, cwx = pw.wx;
         pw.next(nwx, nwy);
-        h16x4v xa[NB];
+        h16x4 xa[NB];
         if (in_stats) {  // (x - mean) * rstd, ReLU, as attn_f16_kernel applies it while staging: fp32 arithmetic, one rounding to fp16
             if (C == 64 || cn != stats_n) {  // wave-uniform: a wave's windows are contiguous, the image changes rarely (C = 64 has no
                 stats_n = cn;                // registers to keep the constants across windows: re-read per window there)
@@ -1566,9 +1535,9 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
             vt[f] = bv[f];
 #pragma unroll
             for (int h = 0; h < NB; ++h) {
-                q[f] = mfma16h(xa[h], wget(0, f, h), q[f]);
-                k[f] = mfma16h(xa[h], wget(1, f, h), k[f]);
-                vt[f] = mfma16h(wget(2, f, h), xa[h], vt[f]);
+                q[f] = mfma16x16x16_f16(xa[h], wget(0, f, h), q[f]);
+                k[f] = mfma16x16x16_f16(xa[h], wget(1, f, h), k[f]);
+                vt[f] = mfma16x16x16_f16(wget(2, f, h), xa[h], vt[f]);
             }
         }
         // F.normalize over channels: a row (g, r) is a pixel, its channels lie across the 16 lanes and NB fragments
@@ -1581,10 +1550,10 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
         f32x4 iq, ik;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            iq[r] = fminf(__builtin_amdgcn_rsqf(row16_sum_f(sq[r])), 1e12f);
-            ik[r] = fminf(__builtin_amdgcn_rsqf(row16_sum_f(sk[r])), 1e12f);
+            iq[r] = fminf(__builtin_amdgcn_rsqf(row16_sum(sq[r])), 1e12f);
+            ik[r] = fminf(__builtin_amdgcn_rsqf(row16_sum(sk[r])), 1e12f);
         }
-        h16x4v qh[NB], kh[NB], vh[NB];
+        h16x4 qh[NB], kh[NB], vh[NB];
 #pragma unroll
         for (int f = 0; f < NB; ++f) {
             qh[f] = cvt4(q[f] * iq);
@@ -1592,14 +1561,14 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
             vh[f] = cvt4(vt[f]);
         }
         // S^T[c2][c1] = sum_p k^[p][c2] q^[p][c1]; softmax over c2 (rows: registers + the four lane groups); |S| <= 1
-        h16x4v pt[NB][NB];
+        h16x4 pt[NB][NB];
 #pragma unroll
         for (int nn = 0; nn < NB; ++nn) {
             f32x4 st[NB];
             float z = 0.f;
 #pragma unroll
             for (int m = 0; m < NB; ++m) {
-                st[m] = mfma16h(kh[m], qh[nn], f32x4{0.f, 0.f, 0.f, 0.f});
+                st[m] = mfma16x16x16_f16(kh[m], qh[nn], f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { st[m][r] = __expf(st[m][r]); z += st[m][r]; }
             }
@@ -1608,12 +1577,12 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
             for (int m = 0; m < NB; ++m) pt[m][nn] = cvt4(st[m] * f32x4{inv, inv, inv, inv});
         }
         // O^T[c1][p] = sum_c2 P^T[c2][c1] v^T[c2][p];  Y^T[co][p] = bp[co] + sum_c1 Wp[co][c1] O^T[c1][p]
-        h16x4v oh[NB];
+        h16x4 oh[NB];
 #pragma unroll
         for (int n1 = 0; n1 < NB; ++n1) {
             f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int m = 0; m < NB; ++m) o = mfma16h(pt[m][n1], vh[m], o);
+            for (int m = 0; m < NB; ++m) o = mfma16x16x16_f16(pt[m][n1], vh[m], o);
             oh[n1] = cvt4(o);
         }
         h16* yp = y + (((size_t)cn * H + 4 * cwy) * W + 4 * cwx) * C + lane_off;
@@ -1621,8 +1590,8 @@ __global__ __launch_bounds__(256, C == 64 ? 2 : 3) void attn_f16r_kernel(const h
         for (int cf = 0; cf < NB; ++cf) {
             f32x4 acc = bp[cf];
 #pragma unroll
-            for (int n1 = 0; n1 < NB; ++n1) acc = mfma16h(wget(3, cf, n1), oh[n1], acc);
-            *reinterpret_cast<h16x4v*>(yp + 16 * cf) = cvt4(acc);
+            for (int n1 = 0; n1 < NB; ++n1) acc = mfma16x16x16_f16(wget(3, cf, n1), oh[n1], acc);
+            *reinterpret_cast<h16x4*>(yp + 16 * cf) = cvt4(acc);
         }
       }
     }
@@ -1673,15 +1642,8 @@ static int launch_attn_f16(const void* x, const float* in_stats, const void* blo
     const char* e_reg = getenv("MSTG_F16_ATTN_REG");
     if (!(e_reg && e_reg[0] == '0')) {  // register-resident chains (default); MSTG_F16_ATTN_REG=0: the LDS-tile kernel of round 2
         const size_t lds_r = T::WLDS ? (size_t)T::NFRAG * 64 * 8 : 0;
-        static int cus = 0;
-        if (!cus) {
-            int dev = 0;
-            hipDeviceProp_t pr;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount;
-            if (cus <= 0) cus = 256;
-        }
         const int nwin = N * (H / 4) * (W / 4);
-        int nb = cus * (C == 64 ? 2 : (C == 32 ? 4 : 8));  // persistent workgroups: what the kernel's registers allow per SIMD
+        int nb = cu_count() * (C == 64 ? 2 : (C == 32 ? 4 : 8));  // persistent workgroups: what the kernel's registers allow per SIMD
         if (nb * 4 > nwin) nb = cdiv(nwin, 4);
         MSTG_LAUNCH((attn_f16r_kernel<C>), dim3(nb), dim3(256), lds_r, st, (const h16*)x, in_stats, wfrag, bias, (h16*)y, N, H, W);
         MSTG_CHECK_LAUNCH("attn_f16r_kernel");

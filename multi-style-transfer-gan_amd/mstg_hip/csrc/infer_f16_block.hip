@@ -9,60 +9,9 @@
 //   flash attention softmax(q k^T / sqrt(D)) v over all L tokens of an image (:70), fp16 operands, fp32 online softmax
 //
 // Every sum runs in a fixed order that does not depend on the batch: image i of a batch equals the same image run alone.
-#include "common.h"
+#include "lanes.h"
 
 namespace mstg {
-
-typedef _Float16 bh16;
-typedef _Float16 bh16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 bh16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 bh16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x4 bmfma32(bh16x8 a, bh16x8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 bmfma16(bh16x4 a, bh16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
-}
-
-// max / sum of lanes l, l ^ 16, l ^ 32, l ^ 48 (the four accumulator row groups of one column): v_permlane16_swap + v_permlane32_swap
-// on two copies of v.  vdst = a, src = b, a = b = v: afterwards a holds the even row (half) and b the odd row (half) of each pair,
-// in every lane.  Inline asm: the builtins' two results of one input get folded into one by the compiler.  The s_nop covers the
-// "VALU write -> v_permlane read" hazard (2 wait states).
-__device__ __forceinline__ void bswap16(float& a, float& b) {
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ void bswap32(float& a, float& b) {
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ float bcol_max(float v) {
-    float a = v, b = v;
-    bswap16(a, b);
-    v = fmaxf(a, b);
-    a = b = v;
-    bswap32(a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float bcol_sum(float v) {  // (even row) + (odd row), then (lower half) + (upper half): the same in every lane
-    float a = v, b = v;
-    bswap16(a, b);
-    v = a + b;
-    a = b = v;
-    bswap32(a, b);
-    return a + b;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float bdpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float brow16_sum(float v) {
-    v += bdpp<0xB1>(v);
-    v += bdpp<0x4E>(v);
-    v += bdpp<0x141>(v);
-    v += bdpp<0x140>(v);
-    return v;
-}
 
 // ---- token GEMM (nn.Linear over tokens) --------------------------------------------------------------------------------------
 // y[t][co] = epi(sum_k x[t][k] W[co][k] + b[co]).  A = the filter (rows = output channels), B = the tokens (columns), so that a
@@ -70,8 +19,8 @@ __device__ __forceinline__ float brow16_sum(float v) {
 // whole rows once (Cin / 32 fragments) and walks every output channel, reading the filter from L2 (<= 256 KB, shared by all).
 // blob: bias fp32 [Cout] | W fp16 [Cout][Cin] (row-major, nn.Linear's layout).
 struct LinArgs {
-    const bh16* x;
-    const bh16* w;
+    const h16* x;
+    const h16* w;
     const float* bias;
     const float* res;  // fp32 [T][Cout] or null
     void* y;           // fp16 or fp32 [T][Cout]
@@ -80,10 +29,10 @@ struct LinArgs {
 };
 
 __global__ void blk_linear_pack_kernel(const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ bias,
-                                       bh16* __restrict__ wh, int Cout, long long total) {
+                                       h16* __restrict__ wh, int Cout, long long total) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < Cout) bias[e] = b ? b[e] : 0.f;
-    if (e < total) wh[e] = (bh16)w[e];
+    if (e < total) wh[e] = (h16)w[e];
 }
 
 template <int KS>  // Cin = 32 KS
@@ -92,12 +41,12 @@ __global__ __launch_bounds__(256) void blk_linear_f16_kernel(LinArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const long long tok = ((long long)blockIdx.x * 4 + wave) * 16 + i;
     const bool tv = tok < a.T;
-    bh16x8 xf[KS];
-    const bh16* xp = a.x + (tv ? tok : 0ll) * CIN + 8 * g;
+    h16x8 xf[KS];
+    const h16* xp = a.x + (tv ? tok : 0ll) * CIN + 8 * g;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        const bh16x8 v = *reinterpret_cast<const bh16x8*>(xp + 32 * ks);
-        xf[ks] = tv ? v : bh16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        const h16x8 v = *reinterpret_cast<const h16x8*>(xp + 32 * ks);
+        xf[ks] = tv ? v : h16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
     const int nf = a.Cout >> 4;  // a multiple of 4
     for (int f0 = 0; f0 < nf; f0 += 4) {
@@ -108,8 +57,8 @@ __global__ __launch_bounds__(256) void blk_linear_f16_kernel(LinArgs a) {
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const bh16x8 wf = *reinterpret_cast<const bh16x8*>(a.w + (size_t)(16 * (f0 + u) + i) * CIN + 32 * ks + 8 * g);
-                acc[u] = bmfma32(wf, xf[ks], acc[u]);
+                const h16x8 wf = *reinterpret_cast<const h16x8*>(a.w + (size_t)(16 * (f0 + u) + i) * CIN + 32 * ks + 8 * g);
+                acc[u] = mfma16x16x32_f16(wf, xf[ks], acc[u]);
             }
         if (!tv) continue;
 #pragma unroll
@@ -122,8 +71,8 @@ __global__ __launch_bounds__(256) void blk_linear_f16_kernel(LinArgs a) {
             const long long off = tok * a.Cout + co;
             if (a.res) v = *reinterpret_cast<const f32x4*>(a.res + off) + v;
             if (a.out_f16) {
-                const bh16x4 o = {(bh16)v[0], (bh16)v[1], (bh16)v[2], (bh16)v[3]};
-                *reinterpret_cast<bh16x4*>(reinterpret_cast<bh16*>(a.y) + off) = o;
+                const h16x4 o = {(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                *reinterpret_cast<h16x4*>(reinterpret_cast<h16*>(a.y) + off) = o;
             } else {
                 *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.y) + off) = v;
             }
@@ -140,7 +89,7 @@ __global__ __launch_bounds__(256) void blk_ln_mod_f16_kernel(const void* __restr
                                                              const float* __restrict__ spw, const float* __restrict__ spb,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              const float* __restrict__ gb, float* __restrict__ h_out,
-                                                             bh16* __restrict__ u, long long T, int L, int dim, float eps) {
+                                                             h16* __restrict__ u, long long T, int L, int dim, float eps) {
     const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
     const long long tok = (long long)blockIdx.x * 16 + grp;
     if (tok >= T) return;
@@ -156,7 +105,7 @@ __global__ __launch_bounds__(256) void blk_ln_mod_f16_kernel(const void* __restr
         if (c < nc) {
             const int ch = 64 * c + 4 * j;
             if constexpr (XF16) {
-                const bh16x4 x4 = *reinterpret_cast<const bh16x4*>(reinterpret_cast<const bh16*>(xv) + tok * dim + ch);
+                const h16x4 x4 = *reinterpret_cast<const h16x4*>(reinterpret_cast<const h16*>(xv) + tok * dim + ch);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[c][e] = (float)x4[e];
             } else {
@@ -176,14 +125,14 @@ __global__ __launch_bounds__(256) void blk_ln_mod_f16_kernel(const void* __restr
             s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
         }
     }
-    const float mean = brow16_sum(s) / (float)dim;
+    const float mean = row16_sum(s) / (float)dim;
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < BLN_MAXC; ++c)
         if (c < nc)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float d = v[c][e] - mean; q += d * d; }
-    const float rstd = rsqrtf(brow16_sum(q) / (float)dim + eps);
+    const float rstd = rsqrtf(row16_sum(q) / (float)dim + eps);
 #pragma unroll
     for (int c = 0; c < BLN_MAXC; ++c) {
         if (c >= nc) continue;
@@ -194,10 +143,10 @@ __global__ __launch_bounds__(256) void blk_ln_mod_f16_kernel(const void* __restr
             gm = *reinterpret_cast<const f32x4*>(gb + n * 2 * dim + ch);
             bm = *reinterpret_cast<const f32x4*>(gb + n * 2 * dim + dim + ch);
         }
-        bh16x4 o;
+        h16x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (bh16)(((v[c][e] - mean) * rstd * ga[e] + be[e]) * (1.f + gm[e]) + bm[e]);
-        *reinterpret_cast<bh16x4*>(u + tok * dim + ch) = o;
+        for (int e = 0; e < 4; ++e) o[e] = (h16)(((v[c][e] - mean) * rstd * ga[e] + be[e]) * (1.f + gm[e]) + bm[e]);
+        *reinterpret_cast<h16x4*>(u + tok * dim + ch) = o;
     }
 }
 
@@ -211,7 +160,7 @@ static int tmean_chunks(int L, int* chunk) {
     return cdiv(L, *chunk);
 }
 
-__global__ __launch_bounds__(256) void blk_token_mean_partial_kernel(const bh16* __restrict__ x, float* __restrict__ part, int L,
+__global__ __launch_bounds__(256) void blk_token_mean_partial_kernel(const h16* __restrict__ x, float* __restrict__ part, int L,
                                                                      int dim, int chunk, int nchunk) {
     __shared__ float red[256];
     const int t = threadIdx.x, n = blockIdx.y, ck = blockIdx.x;
@@ -264,11 +213,11 @@ struct BfCfg {
 };
 
 template <int D>
-__global__ __launch_bounds__(256) void blk_flash_f16_kernel(const bh16* __restrict__ qkv, bh16* __restrict__ out, int L, int heads,
+__global__ __launch_bounds__(256) void blk_flash_f16_kernel(const h16* __restrict__ qkv, h16* __restrict__ out, int L, int heads,
                                                             float cexp) {
     typedef BfCfg<D> CF;
-    __shared__ __attribute__((aligned(16))) bh16 Ks[BF_TK * CF::KST];
-    __shared__ __attribute__((aligned(16))) bh16 Vt[D * CF::VST];
+    __shared__ __attribute__((aligned(16))) h16 Ks[BF_TK * CF::KST];
+    __shared__ __attribute__((aligned(16))) h16 Vt[D * CF::VST];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i = lane & 15, g = lane >> 4;
     const int h = blockIdx.y, dim = heads * D;
     const long long ld = 3ll * dim, img = (long long)blockIdx.z * L;
@@ -276,18 +225,18 @@ __global__ __launch_bounds__(256) void blk_flash_f16_kernel(const bh16* __restri
     const bool qv = qi < L;
 
     // Q as the B operand: Q[qi][channels of k-slot]
-    bh16x8 qf8[CF::NQ];
-    bh16x4 qf4 = {0, 0, 0, 0};
+    h16x8 qf8[CF::NQ];
+    h16x4 qf4 = {0, 0, 0, 0};
     {
-        const bh16* qp = qkv + (img + (qv ? qi : 0)) * ld + h * D;
+        const h16* qp = qkv + (img + (qv ? qi : 0)) * ld + h * D;
         if constexpr (D == 16) {
-            const bh16x4 t = *reinterpret_cast<const bh16x4*>(qp + 4 * g);
-            qf4 = qv ? t : bh16x4{0, 0, 0, 0};
+            const h16x4 t = *reinterpret_cast<const h16x4*>(qp + 4 * g);
+            qf4 = qv ? t : h16x4{0, 0, 0, 0};
         } else {
 #pragma unroll
             for (int s = 0; s < CF::NQ; ++s) {
-                const bh16x8 t = *reinterpret_cast<const bh16x8*>(qp + 32 * s + 8 * g);
-                qf8[s] = qv ? t : bh16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                const h16x8 t = *reinterpret_cast<const h16x8*>(qp + 32 * s + 8 * g);
+                qf8[s] = qv ? t : h16x8{0, 0, 0, 0, 0, 0, 0, 0};
             }
         }
     }
@@ -321,11 +270,11 @@ __global__ __launch_bounds__(256) void blk_flash_f16_kernel(const bh16* __restri
         }
         if (tid < CF::VP) {
             const int kp = tid & 31, q = tid >> 5;
-            const bh16x8 a = __builtin_bit_cast(bh16x8, vreg0), b = __builtin_bit_cast(bh16x8, vreg1);
+            const h16x8 a = __builtin_bit_cast(h16x8, vreg0), b = __builtin_bit_cast(h16x8, vreg1);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const bh16x2 pr = {a[e], b[e]};
-                *reinterpret_cast<bh16x2*>(&Vt[(8 * q + e) * CF::VST + 2 * kp]) = pr;
+                const h16x2 pr = {a[e], b[e]};
+                *reinterpret_cast<h16x2*>(&Vt[(8 * q + e) * CF::VST + 2 * kp]) = pr;
             }
         }
     };
@@ -345,12 +294,12 @@ __global__ __launch_bounds__(256) void blk_flash_f16_kernel(const bh16* __restri
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             s[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const bh16* kp = &Ks[(16 * c + i) * CF::KST];
+            const h16* kp = &Ks[(16 * c + i) * CF::KST];
             if constexpr (D == 16) {
-                s[c] = bmfma16(*reinterpret_cast<const bh16x4*>(kp + 4 * g), qf4, s[c]);
+                s[c] = mfma16x16x16_f16(*reinterpret_cast<const h16x4*>(kp + 4 * g), qf4, s[c]);
             } else {
 #pragma unroll
-                for (int st = 0; st < CF::NQ; ++st) s[c] = bmfma32(*reinterpret_cast<const bh16x8*>(kp + 32 * st + 8 * g), qf8[st], s[c]);
+                for (int st = 0; st < CF::NQ; ++st) s[c] = mfma16x16x32_f16(*reinterpret_cast<const h16x8*>(kp + 32 * st + 8 * g), qf8[st], s[c]);
             }
         }
         if (k0 + BF_TK > L) {  // ragged last tile
@@ -365,7 +314,7 @@ __global__ __launch_bounds__(256) void blk_flash_f16_kernel(const bh16* __restri
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, s[c][r]);
-        tmax = bcol_max(tmax);
+        tmax = col4_max(tmax);
         const float mnew = fmaxf(m, tmax);                       // finite: every tile holds a valid key
         const float alpha = __builtin_amdgcn_exp2f((m - mnew) * cexp);  // m = -inf on the first tile: 0
         lsum *= alpha;
@@ -373,25 +322,25 @@ __global__ __launch_bounds__(256) void blk_flash_f16_kernel(const bh16* __restri
         for (int df = 0; df < CF::NDF; ++df) o[df] *= alpha;
         m = mnew;
         const float mc = m * cexp;
-        bh16x4 ph[4];
+        h16x4 ph[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float p = __builtin_amdgcn_exp2f(fmaf(s[c][r], cexp, -mc));
                 lsum += p;
-                ph[c][r] = (bh16)p;
+                ph[c][r] = (h16)p;
             }
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
-            const bh16x8 pb = {ph[2 * kb][0], ph[2 * kb][1], ph[2 * kb][2], ph[2 * kb][3],
+            const h16x8 pb = {ph[2 * kb][0], ph[2 * kb][1], ph[2 * kb][2], ph[2 * kb][3],
                                ph[2 * kb + 1][0], ph[2 * kb + 1][1], ph[2 * kb + 1][2], ph[2 * kb + 1][3]};
 #pragma unroll
             for (int df = 0; df < CF::NDF; ++df) {
-                const bh16* vp = &Vt[(16 * df + i) * CF::VST + 32 * kb + 4 * g];
-                const bh16x4 lo = *reinterpret_cast<const bh16x4*>(vp), hi = *reinterpret_cast<const bh16x4*>(vp + 16);
-                const bh16x8 va = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                o[df] = bmfma32(va, pb, o[df]);
+                const h16* vp = &Vt[(16 * df + i) * CF::VST + 32 * kb + 4 * g];
+                const h16x4 lo = *reinterpret_cast<const h16x4*>(vp), hi = *reinterpret_cast<const h16x4*>(vp + 16);
+                const h16x8 va = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                o[df] = mfma16x16x32_f16(va, pb, o[df]);
             }
         }
         __syncthreads();
@@ -400,14 +349,14 @@ __global__ __launch_bounds__(256) void blk_flash_f16_kernel(const bh16* __restri
             __syncthreads();
         }
     }
-    lsum = bcol_sum(lsum);
+    lsum = col4_sum(lsum);
     if (qv) {
         const float inv = 1.f / lsum;
-        bh16* op = out + (img + qi) * dim + h * D;
+        h16* op = out + (img + qi) * dim + h * D;
 #pragma unroll
         for (int df = 0; df < CF::NDF; ++df) {
-            const bh16x4 v = {(bh16)(o[df][0] * inv), (bh16)(o[df][1] * inv), (bh16)(o[df][2] * inv), (bh16)(o[df][3] * inv)};
-            *reinterpret_cast<bh16x4*>(op + 16 * df + 4 * g) = v;
+            const h16x4 v = {(h16)(o[df][0] * inv), (h16)(o[df][1] * inv), (h16)(o[df][2] * inv), (h16)(o[df][3] * inv)};
+            *reinterpret_cast<h16x4*>(op + 16 * df + 4 * g) = v;
         }
     }
 }
@@ -427,8 +376,8 @@ static void linear_launch(const LinArgs& a, unsigned grid, hipStream_t st) {
 template <int D>
 static void flash_launch(const void* qkv, void* out, int N, int L, int heads, hipStream_t st) {
     const float cexp = 1.4426950408889634f / sqrtf((float)D);
-    MSTG_LAUNCH((blk_flash_f16_kernel<D>), dim3(cdiv(L, BF_TQ), heads, N), dim3(256), 0, st, reinterpret_cast<const bh16*>(qkv),
-                reinterpret_cast<bh16*>(out), L, heads, cexp);
+    MSTG_LAUNCH((blk_flash_f16_kernel<D>), dim3(cdiv(L, BF_TQ), heads, N), dim3(256), 0, st, reinterpret_cast<const h16*>(qkv),
+                reinterpret_cast<h16*>(out), L, heads, cexp);
 }
 
 }  // namespace mstg
@@ -448,7 +397,7 @@ extern "C" int mstg_f16_linear_pack(const float* w, const float* b, int Cin, int
     if (!w || !blob) return fail_arg(MSTG_E_BADARG, "mstg_f16_linear_pack: null pointer");
     if (blob_bytes < mstg_f16_linear_plan_bytes(Cin, Cout)) return fail_arg(MSTG_E_BADARG, "mstg_f16_linear_pack: blob smaller than mstg_f16_linear_plan_bytes");
     float* bias = reinterpret_cast<float*>(blob);
-    bh16* wh = reinterpret_cast<bh16*>(bias + Cout);
+    h16* wh = reinterpret_cast<h16*>(bias + Cout);
     const long long total = (long long)Cout * Cin;
     MSTG_LAUNCH(blk_linear_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, b, bias, wh, Cout, total);
     MSTG_CHECK_LAUNCH("mstg_f16_linear_pack");
@@ -464,9 +413,9 @@ extern "C" int mstg_f16_linear_fwd(const void* blob, const void* x, const float*
     const long long T = (long long)N * L;
     if ((T + 63) / 64 >= (1ll << 31)) return fail_arg(MSTG_E_BADARG, "mstg_f16_linear_fwd: too many tokens");
     LinArgs a;
-    a.x = reinterpret_cast<const bh16*>(x);
+    a.x = reinterpret_cast<const h16*>(x);
     a.bias = reinterpret_cast<const float*>(blob);
-    a.w = reinterpret_cast<const bh16*>(a.bias + Cout);
+    a.w = reinterpret_cast<const h16*>(a.bias + Cout);
     a.res = residual;
     a.y = y;
     a.T = T;
@@ -498,10 +447,10 @@ extern "C" int mstg_f16_ln_mod_fwd(const void* x, int x_f16, const float* smap, 
     hipStream_t st = (hipStream_t)stream;
     if (x_f16)
         MSTG_LAUNCH(blk_ln_mod_f16_kernel<true>, dim3(grid), dim3(256), 0, st, x, smap, sp_w, sp_b, gamma, beta, gb, h_out,
-                    reinterpret_cast<bh16*>(u), T, L, dim, eps);
+                    reinterpret_cast<h16*>(u), T, L, dim, eps);
     else
         MSTG_LAUNCH(blk_ln_mod_f16_kernel<false>, dim3(grid), dim3(256), 0, st, x, smap, sp_w, sp_b, gamma, beta, gb, h_out,
-                    reinterpret_cast<bh16*>(u), T, L, dim, eps);
+                    reinterpret_cast<h16*>(u), T, L, dim, eps);
     MSTG_CHECK_LAUNCH("mstg_f16_ln_mod_fwd");
     return MSTG_OK;
 }
@@ -521,7 +470,7 @@ extern "C" int mstg_f16_token_mean(const void* x, float* out, int N, int L, int 
     int chunk;
     const int nchunk = tmean_chunks(L, &chunk);
     hipStream_t st = (hipStream_t)stream;
-    MSTG_LAUNCH(blk_token_mean_partial_kernel, dim3(nchunk, N), dim3(256), 0, st, reinterpret_cast<const bh16*>(x), (float*)workspace, L,
+    MSTG_LAUNCH(blk_token_mean_partial_kernel, dim3(nchunk, N), dim3(256), 0, st, reinterpret_cast<const h16*>(x), (float*)workspace, L,
                 dim, chunk, nchunk);
     MSTG_CHECK_LAUNCH("blk_token_mean_partial_kernel");
     MSTG_LAUNCH(blk_token_mean_reduce_kernel, dim3(N), dim3(256), 0, st, (const float*)workspace, out, L, dim, nchunk);

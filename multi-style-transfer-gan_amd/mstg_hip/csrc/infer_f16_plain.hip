@@ -30,13 +30,9 @@
 // Stem (encoder.0): the (N,3,H,W) fp32 image, K order (tap, 4 channels) = 64 with the fourth channel zero: one chunk.
 // Head (decoder.9): Cout = 3 padded to one fragment, tanh, (N,3,2H,2W) fp16 NCHW.
 // Fixed summation order, no atomics, no split-K.
-#include "common.h"
+#include "lanes.h"
 
 namespace mstg {
-
-typedef _Float16 ph16;
-typedef _Float16 ph16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 ph16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int PL_BK = 64;        // K elements per chunk
 constexpr int PL_MAXC = 512;
@@ -44,7 +40,7 @@ constexpr int PL_MAXC = 512;
 struct PlainArgs {
     const void* x;
     void* y;
-    const ph16* wpk;
+    const h16* wpk;
     const float* scale;
     const float* shift;
     long long M;          // GEMM columns: N * Hm * Wm
@@ -65,7 +61,7 @@ static inline int plain_ktot(const mstg_f16_plain_desc* d) { return (d->kind == 
 static inline int plain_nchunks(const mstg_f16_plain_desc* d) { return (plain_ktot(d) + PL_BK - 1) / PL_BK; }
 
 __global__ void plain_pack_kernel(const float* __restrict__ w, const float* __restrict__ scale, const float* __restrict__ shift,
-                                  float* __restrict__ bscale, float* __restrict__ bshift, ph16* __restrict__ out, int kind, int Cin,
+                                  float* __restrict__ bscale, float* __restrict__ bshift, h16* __restrict__ out, int kind, int Cin,
                                   int Cout, int CoutP, int cinp, int NT, int ntn, int nchunks, long long total) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < CoutP) {
@@ -95,7 +91,7 @@ __global__ void plain_pack_kernel(const float* __restrict__ w, const float* __re
             v = w[(((size_t)co * Cin + ci) * 4 + (tap >> 2)) * 4 + (tap & 3)];
         }
     }
-    out[e] = (ph16)v;
+    out[e] = (h16)v;
 }
 
 // ---- the convolution -----------------------------------------------------------------------------------------------------
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(256) void plain_conv_f16_kernel(PlainArgs a) {
             const int ty = q >> 1, tx0 = (q & 1) * 2;
 #pragma unroll
             for (int i = 0; i < NA; ++i) {
-                ph16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+                h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
                 const int iy = by[i] + ty - 1;
                 if (nbase[i] >= 0 && (unsigned)iy < (unsigned)a.H) {
 #pragma unroll
@@ -185,14 +181,14 @@ __global__ __launch_bounds__(256) void plain_conv_f16_kernel(PlainArgs a) {
                         if ((unsigned)ix < (unsigned)a.W) {
 #pragma unroll
                             for (int c = 0; c < 3; ++c)
-                                v[4 * t + c] = (ph16)img[((nbase[i] * 3 + c) * a.H + iy) * (long long)a.W + ix];
+                                v[4 * t + c] = (h16)img[((nbase[i] * 3 + c) * a.H + iy) * (long long)a.W + ix];
                         }
                     }
                 }
                 areg[i] = *reinterpret_cast<uint4*>(&v);
             }
         } else {
-            const ph16* src = reinterpret_cast<const ph16*>(a.x);
+            const h16* src = reinterpret_cast<const h16*>(a.x);
             const int g = ch * QN + q;
             const bool gok = g < a.kgroups;
             const int tap = (int)(((unsigned)g * (unsigned)a.cg_magic) >> 20), c = (g - tap * a.cg) * 8;  // g / cg, g < 2048
@@ -234,23 +230,23 @@ __global__ __launch_bounds__(256) void plain_conv_f16_kernel(PlainArgs a) {
         if (more) load_chunk(ch + 1);  // in flight under the MFMAs below
 #pragma unroll
         for (int s = 0; s < 2 * KC; ++s) {  // K-steps of 32 in k order
-            ph16x8 wf[NT], xf[MT];
+            h16x8 wf[NT], xf[MT];
 #pragma unroll
-            for (int f = 0; f < NT; ++f) wf[f] = *reinterpret_cast<const ph16x8*>(&Ws[buf * WST + ((s * NT + f) * 64 + lane) * 16]);
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-                xf[m] = *reinterpret_cast<const ph16x8*>(&As[buf * BM * AROW + (wave * 16 * MT + 16 * m + (lane & 15)) * AROW + 64 * s + 16 * (lane >> 4)]);
+            for (int f = 0; f < NT; ++f) wf[f] = *reinterpret_cast<const h16x8*>(&Ws[buf * WST + ((s * NT + f) * 64 + lane) * 16]);
 #pragma unroll
             for (int m = 0; m < MT; ++m)
+                xf[m] = *reinterpret_cast<const h16x8*>(&As[buf * BM * AROW + (wave * 16 * MT + 16 * m + (lane & 15)) * AROW + 64 * s + 16 * (lane >> 4)]);
 #pragma unroll
-                for (int f = 0; f < NT; ++f) acc[m][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[f], xf[m], acc[m][f], 0, 0, 0);
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int f = 0; f < NT; ++f) acc[m][f] = mfma16x16x32_f16(wf[f], xf[m], acc[m][f]);
         }
         if (more) store_chunk(buf ^ 1);  // last read before the barrier that closed chunk ch - 1
         __syncthreads();
     }
 
     // epilogue: acc[m][f][r] = D[cout = 16 NT nt + 16 f + 4 (lane >> 4) + r][pixel = m0 + 16 MT wave + 16 m + (lane & 15)]
-    ph16* y = reinterpret_cast<ph16*>(a.y);
+    h16* y = reinterpret_cast<h16*>(a.y);
     const int Ho = a.kind == 1 ? 2 * a.Hm : a.Hm, Wo = a.kind == 1 ? 2 * a.Wm : a.Wm;
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -274,10 +270,10 @@ __global__ __launch_bounds__(256) void plain_conv_f16_kernel(PlainArgs a) {
             if (a.dst_nchw) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (co + r < a.Cout) y[((n * a.Cout + co + r) * Ho + oy) * (long long)Wo + ox] = (ph16)v[r];
+                    if (co + r < a.Cout) y[((n * a.Cout + co + r) * Ho + oy) * (long long)Wo + ox] = (h16)v[r];
             } else {
-                const ph16x4 o = {(ph16)v[0], (ph16)v[1], (ph16)v[2], (ph16)v[3]};
-                *reinterpret_cast<ph16x4*>(y + ((n * Ho + oy) * (long long)Wo + ox) * a.Cout + co) = o;
+                const h16x4 o = {(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                *reinterpret_cast<h16x4*>(y + ((n * Ho + oy) * (long long)Wo + ox) * a.Cout + co) = o;
             }
         }
     }
@@ -346,7 +342,7 @@ extern "C" int mstg_f16_plain_pack(const mstg_f16_plain_desc* d, const float* w,
     const int CoutP = plain_coutp(d->Cout), NT = plain_nt(d->Cout);
     float* bscale = reinterpret_cast<float*>(blob);
     float* bshift = bscale + CoutP;
-    ph16* out = reinterpret_cast<ph16*>(bshift + CoutP);
+    h16* out = reinterpret_cast<h16*>(bshift + CoutP);
     const long long total = (long long)plain_filter_halves(d);
     const unsigned grid = (unsigned)((total + 255) / 256);
     MSTG_LAUNCH(plain_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, w, scale, shift, bscale, bshift, out, d->kind, d->Cin,
@@ -371,7 +367,7 @@ extern "C" int mstg_f16_plain_fwd(const mstg_f16_plain_desc* d, const void* blob
     a.y = y;
     a.scale = reinterpret_cast<const float*>(blob);
     a.shift = a.scale + CoutP;
-    a.wpk = reinterpret_cast<const ph16*>(a.shift + CoutP);
+    a.wpk = reinterpret_cast<const h16*>(a.shift + CoutP);
     a.M = M;
     a.H = d->H; a.W = d->W; a.Cin = d->Cin;
     a.Hm = Hm; a.Wm = Wm;

@@ -22,12 +22,8 @@
 // Every offset into an activation is 64-bit: at batch 64, 1024 x 1024 and 64 channels one tensor holds 2^32 elements.
 #include <hip/hip_fp16.h>
 
-#include "common.h"
+#include "lanes.h"
 #include "infer_f16_wide.h"
-
-typedef _Float16 h16;
-typedef _Float16 h16x4w __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8w __attribute__((ext_vector_type(8)));
 
 namespace mstg {
 
@@ -46,18 +42,6 @@ struct WGeom {
     int T;         // tap slots per block in the packed filter
     int chunks;    // Cin / 32
 };
-
-template <int CTRL>
-static __device__ __forceinline__ float dppw(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-static __device__ __forceinline__ float row16_sum_w(float v) {  // sum over the 16 lanes of a DPP row (row16_sum_f of infer_f16.hip)
-    v += dppw<0xB1>(v);
-    v += dppw<0x4E>(v);
-    v += dppw<0x141>(v);
-    v += dppw<0x140>(v);
-    return v;
-}
 
 // taps of block `blk`: how many, and the source offset (dy, dx) of tap t relative to (gy * stride, gx * stride)
 static __host__ __device__ __forceinline__ int wtaps(const WGeom& g, int blk) {
@@ -169,15 +153,15 @@ __global__ __launch_bounds__(256, 2) void conv_f16w_kernel(const F16WArgs a) {
     const size_t img = (size_t)n * a.H * a.W * G.Cin;
     const h16* xi = a.x + img;
     const h16* ri = SRC == 2 ? a.res + img : nullptr;
-    const h16x8w* wp = reinterpret_cast<const h16x8w*>(a.wpk) + (size_t)blk * G.T * G.chunks * NF * 64 + lane;
+    const h16x8* wp = reinterpret_cast<const h16x8*>(a.wpk) + (size_t)blk * G.T * G.chunks * NF * 64 + lane;
 
-    struct Ops { h16x8w af[NF]; h16x8w v[RPW]; h16x8w r[SRC == 2 ? RPW : 1]; unsigned ok; };
+    struct Ops { h16x8 af[NF]; h16x8 v[RPW]; h16x8 r[SRC == 2 ? RPW : 1]; unsigned ok; };
     // operands of K-step s: the filter fragments and this lane's 8 channels of the 4 pixels; out-of-image pixels read offset 0
     auto fetch = [&](int s, Ops& o) {
         const int chunk = s / ntap, t = s - chunk * ntap;
         int dy, dx;
         wtap_off(G, blk, t, dy, dx);
-        const h16x8w* w = wp + (size_t)(chunk * G.T + t) * NF * 64;
+        const h16x8* w = wp + (size_t)(chunk * G.T + t) * NF * 64;
 #pragma unroll
         for (int f = 0; f < NF; ++f) o.af[f] = w[f * 64];
         const int ix = gx * str + dx, cofs = 32 * chunk + 8 * g;
@@ -188,8 +172,8 @@ __global__ __launch_bounds__(256, 2) void conv_f16w_kernel(const F16WArgs a) {
             const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
             o.ok |= (unsigned)ok << r;
             const size_t off = ok ? ((size_t)iy * a.W + ix) * G.Cin + cofs : 0;
-            o.v[r] = *reinterpret_cast<const h16x8w*>(xi + off);
-            if (SRC == 2) o.r[r] = *reinterpret_cast<const h16x8w*>(ri + off);
+            o.v[r] = *reinterpret_cast<const h16x8*>(xi + off);
+            if (SRC == 2) o.r[r] = *reinterpret_cast<const h16x8*>(ri + off);
         }
     };
     f32x4 acc[RPW][NF];
@@ -203,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16w_kernel(const F16WArgs a) {
     fetch(0, cur);
     for (int s = 0; s < nsteps; ++s) {
         if (s + 1 < nsteps) fetch(s + 1, nxt);
-        h16x8w bf[RPW];
+        h16x8 bf[RPW];
         if (norm) {
             const int c0 = 32 * (s / ntap) + 8 * g;
             float sc[8], nb[8];
@@ -211,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16w_kernel(const F16WArgs a) {
             for (int c = 0; c < 8; ++c) { sc[c] = s_sc[c0 + c]; nb[c] = s_nb[c0 + c]; }
 #pragma unroll
             for (int r = 0; r < RPW; ++r) {
-                h16x8w w = cur.v[r];
+                h16x8 w = cur.v[r];
                 if (SRC == 2) {  // the arithmetic of f16_norm_residual_kernel, so that folding the pass changes no bit
 #pragma unroll
                     for (int c = 0; c < 8; ++c) w[c] = (h16)(fmaxf(fmaf((float)w[c], sc[c], nb[c]), 0.f) + (float)cur.r[r][c]);
@@ -219,16 +203,16 @@ __global__ __launch_bounds__(256, 2) void conv_f16w_kernel(const F16WArgs a) {
 #pragma unroll
                     for (int c = 0; c < 8; ++c) w[c] = (h16)fmaxf(fmaf((float)w[c], sc[c], nb[c]), 0.f);
                 }
-                bf[r] = ((cur.ok >> r) & 1) ? w : h16x8w{0, 0, 0, 0, 0, 0, 0, 0};  // zero padding of the NORMALISED activation
+                bf[r] = ((cur.ok >> r) & 1) ? w : h16x8{0, 0, 0, 0, 0, 0, 0, 0};  // zero padding of the NORMALISED activation
             }
         } else {
 #pragma unroll
-            for (int r = 0; r < RPW; ++r) bf[r] = ((cur.ok >> r) & 1) ? cur.v[r] : h16x8w{0, 0, 0, 0, 0, 0, 0, 0};
+            for (int r = 0; r < RPW; ++r) bf[r] = ((cur.ok >> r) & 1) ? cur.v[r] : h16x8{0, 0, 0, 0, 0, 0, 0, 0};
         }
 #pragma unroll
         for (int f = 0; f < NF; ++f)
 #pragma unroll
-            for (int r = 0; r < RPW; ++r) acc[r][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur.af[f], bf[r], acc[r][f], 0, 0, 0);
+            for (int r = 0; r < RPW; ++r) acc[r][f] = mfma16x16x32_f16(cur.af[f], bf[r], acc[r][f]);
         if (s + 1 < nsteps) cur = nxt;
     }
 
@@ -250,7 +234,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16w_kernel(const F16WArgs a) {
             const f32x4 v = acc[r][f];
 #pragma unroll
             for (int q = 0; q < 4; ++q) { ssum[f][q] += v[q]; ssq[f][q] += v[q] * v[q]; }
-            *reinterpret_cast<h16x4w*>(yp + 16 * f) = h16x4w{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+            *reinterpret_cast<h16x4*>(yp + 16 * f) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
         }
     }
     if (a.partial) {  // fixed order: 16 lanes of a row by DPP, then the four waves in order
@@ -258,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void conv_f16w_kernel(const F16WArgs a) {
         for (int f = 0; f < NF; ++f)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float s1 = row16_sum_w(ssum[f][q]), s2 = row16_sum_w(ssq[f][q]);
+                const float s1 = row16_sum(ssum[f][q]), s2 = row16_sum(ssq[f][q]);
                 if (nl == 0) {
                     red[wv][0][16 * f + 4 * g + q] = s1;
                     red[wv][1][16 * f + 4 * g + q] = s2;
@@ -320,8 +304,6 @@ static size_t wblob_bytes(const WGeom& g) { return FW_BIAS_BYTES + (size_t)g.nbl
 // ---------------------------------------------------------------------------------------------------------------------------
 // LocalAttention, C = 128 / 256.  Lane (i = lane & 15, g = lane >> 4); accumulator register r of an MFMA = D[4g + r][i].
 // ---------------------------------------------------------------------------------------------------------------------------
-static __device__ __forceinline__ f32x4 mfma16w(h16x4w a, h16x4w b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-static __device__ __forceinline__ h16x4w cvt4w(f32x4 v) { return h16x4w{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]}; }
 // keeps the compiler from hoisting the next fragment row's filter loads (NB^2 of them per product) into registers it does not have
 static __device__ __forceinline__ void fence_loads() { asm volatile("" ::: "memory"); }
 
@@ -332,8 +314,8 @@ __global__ __launch_bounds__(256) void attn_f16w_kernel(const h16* __restrict__ 
     constexpr int NB = C / 16;
     const int tid = threadIdx.x, l = tid & 63, i = l & 15, g = l >> 4;
     // lane (i, g): W[part * C + 16 f + i][16 ks + 4 g + j]
-    const h16x4w* wl = reinterpret_cast<const h16x4w*>(wfrag) + l;
-    auto wget = [&](int part, int f, int ks) -> h16x4w { return wl[(size_t)((part * NB + f) * NB + ks) * 64]; };
+    const h16x4* wl = reinterpret_cast<const h16x4*>(wfrag) + l;
+    auto wget = [&](int part, int f, int ks) -> h16x4 { return wl[(size_t)((part * NB + f) * NB + ks) * 64]; };
     const int nwx = W / 4, nwy = H / 4;
     const long nwin = (long)N * nwx * nwy;
     const long wv = blockIdx.x * 4L + (tid >> 6), nwv = gridDim.x * 4L;
@@ -341,16 +323,16 @@ __global__ __launch_bounds__(256) void attn_f16w_kernel(const h16* __restrict__ 
     const unsigned lane_off = (unsigned)(((i >> 2) * W + (i & 3)) * C + 4 * g);
     // wave-private LDS tiles of q^ (later O^T), k^ and v^T, fragment-major: [f][lane] 8 bytes (conflict-free)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    h16x4w* qh = reinterpret_cast<h16x4w*>(smem) + (size_t)(tid >> 6) * 3 * NB * 64 + l;
-    h16x4w* kh = qh + NB * 64;
-    h16x4w* vh = kh + NB * 64;
+    h16x4* qh = reinterpret_cast<h16x4*>(smem) + (size_t)(tid >> 6) * 3 * NB * 64 + l;
+    h16x4* kh = qh + NB * 64;
+    h16x4* vh = kh + NB * 64;
     for (long win = w0; win < w1; ++win) {
         const int cn = (int)(win / ((long)nwx * nwy)), rem = (int)(win - (long)cn * nwx * nwy), cwy = rem / nwx, cwx = rem - cwy * nwx;
         const size_t woff = (((size_t)cn * H + 4 * cwy) * W + 4 * cwx) * C + lane_off;
-        h16x4w xa[NB];
+        h16x4 xa[NB];
 #pragma unroll
         for (int h = 0; h < NB; ++h) {
-            xa[h] = *reinterpret_cast<const h16x4w*>(x + woff + 16 * h);
+            xa[h] = *reinterpret_cast<const h16x4*>(x + woff + 16 * h);
             if (in_stats) {  // (x - mean) * rstd, ReLU: fp32 arithmetic, one rounding to fp16 (attn_f16r_kernel's form)
                 const float* st = in_stats + ((size_t)cn * C + 16 * h + 4 * g) * 2;
                 const f32x4 s0 = *reinterpret_cast<const f32x4*>(st), s1 = *reinterpret_cast<const f32x4*>(st + 4);
@@ -370,35 +352,35 @@ __global__ __launch_bounds__(256) void attn_f16w_kernel(const h16* __restrict__ 
                 const float b = bias[part * C + 16 * f + i];
                 q[f] = f32x4{b, b, b, b};
 #pragma unroll
-                for (int h = 0; h < NB; ++h) q[f] = mfma16w(xa[h], wget(part, f, h), q[f]);
+                for (int h = 0; h < NB; ++h) q[f] = mfma16x16x16_f16(xa[h], wget(part, f, h), q[f]);
                 ss += q[f] * q[f];
                 fence_loads();
             }
             f32x4 iv;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) iv[r] = fminf(__builtin_amdgcn_rsqf(row16_sum_w(ss[r])), 1e12f);  // 1 / max(||.||, 1e-12)
-            h16x4w* dst = part == 0 ? qh : kh;
+            for (int r = 0; r < 4; ++r) iv[r] = fminf(__builtin_amdgcn_rsqf(row16_sum(ss[r])), 1e12f);  // 1 / max(||.||, 1e-12)
+            h16x4* dst = part == 0 ? qh : kh;
 #pragma unroll
-            for (int f = 0; f < NB; ++f) dst[64 * f] = cvt4w(q[f] * iv);
+            for (int f = 0; f < NB; ++f) dst[64 * f] = cvt4(q[f] * iv);
         }
         // v^T = Wv X^T + b: D[channel][pixel]
 #pragma unroll 1
         for (int f = 0; f < NB; ++f) {
             f32x4 v = *reinterpret_cast<const f32x4*>(bias + 2 * C + 16 * f + 4 * g);
 #pragma unroll
-            for (int h = 0; h < NB; ++h) v = mfma16w(wget(2, f, h), xa[h], v);
-            vh[64 * f] = cvt4w(v);
+            for (int h = 0; h < NB; ++h) v = mfma16x16x16_f16(wget(2, f, h), xa[h], v);
+            vh[64 * f] = cvt4(v);
         }
         // per 16-column block nn of S^T[c2][c1] = sum_p k^[p][c2] q^[p][c1]: softmax over c2 (|S| <= 1: no max subtraction), then
         // O^T[c1 in nn][p] = sum_c2 P^T[c2][c1] v^T[c2][p], written over q^'s block nn (read for the last time just before)
 #pragma unroll 1
         for (int nn = 0; nn < NB; ++nn) {
-            const h16x4w qb = qh[64 * nn];
+            const h16x4 qb = qh[64 * nn];
             f32x4 st[NB];
             float z = 0.f;
 #pragma unroll
             for (int m = 0; m < NB; ++m) {
-                st[m] = mfma16w(kh[64 * m], qb, f32x4{0.f, 0.f, 0.f, 0.f});
+                st[m] = mfma16x16x16_f16(kh[64 * m], qb, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { st[m][r] = __expf(st[m][r]); z += st[m][r]; }
             }
@@ -407,8 +389,8 @@ __global__ __launch_bounds__(256) void attn_f16w_kernel(const h16* __restrict__ 
             const float inv = __builtin_amdgcn_rcpf(z);
             f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int m = 0; m < NB; ++m) o = mfma16w(cvt4w(st[m] * f32x4{inv, inv, inv, inv}), vh[64 * m], o);
-            qh[64 * nn] = cvt4w(o);
+            for (int m = 0; m < NB; ++m) o = mfma16x16x16_f16(cvt4(st[m] * f32x4{inv, inv, inv, inv}), vh[64 * m], o);
+            qh[64 * nn] = cvt4(o);
         }
         // Y^T[co][p] = bp[co] + sum_c1 Wp[co][c1] O^T[c1][p] -> 8-byte NHWC stores
         h16* yp = y + woff;
@@ -416,21 +398,10 @@ __global__ __launch_bounds__(256) void attn_f16w_kernel(const h16* __restrict__ 
         for (int cf = 0; cf < NB; ++cf) {
             f32x4 acc = *reinterpret_cast<const f32x4*>(bias + 3 * C + 16 * cf + 4 * g);
 #pragma unroll
-            for (int n1 = 0; n1 < NB; ++n1) acc = mfma16w(wget(3, cf, n1), qh[64 * n1], acc);
-            *reinterpret_cast<h16x4w*>(yp + 16 * cf) = cvt4w(acc);
+            for (int n1 = 0; n1 < NB; ++n1) acc = mfma16x16x16_f16(wget(3, cf, n1), qh[64 * n1], acc);
+            *reinterpret_cast<h16x4*>(yp + 16 * cf) = cvt4(acc);
         }
     }
-}
-
-static int f16w_cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) cus = pr.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
 }
 
 size_t f16w_conv_plan_bytes(const mstg_f16_conv_desc* d) {
@@ -498,7 +469,7 @@ int f16w_attn_fwd(const void* x, const float* in_stats, const void* blob, void* 
     const float* bias = (const float*)blob;
     const h16* wfrag = (const h16*)((const char*)blob + (size_t)4 * C * sizeof(float));
     const long nwin = (long)N * (H / 4) * (W / 4);
-    long nb = (long)f16w_cu_count() * 2;  // persistent workgroups, each wave a contiguous run of windows
+    long nb = (long)cu_count() * 2;  // persistent workgroups, each wave a contiguous run of windows
     if (nb * 4 > nwin) nb = (nwin + 3) / 4;
     const size_t lds = (size_t)4 * 3 * C * 16 * sizeof(h16);  // 48 KiB at C = 128, 96 KiB at C = 256
     if (C == 256) {

@@ -907,17 +907,6 @@ static int launch_ms_wgrad(const float* x, const float* dy, const MsGradPtrs& ou
     return MSTG_OK;
 }
 
-static int ms_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 template <int CH>
 static int launch_ms_fwd(const float* x, const MsParamPtrs& prm, float* y, int N, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
     typedef MsUnits<CH> G;
@@ -950,7 +939,7 @@ static int launch_ms_fwd(const float* x, const MsParamPtrs& prm, float* y, int N
                 if (!ws || ws_bytes < (size_t)PACKED * sizeof(float)) return fail_arg(MSTG_E_WORKSPACE, "msblock_fwd: workspace too small");
                 MSTG_PACK_LAUNCH((ms_pack_fwd4b_kernel<C4K>), dim3(cdiv(PACKED, 256)), dim3(256), 0, st, prm, (float*)ws);
                 MSTG_CHECK_LAUNCH("ms_pack_fwd4b_kernel");
-                const int ntiles = N * tiles_x * tiles_y, slots = (C4K == 16 ? 3 : 2) * ms_cus();  // workgroups a CU's LDS holds
+                const int ntiles = N * tiles_x * tiles_y, slots = (C4K == 16 ? 3 : 2) * cu_count();  // workgroups a CU's LDS holds
                 MSTG_LAUNCH((ms_fwd4b_kernel<C4K>), dim3(ntiles < slots ? ntiles : slots), dim3(256), lds, st, x, (const float*)ws, y, N, H, W,
                             tiles_x, tiles_y, ntiles);
             } else MSTG_LAUNCH((ms_fwd4_kernel<C4K>), dim3(N * tiles_x * tiles_y), dim3(256), lds, st, x, prm, y, N, H, W, tiles_x, tiles_y);

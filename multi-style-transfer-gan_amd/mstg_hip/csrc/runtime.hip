@@ -36,6 +36,30 @@ static EnvCache g_env;  // constructed when the shared object is loaded
 
 const char* env_get(EnvKnob k) { return g_env.set[k] ? g_env.val[k] : nullptr; }
 
+// ---- launch sizing ---------------------------------------------------------------------------------------------------------
+int cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t p;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
+        if (cus <= 0) cus = 256;
+    }
+    return cus;
+}
+
+int persistent_occupancy(OccCache& c, const void* kern, size_t lds) {
+    if (c.kern != kern || c.lds != lds) {
+        if (lds > 64 * 1024) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        int nb = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
+        c.occ = nb > 4 ? 4 : nb;
+        c.kern = kern;
+        c.lds = lds;
+    }
+    return c.occ;
+}
+
 // ---- per-launch profiler ---------------------------------------------------------------------------------------------------
 bool g_prof_on = false;
 struct ProfRec {

@@ -21,13 +21,9 @@
 // 32-lane half reads the 8 CONSECUTIVE rows 8 (g >> 1) .. + 7 (+ 16): with a row stride of 8 x odd dwords (WG_ROW) the eight rows
 // start 8 banks apart and the half's 64 dwords cover the 64 banks once, conflict-free.
 // Slabs are fp32 [slab][tap][s][b]; wgrad_reduce_kernel adds them in slab order, multiplies by 1 / loss scale and writes (s, b, 4, 4).
-#include "common.h"
+#include "lanes.h"
 
 namespace mstg {
-
-typedef _Float16 th16;
-typedef _Float16 th16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 th16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TR_MAXC = 512;
 constexpr int TR_MAX_PART = 256;  // partial rows of a per-channel reduction
@@ -49,14 +45,14 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 }
 
 // ---- image -> NHWC fp16, 3 channels padded to 8 (the stem's weight gradient reads it as its big map) --------------------------
-__global__ void train_img_nhwc8_kernel(const float* __restrict__ img, th16* __restrict__ out, long long npix, long long HW) {
+__global__ void train_img_nhwc8_kernel(const float* __restrict__ img, h16* __restrict__ out, long long npix, long long HW) {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npix) return;
     const long long n = p / HW, i = p - n * HW;
-    th16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    h16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = (th16)img[(n * 3 + c) * HW + i];
-    *reinterpret_cast<th16x8*>(out + p * 8) = v;
+    for (int c = 0; c < 3; ++c) v[c] = (h16)img[(n * 3 + c) * HW + i];
+    *reinterpret_cast<h16x8*>(out + p * 8) = v;
 }
 
 // ---- per-channel sums over the pixels of an NHWC fp16 tensor -----------------------------------------------------------------
@@ -66,8 +62,8 @@ __global__ void train_img_nhwc8_kernel(const float* __restrict__ img, th16* __re
 // MODE 1: BatchNorm backward: sum(dyh), sum(dyh * xhat) with dyh = dy * act'(gamma xhat + beta)  (pa, pb).
 // MODE 2: plain sum (bias gradients)  (pa).
 struct ChanArgs {
-    const th16* z;
-    const th16* dy;
+    const h16* z;
+    const h16* dy;
     const float *mean, *rstd, *gamma, *beta;
     float *pa, *pb;
     long long P, ppb;
@@ -100,7 +96,7 @@ __global__ __launch_bounds__(256) void train_chan_partial_kernel(ChanArgs a) {
     if constexpr (MODE == 0) {
         if (active)
             for (long long p = p0 + row; p < p1; p += rows) {
-                const th16x8 v = *reinterpret_cast<const th16x8*>(a.z + p * a.C + 8 * g);
+                const h16x8 v = *reinterpret_cast<const h16x8*>(a.z + p * a.C + 8 * g);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] += (float)v[j];
             }
@@ -113,7 +109,7 @@ __global__ __launch_bounds__(256) void train_chan_partial_kernel(ChanArgs a) {
         }
         if (active)
             for (long long p = p0 + row; p < p1; p += rows) {
-                const th16x8 v = *reinterpret_cast<const th16x8*>(a.z + p * a.C + 8 * g);
+                const h16x8 v = *reinterpret_cast<const h16x8*>(a.z + p * a.C + 8 * g);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float d = (float)v[j] - m[j];
@@ -134,8 +130,8 @@ __global__ __launch_bounds__(256) void train_chan_partial_kernel(ChanArgs a) {
                 bet[j] = a.beta[8 * g + j];
             }
             for (long long p = p0 + row; p < p1; p += rows) {
-                const th16x8 v = *reinterpret_cast<const th16x8*>(a.z + p * a.C + 8 * g);
-                const th16x8 d = *reinterpret_cast<const th16x8*>(a.dy + p * a.C + 8 * g);
+                const h16x8 v = *reinterpret_cast<const h16x8*>(a.z + p * a.C + 8 * g);
+                const h16x8 d = *reinterpret_cast<const h16x8*>(a.dy + p * a.C + 8 * g);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float xh = ((float)v[j] - mean[j]) * rstd[j];
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(256) void train_chan_partial_kernel(ChanArgs a) {
     } else {
         if (active)
             for (long long p = p0 + row; p < p1; p += rows) {
-                const th16x8 v = *reinterpret_cast<const th16x8*>(a.z + p * a.C + 8 * g);
+                const h16x8 v = *reinterpret_cast<const h16x8*>(a.z + p * a.C + 8 * g);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] += (float)v[j];
             }
@@ -217,8 +213,8 @@ __global__ __launch_bounds__(64) void train_bias_final_kernel(const float* __res
 
 // y = act(gamma (z - mean) rstd + beta), one rounding to fp16.  The grid's thread count is a multiple of cg = C / 8 (bn_ew_blocks),
 // so a thread stays on one group of 8 channels: its 32 per-channel constants are loaded once, the loop only streams.
-__global__ void train_bn_apply_kernel(const th16* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ rstd,
-                                      const float* __restrict__ gamma, const float* __restrict__ beta, th16* __restrict__ y,
+__global__ void train_bn_apply_kernel(const h16* __restrict__ z, const float* __restrict__ mean, const float* __restrict__ rstd,
+                                      const float* __restrict__ gamma, const float* __restrict__ beta, h16* __restrict__ y,
                                       long long pieces, int cg, int act) {
     const long long stride = (long long)gridDim.x * blockDim.x, i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int c = (int)(i0 % cg) * 8;
@@ -231,18 +227,18 @@ __global__ void train_bn_apply_kernel(const th16* __restrict__ z, const float* _
         be[j] = beta[c + j];
     }
     for (long long i = i0; i < pieces; i += stride) {
-        const th16x8 v = reinterpret_cast<const th16x8*>(z)[i];
-        th16x8 o;
+        const h16x8 v = reinterpret_cast<const h16x8*>(z)[i];
+        h16x8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (th16)apply_act(ga[j] * (((float)v[j] - mu[j]) * rs[j]) + be[j], act);
-        reinterpret_cast<th16x8*>(y)[i] = o;
+        for (int j = 0; j < 8; ++j) o[j] = (h16)apply_act(ga[j] * (((float)v[j] - mu[j]) * rs[j]) + be[j], act);
+        reinterpret_cast<h16x8*>(y)[i] = o;
     }
 }
 
 // dz = gamma rstd (dyh - mean(dyh) - xhat mean(dyh xhat)), one rounding to fp16; sums = {sum dyh [C], sum dyh xhat [C]}
-__global__ void train_bn_bwd_apply_kernel(const th16* __restrict__ z, const th16* __restrict__ dy, const float* __restrict__ mean,
+__global__ void train_bn_bwd_apply_kernel(const h16* __restrict__ z, const h16* __restrict__ dy, const float* __restrict__ mean,
                                           const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                          const float* __restrict__ sums, th16* __restrict__ dz, long long pieces, int cg, int act,
+                                          const float* __restrict__ sums, h16* __restrict__ dz, long long pieces, int cg, int act,
                                           float invP) {
     const int C = cg * 8;
     const long long stride = (long long)gridDim.x * blockDim.x, i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -259,29 +255,29 @@ __global__ void train_bn_bwd_apply_kernel(const th16* __restrict__ z, const th16
         m2[j] = sums[C + c + j] * invP;
     }
     for (long long i = i0; i < pieces; i += stride) {
-        const th16x8 v = reinterpret_cast<const th16x8*>(z)[i];
-        const th16x8 d = reinterpret_cast<const th16x8*>(dy)[i];
-        th16x8 o;
+        const h16x8 v = reinterpret_cast<const h16x8*>(z)[i];
+        const h16x8 d = reinterpret_cast<const h16x8*>(dy)[i];
+        h16x8 o;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float xh = ((float)v[j] - mu[j]) * rs[j];
             const float dh = (float)d[j] * act_grad(ga[j] * xh + be[j], act);
-            o[j] = (th16)(gr[j] * (dh - m1[j] - xh * m2[j]));
+            o[j] = (h16)(gr[j] * (dh - m1[j] - xh * m2[j]));
         }
-        reinterpret_cast<th16x8*>(dz)[i] = o;
+        reinterpret_cast<h16x8*>(dz)[i] = o;
     }
 }
 
 // backward of LeakyReLU(0.2) / ReLU from the activation's OUTPUT a (both keep the sign of their input): dz = da * act'(a)
-__global__ void train_act_bwd_kernel(const th16* __restrict__ a, const th16* __restrict__ da, th16* __restrict__ dz, long long pieces, int act) {
+__global__ void train_act_bwd_kernel(const h16* __restrict__ a, const h16* __restrict__ da, h16* __restrict__ dz, long long pieces, int act) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < pieces; i += stride) {
-        const th16x8 v = reinterpret_cast<const th16x8*>(a)[i];
-        const th16x8 d = reinterpret_cast<const th16x8*>(da)[i];
-        th16x8 o;
+        const h16x8 v = reinterpret_cast<const h16x8*>(a)[i];
+        const h16x8 d = reinterpret_cast<const h16x8*>(da)[i];
+        h16x8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (th16)((float)d[j] * act_grad((float)v[j], act));
-        reinterpret_cast<th16x8*>(dz)[i] = o;
+        for (int j = 0; j < 8; ++j) o[j] = (h16)((float)d[j] * act_grad((float)v[j], act));
+        reinterpret_cast<h16x8*>(dz)[i] = o;
     }
 }
 
@@ -289,26 +285,26 @@ __global__ void train_act_bwd_kernel(const th16* __restrict__ a, const th16* __r
 // y: the head's fp16 image (N,3,H,W); real, mask: fp32 (N,3,H,W).  With k = 1 - mask and d = y k - real k (products first, as the
 // reference forms them): partial[block] = sum |d|, dz[pixel][c] = scale / numel * sign(d) * k * (1 - y^2) as NHWC fp16 with the 3
 // channels padded to 8 (the layout the head's input and weight gradients read).
-__global__ __launch_bounds__(256) void train_head_loss_bwd_kernel(const th16* __restrict__ y, const float* __restrict__ real,
+__global__ __launch_bounds__(256) void train_head_loss_bwd_kernel(const h16* __restrict__ y, const float* __restrict__ real,
                                                                   const float* __restrict__ mask, long long npix, long long HW,
                                                                   const float* __restrict__ fstate, float inv_numel,
-                                                                  float* __restrict__ partial, th16* __restrict__ dz) {
+                                                                  float* __restrict__ partial, h16* __restrict__ dz) {
     __shared__ float sh4[4];
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     float acc = 0.f;
     if (p < npix) {
         const float gs = fstate[0] * inv_numel;
         const long long n = p / HW, i = p - n * HW;
-        th16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+        h16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const long long e = (n * 3 + c) * HW + i;
             const float yv = (float)y[e], k = 1.f - mask[e];
             const float d = yv * k - real[e] * k;
             acc += fabsf(d);
-            o[c] = (th16)((d > 0.f ? gs : (d < 0.f ? -gs : 0.f)) * k * (1.f - yv * yv));
+            o[c] = (h16)((d > 0.f ? gs : (d < 0.f ? -gs : 0.f)) * k * (1.f - yv * yv));
         }
-        *reinterpret_cast<th16x8*>(dz + p * 8) = o;
+        *reinterpret_cast<h16x8*>(dz + p * 8) = o;
     }
     const float r = train_block_sum(acc, sh4);
     if (threadIdx.x == 0) partial[blockIdx.x] = r;
@@ -328,8 +324,8 @@ constexpr int wg_row(int frags) { return frags == 1 ? 32 : (frags == 2 ? 96 : 16
 constexpr int wg_lds_bytes(int MS, int NB) { return WG_PX * wg_row(MS) + 16 * WG_PX * wg_row(NB); }
 
 struct WgradArgs {
-    const th16* S;
-    const th16* B;
+    const h16* S;
+    const h16* B;
     float* part;      // [slab][16][Cs][CbOut]
     long long P;      // small pixels N h w
     int h, w, Cs, Cb, CbOut;
@@ -337,14 +333,14 @@ struct WgradArgs {
     int nchunks, cps; // chunks of 32 pixels, chunks per slab
 };
 
-__device__ __forceinline__ th16x8 wg_tr_read(const unsigned char* base, int off_lo, int off_hi) {
+__device__ __forceinline__ h16x8 wg_tr_read(const unsigned char* base, int off_lo, int off_hi) {
     typedef __fp16 trv4 __attribute__((__vector_size__(8)));
     typedef __attribute__((address_space(3))) trv4 lds_trv4;
     const trv4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_trv4*)(base + off_lo));
     const trv4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16((lds_trv4*)(base + off_hi));
     union {
         trv4 h[2];
-        th16x8 v;
+        h16x8 v;
     } u;
     u.h[0] = lo;
     u.h[1] = hi;
@@ -429,7 +425,7 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(WgradArgs a) {
     for (int ch = c_begin; ch < c_end; ++ch) {
         const bool more = ch + 1 < c_end;
         if (more) load_chunk(ch + 1);
-        th16x8 sf[MS];
+        h16x8 sf[MS];
 #pragma unroll
         for (int m = 0; m < MS; ++m) sf[m] = wg_tr_read(Ss, s_lo + 32 * m, s_lo + 32 * m + 16 * SROW);
 #pragma unroll
@@ -437,9 +433,9 @@ __global__ __launch_bounds__(256) void wgrad_f16_kernel(WgradArgs a) {
             const unsigned char* bt = Bs + (wave * 4 + t) * BTAP;
 #pragma unroll
             for (int n = 0; n < NB; ++n) {
-                const th16x8 bf = wg_tr_read(bt, b_lo + 32 * n, b_lo + 32 * n + 16 * BROW);
+                const h16x8 bf = wg_tr_read(bt, b_lo + 32 * n, b_lo + 32 * n + 16 * BROW);
 #pragma unroll
-                for (int m = 0; m < MS; ++m) acc[t][m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sf[m], bf, acc[t][m][n], 0, 0, 0);
+                for (int m = 0; m < MS; ++m) acc[t][m][n] = mfma16x16x32_f16(sf[m], bf, acc[t][m][n]);
             }
         }
         __syncthreads();  // every wave has read chunk ch
@@ -583,7 +579,7 @@ extern "C" int mstg_f16_train_image_nhwc8(const float* img, void* out, int N, in
     if (N < 1 || H < 1 || W < 1) return fail_arg(MSTG_E_BADARG, "mstg_f16_train_image_nhwc8: N, H, W must be positive");
     const long long HW = (long long)H * W, npix = HW * N;
     MSTG_LAUNCH(train_img_nhwc8_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img,
-                reinterpret_cast<th16*>(out), npix, HW);
+                reinterpret_cast<h16*>(out), npix, HW);
     MSTG_CHECK_LAUNCH("train_img_nhwc8_kernel");
     return MSTG_OK;
 }
@@ -607,7 +603,7 @@ extern "C" int mstg_f16_train_bn_fwd(const void* z, const float* gamma, const fl
     if (workspace_bytes < chan_ws_bytes(C)) return fail_arg(MSTG_E_WORKSPACE, "mstg_f16_train_bn_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     ChanArgs a{};
-    a.z = reinterpret_cast<const th16*>(z);
+    a.z = reinterpret_cast<const h16*>(z);
     a.P = (long long)P;
     a.C = C;
     a.pa = reinterpret_cast<float*>(workspace);
@@ -619,7 +615,7 @@ extern "C" int mstg_f16_train_bn_fwd(const void* z, const float* gamma, const fl
                 running_mean, running_var);
     MSTG_CHECK_LAUNCH("train_bn_stats_final_kernel");
     const long long pieces = a.P * (C / 8);
-    MSTG_LAUNCH(train_bn_apply_kernel, dim3(bn_ew_blocks(pieces, C / 8)), dim3(256), 0, st, a.z, mean, rstd, gamma, beta, reinterpret_cast<th16*>(y),
+    MSTG_LAUNCH(train_bn_apply_kernel, dim3(bn_ew_blocks(pieces, C / 8)), dim3(256), 0, st, a.z, mean, rstd, gamma, beta, reinterpret_cast<h16*>(y),
                 pieces, C / 8, act);
     MSTG_CHECK_LAUNCH("train_bn_apply_kernel");
     return MSTG_OK;
@@ -636,8 +632,8 @@ extern "C" int mstg_f16_train_bn_bwd(const void* z, const void* dy, const float*
     if (workspace_bytes < chan_ws_bytes(C)) return fail_arg(MSTG_E_WORKSPACE, "mstg_f16_train_bn_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     ChanArgs a{};
-    a.z = reinterpret_cast<const th16*>(z);
-    a.dy = reinterpret_cast<const th16*>(dy);
+    a.z = reinterpret_cast<const h16*>(z);
+    a.dy = reinterpret_cast<const h16*>(dy);
     a.mean = mean; a.rstd = rstd; a.gamma = gamma; a.beta = beta;
     a.P = (long long)P;
     a.C = C;
@@ -652,7 +648,7 @@ extern "C" int mstg_f16_train_bn_bwd(const void* z, const void* dy, const float*
     MSTG_CHECK_LAUNCH("train_bn_bwd_final_kernel");
     const long long pieces = a.P * (C / 8);
     MSTG_LAUNCH(train_bn_bwd_apply_kernel, dim3(bn_ew_blocks(pieces, C / 8)), dim3(256), 0, st, a.z, a.dy, mean, rstd, gamma, beta, sums,
-                reinterpret_cast<th16*>(dz), pieces, C / 8, act, (float)(1.0 / (double)P));
+                reinterpret_cast<h16*>(dz), pieces, C / 8, act, (float)(1.0 / (double)P));
     MSTG_CHECK_LAUNCH("train_bn_bwd_apply_kernel");
     return MSTG_OK;
 }
@@ -663,8 +659,8 @@ extern "C" int mstg_f16_train_act_bwd(const void* a, const void* da, void* dz, s
     if (act != MSTG_ACT_RELU && act != MSTG_ACT_LEAKY02)
         return fail_arg(MSTG_E_UNSUPPORTED, "mstg_f16_train_act_bwd: act must be ReLU or LeakyReLU(0.2) (their outputs keep the input's sign)");
     const long long pieces = (long long)(n / 8);
-    MSTG_LAUNCH(train_act_bwd_kernel, dim3(ew_blocks(pieces)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const th16*>(a),
-                reinterpret_cast<const th16*>(da), reinterpret_cast<th16*>(dz), pieces, act);
+    MSTG_LAUNCH(train_act_bwd_kernel, dim3(ew_blocks(pieces)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const h16*>(a),
+                reinterpret_cast<const h16*>(da), reinterpret_cast<h16*>(dz), pieces, act);
     MSTG_CHECK_LAUNCH("train_act_bwd_kernel");
     return MSTG_OK;
 }
@@ -686,8 +682,8 @@ extern "C" int mstg_f16_train_head_loss_bwd(const void* y, const float* real, co
     if (workspace_bytes < (size_t)nb * sizeof(float)) return fail_arg(MSTG_E_WORKSPACE, "mstg_f16_train_head_loss_bwd: workspace too small");
     const float inv_numel = (float)(1.0 / (3.0 * (double)npix));
     hipStream_t st = (hipStream_t)stream;
-    MSTG_LAUNCH(train_head_loss_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<const th16*>(y), real, mask, npix, HW,
-                fstate, inv_numel, reinterpret_cast<float*>(workspace), reinterpret_cast<th16*>(dz));
+    MSTG_LAUNCH(train_head_loss_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, st, reinterpret_cast<const h16*>(y), real, mask, npix, HW,
+                fstate, inv_numel, reinterpret_cast<float*>(workspace), reinterpret_cast<h16*>(dz));
     MSTG_CHECK_LAUNCH("train_head_loss_bwd_kernel");
     MSTG_LAUNCH(train_loss_final_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const float*>(workspace), nb, inv_numel, loss);
     MSTG_CHECK_LAUNCH("train_loss_final_kernel");
@@ -711,8 +707,8 @@ extern "C" int mstg_f16_train_wgrad(const void* S, const void* B, int N, int h, 
     if (workspace_bytes < (size_t)p.nslabs * 16 * Cs * CbOut * sizeof(float))
         return fail_arg(MSTG_E_WORKSPACE, "mstg_f16_train_wgrad: workspace smaller than mstg_f16_train_wgrad_workspace_bytes");
     WgradArgs a;
-    a.S = reinterpret_cast<const th16*>(S);
-    a.B = reinterpret_cast<const th16*>(B);
+    a.S = reinterpret_cast<const h16*>(S);
+    a.B = reinterpret_cast<const h16*>(B);
     a.part = reinterpret_cast<float*>(workspace);
     a.P = (long long)N * h * w;
     a.h = h; a.w = w; a.Cs = Cs; a.Cb = Cb; a.CbOut = CbOut;
@@ -738,7 +734,7 @@ extern "C" int mstg_f16_train_bias_grad(const void* dz, size_t P, int C, int Cva
     if (workspace_bytes < chan_ws_bytes(C)) return fail_arg(MSTG_E_WORKSPACE, "mstg_f16_train_bias_grad: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     ChanArgs a{};
-    a.z = reinterpret_cast<const th16*>(dz);
+    a.z = reinterpret_cast<const h16*>(dz);
     a.P = (long long)P;
     a.C = C;
     a.pa = reinterpret_cast<float*>(workspace);

@@ -10,21 +10,9 @@
 //                      probabilities sit in the registers exactly as the B operand of the next product needs them (k-slot g <-> key
 //                      4g + r): P never goes through LDS.  Backward = two kernels without atomics: dQ per query tile (loop over
 //                      keys) and dK / dV per key tile (loop over queries), each recomputing P from q, k and the saved log-sum-exp.
-#include "common.h"
+#include "lanes.h"
 
 namespace mstg {
-
-template <int CTRL>
-__device__ __forceinline__ float tdpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float trow16_sum(float v) {
-    v += tdpp<0xB1>(v);
-    v += tdpp<0x4E>(v);
-    v += tdpp<0x141>(v);
-    v += tdpp<0x140>(v);
-    return v;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 __global__ void structure_map_kernel(const float* __restrict__ img, float* __restrict__ out, int N, int H, int W) {
@@ -73,14 +61,14 @@ __global__ __launch_bounds__(256) void ln_mod_fwd_kernel(const float* __restrict
         if (64 * c + 4 * j < dim) v[c] = *reinterpret_cast<const f32x4*>(xp + 64 * c + 4 * j);
         s += v[c][0] + v[c][1] + v[c][2] + v[c][3];
     }
-    const float mean = trow16_sum(s) / (float)dim;
+    const float mean = row16_sum(s) / (float)dim;
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < LN_MAXC; ++c)
         if (64 * c + 4 * j < dim)
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float d = v[c][e] - mean; q += d * d; }
-    const float rstd = rsqrtf(trow16_sum(q) / (float)dim + eps);
+    const float rstd = rsqrtf(row16_sum(q) / (float)dim + eps);
     if (j == 0) { stats[tok * 2] = mean; stats[tok * 2 + 1] = rstd; }
 #pragma unroll
     for (int c = 0; c < LN_MAXC; ++c) {
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(const float* __restrict
                 }
             }
         }
-        const float m1 = trow16_sum(s1) / (float)dim, m2 = trow16_sum(s2) / (float)dim;
+        const float m1 = row16_sum(s1) / (float)dim, m2 = row16_sum(s2) / (float)dim;
 #pragma unroll
         for (int c = 0; c < LN_MAXC; ++c) {
             const int ch = 64 * c + 4 * j;

@@ -11,42 +11,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from f16_helpers import DEV, _lib_loaded, h, norm_relu, report, rnd, stats_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from mstg_hip import _lib
-    _lib.load()
-
-
-def report(name, err, tol):
-    print(f"  [parity] {name:64s} rel-L2 {err:.2e} (tol {tol:.0e})")
-    assert err <= tol, f"{name}: {err:.3e} > {tol:.0e}"
-
-
-def h(t):
-    """round to fp16 and back (CPU, fp32)"""
-    return t.half().float()
-
-
-def rnd(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g) * scale
-
-
-def stats_of(y_nchw):
-    mu = y_nchw.mean(dim=(2, 3))
-    var = y_nchw.var(dim=(2, 3), unbiased=False)
-    return torch.stack([mu, torch.rsqrt(var + 1e-5)], dim=-1)  # (N, C, 2)
-
-
-def norm_relu(x_nchw, st):
-    return F.relu((x_nchw - st[..., 0][:, :, None, None]) * st[..., 1][:, :, None, None])
 
 
 CONV_CASES = [

@@ -16,27 +16,9 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_l2
+from f16_helpers import DEV, _lib_loaded, report, rnd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from mstg_hip import _lib
-    _lib.load()
-
-
-def report(name, err, tol):
-    print(f"  [parity] {name:64s} rel-L2 {err:.2e} (tol {tol:.0e})")
-    assert err <= tol, f"{name}: {err:.3e} > {tol:.0e}"
-
-
-def rnd(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g) * scale
 
 
 def attn_ref(qkv, heads):

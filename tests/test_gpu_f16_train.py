@@ -22,41 +22,13 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLD, ROOT, rel_l2
-from test_gpu_f16_plain import LAYER_CASES, STEM_HEAD_CASES
+from f16_helpers import (ACT_LEAKY02, ACT_NONE, ACT_RELU, DEV, LAYER_CASES, STEM_HEAD_CASES, _lib_loaded, h, nhwc16, report,  # noqa: F401
+                         rnd)
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-ACT_NONE, ACT_RELU, ACT_LEAKY02 = 0, 1, 2
 ACTS = {ACT_NONE: lambda t: t, ACT_RELU: F.relu, ACT_LEAKY02: lambda t: F.leaky_relu(t, 0.2)}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _lib_loaded():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    from mstg_hip import _lib
-    _lib.load()
-
-
-def report(name, err, tol):
-    print(f"  [parity] {name:64s} rel-L2 {err:.2e} (tol {tol:.0e})")
-    assert err <= tol, f"{name}: {err:.3e} > {tol:.0e}"
-
-
-def h(t):
-    """round to fp16 and back (CPU, fp32)"""
-    return t.half().float()
-
-
-def rnd(shape, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(shape, generator=g) * scale
-
-
-def nhwc16(t):
-    return t.permute(0, 2, 3, 1).contiguous().half().to(DEV)
 
 
 def state(scale=4.0):
