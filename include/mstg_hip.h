@@ -487,6 +487,24 @@ int mstg_blend_u8(const unsigned char* orig, const unsigned char* styled, double
                   const double* weight_map /*nullable*/, unsigned char* out, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image-quality metrics of the reference's evaluation scripts (compare_image_quality.py:14-33, image_quality_comparison.py:11-34,
+ * complete_comparison.py:13-32, improved_image_compare.py:8-27), on the device: a, b = two batches of 8-bit RGB images
+ * (N, H, W, 3), contiguous; out[n] = {mse, psnr, ssim, ssim_c0, ssim_c1, ssim_c2} (fp64) of pair n on the images / 255:
+ *   mse  = np.mean((a - b) ** 2) = SSD / (255^2 H W 3) from the exact integer sum of squared byte differences;
+ *   psnr = skimage peak_signal_noise_ratio(data_range=1) = 10 log10(1 / mse), +inf for equal images;
+ *   ssim = skimage structural_similarity(channel_axis=2, data_range=1): uniform 7x7 window, sample covariance (49 / 48),
+ *          K1 = 0.01, K2 = 0.03, mean over the (H - 6)(W - 6) windows inside the image per channel, ((c0 + c1) + c2) / 3.
+ * Window sums are exact integers, S is formed in fp64, sums run in a fixed order without atomics: results are bit-identical from
+ * run to run and do not depend on N.  H, W >= 7 (BADARG names the window otherwise); H * W * 3 < 2^31 (else UNSUPPORTED).
+ * A workgroup takes MSTG_METRICS_TILE_H x MSTG_METRICS_TILE_W windows; the workspace holds four 8-byte words per tile.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_METRICS_TILE_H 16
+#define MSTG_METRICS_TILE_W 64
+size_t mstg_image_metrics_workspace_bytes(int N, int H, int W); /* 0 for an invalid shape */
+int mstg_image_metrics_u8(const unsigned char* a, const unsigned char* b, int N, int H, int W, double* out /* [N][6] */,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain
  * (enhanced_generator.py:4; call shape :115, :218-225) -- parity unpinned; definition in structural_transformer.py.
  * The block's Linear layers go through mstg_conv2d_* (a Linear over tokens (N, L, dim) is a 1x1 convolution on NHWC).

@@ -167,6 +167,8 @@ SIGNATURES = {
     "mstg_u8_to_tensor": (_i, [_vp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, C.c_ulonglong, _i, _vp]),
     "mstg_tensor_to_u8": (_i, [_fp, _i, _i, _vp, _vp]),
     "mstg_blend_u8": (_i, [_vp, _vp, C.c_double, C.c_double, _vp, _vp, _i, _i, _vp]),
+    "mstg_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_image_metrics_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
