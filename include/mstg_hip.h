@@ -487,6 +487,67 @@ int mstg_blend_u8(const unsigned char* orig, const unsigned char* styled, double
                   const double* weight_map /*nullable*/, unsigned char* out, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Batched image pipeline (csrc/image_batch.hip): the steps above for N images of different sizes per launch, byte-identical to
+ * the one-image entry points.  Folder inference (batch_process_images.py:176-236, :255-441) and MonetPhotoDataset batches.
+ *
+ * One descriptor per image and per direction (pre: image -> T x T canvas; post: canvas -> image), built on the host:
+ *   box     the part of `src` that is resampled (pre: the whole image; post: the crop box of the canvas);
+ *   rs      the size the box is resampled to with `filter`; a pass whose size does not change copies (ks_* = 0);
+ *   win     the window of the resampled image that is wanted (letterbox: all of it; dataset item: the centre crop);
+ *   dst     where the window lands in the T x T canvas (tensor output only), `fill` = the byte outside it;
+ *   tables  kk [rs][ks] and bounds [rs][2] of mstg_resample_coeffs(box, rs, filter) per direction, as int32 indices into ONE
+ *           packed table buffer (host copy for validation, device copy for the kernels);
+ *   inter   the horizontal pass writes columns [win_x, win_x + win_w) of box rows [y_first, y_first + irows) -- the rows the
+ *           vertical pass reads for the window -- as 8-bit rows of `ipitch` bytes (multiple of 4, >= 3 win_w) at byte
+ *           `inter_off` (multiple of 4) of one ragged intermediate buffer;
+ *   out_off byte offset of the (win_h, win_w, 3) result in the ragged output buffer (u8 output only).
+ * Work is distributed by a host-built tile list, four int32 per tile: {image, y0, x0, extent}.  mstg_img_batch_tiles sizes each
+ * image's tiles so that a tile's source segment and coefficient window fit the kernel's LDS, and refuses (UNSUPPORTED, naming
+ * the image) a reduction factor for which no tile does.  The kernels check every tile against its descriptor before they touch
+ * memory.  Integer sums with the 2^21 rounding term, fixed order, no atomics.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct mstg_img_desc {
+    const unsigned char* src; /* device: (src_h, src_w, 3) */
+    int32_t src_h, src_w;
+    int32_t box_y, box_x, box_h, box_w;
+    int32_t rs_h, rs_w, filter;
+    int32_t win_y, win_x, win_h, win_w;
+    int32_t dst_y, dst_x, fill;
+    int32_t ks_h, ks_v;
+    int32_t y_first, irows, ipitch;
+    int64_t kk_h, bounds_h, kk_v, bounds_v;
+    int64_t inter_off, out_off;
+    uint64_t grid; /* 8x8 keep-mask of this image (tensor output with use_mask) */
+} mstg_img_desc;
+#define MSTG_IMG_PASS_H 0        /* tiles of the intermediate: 4 rows x extent columns */
+#define MSTG_IMG_PASS_V_TENSOR 1 /* tiles of the canvas: extent rows x 64 columns */
+#define MSTG_IMG_PASS_V_U8 2     /* tiles of the window: extent rows x 64 columns */
+/* Host only, touches no device: windows inside their images, positive sizes, table / intermediate / output extents inside the
+ * buffers given, every bounds entry inside its source, non-null pointers.  canvas = T for the tensor output, 0 for the ragged
+ * uint8 output of `out_bytes`.  A refusal names the image index in mstg_last_error.  Every launch entry below calls it first. */
+int mstg_img_batch_validate(const mstg_img_desc* descs, int n, const int32_t* table, size_t table_len, size_t inter_bytes, int canvas,
+                            size_t out_bytes);
+/* number of tiles of `pass` (negative: error); writes them when tiles != NULL (cap = tiles the buffer holds) */
+int mstg_img_batch_tiles(const mstg_img_desc* descs, int n, const int32_t* table, size_t table_len, int pass, int canvas,
+                         int32_t* tiles, size_t cap);
+/* descs / table: host copies; descs_dev / tiles_dev / table_dev: the same bytes on the device */
+int mstg_img_batch_resample_h(const mstg_img_desc* descs, int n, const int32_t* table, size_t table_len, const void* descs_dev,
+                              const int32_t* tiles_dev, int ntiles, const int32_t* table_dev, unsigned char* inter, size_t inter_bytes,
+                              void* stream);
+/* vertical pass + placement + fill + ToTensor / Normalize: out (n, 3, T, T) fp32; use_mask: out is the masked image and
+ * image_out / mask_out (nullable) the unmasked image / the mask; canvas_u8 (nullable): the (n, T, T, 3) uint8 canvas */
+int mstg_img_batch_resample_v_tensor(const mstg_img_desc* descs, int n, const int32_t* table, size_t table_len, const void* descs_dev,
+                                     const int32_t* tiles_dev, int ntiles, const int32_t* table_dev, const unsigned char* inter,
+                                     size_t inter_bytes, int T, float* out, float* image_out, float* mask_out, unsigned char* canvas_u8,
+                                     int use_mask, void* stream);
+/* vertical pass into the ragged uint8 output */
+int mstg_img_batch_resample_v_u8(const mstg_img_desc* descs, int n, const int32_t* table, size_t table_len, const void* descs_dev,
+                                 const int32_t* tiles_dev, int ntiles, const int32_t* table_dev, const unsigned char* inter,
+                                 size_t inter_bytes, unsigned char* out, size_t out_bytes, void* stream);
+/* mstg_tensor_to_u8 for a batch: y (N, 3, H, W) fp32 or fp16 (is_f16; widened exactly) -> dst (N, H, W, 3) */
+int mstg_img_batch_tensor_to_u8(const void* y, int is_f16, int N, int H, int W, unsigned char* dst, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Image-quality metrics of the reference's evaluation scripts (compare_image_quality.py:14-33, image_quality_comparison.py:11-34,
  * complete_comparison.py:13-32, improved_image_compare.py:8-27), on the device: a, b = two batches of 8-bit RGB images
  * (N, H, W, 3), contiguous; out[n] = {mse, psnr, ssim, ssim_c0, ssim_c1, ssim_c2} (fp64) of pair n on the images / 255:

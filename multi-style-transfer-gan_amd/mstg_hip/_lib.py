@@ -30,6 +30,16 @@ class F16PlainDesc(C.Structure):
         "kind", "N", "H", "W", "Cin", "Ho", "Wo", "Cout", "K", "src_nchw_f32", "dst_nchw", "act")]
 
 
+class ImgDesc(C.Structure):
+    """mirror of mstg_img_desc"""
+    _fields_ = ([("src", C.c_void_p)] + [(n, C.c_int32) for n in (
+        "src_h", "src_w", "box_y", "box_x", "box_h", "box_w", "rs_h", "rs_w", "filter", "win_y", "win_x", "win_h", "win_w",
+        "dst_y", "dst_x", "fill", "ks_h", "ks_v", "y_first", "irows", "ipitch")] + [(n, C.c_int64) for n in (
+            "kk_h", "bounds_h", "kk_v", "bounds_v", "inter_off", "out_off")] + [("grid", C.c_uint64)])
+
+
+IMG_PASS_H, IMG_PASS_V_TENSOR, IMG_PASS_V_U8 = 0, 1, 2
+
 _vp, _fp, _sz, _i, _f = C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float
 _dp = C.POINTER(ConvDesc)
 _hp = C.POINTER(F16ConvDesc)
@@ -167,6 +177,12 @@ SIGNATURES = {
     "mstg_u8_to_tensor": (_i, [_vp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, C.c_ulonglong, _i, _vp]),
     "mstg_tensor_to_u8": (_i, [_fp, _i, _i, _vp, _vp]),
     "mstg_blend_u8": (_i, [_vp, _vp, C.c_double, C.c_double, _vp, _vp, _i, _i, _vp]),
+    "mstg_img_batch_validate": (_i, [_vp, _i, _vp, _sz, _sz, _i, _sz]),
+    "mstg_img_batch_tiles": (_i, [_vp, _i, _vp, _sz, _i, _i, _vp, _sz]),
+    "mstg_img_batch_resample_h": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "mstg_img_batch_resample_v_tensor": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp, _sz, _i, _fp, _fp, _fp, _vp, _i, _vp]),
+    "mstg_img_batch_resample_v_u8": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "mstg_img_batch_tensor_to_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mstg_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_image_metrics_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
 }

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 from functools import lru_cache
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -224,3 +225,339 @@ def process_local_style(model, img_u8: torch.Tensor, mode="simple", strength=0.8
     if width * height <= 1024 * 1024:
         out = resize_u8(out, (width, height), LANCZOS)
     return out
+
+
+# ---- the batched pipeline (csrc/image_batch.hip) ---------------------------------------------------------------------------
+# N images of different sizes per call; the number of library launches does not depend on N and every byte equals the one-image
+# functions above.  Geometry is planned in pure Python with the expressions of letterbox / process_cyclegan /
+# process_local_style / dataset_item, turned into one descriptor per image and direction, and uploaded -- descriptors, tile
+# lists and the coefficient tables of the whole chunk -- in one pinned host-to-device copy.
+class LetterboxGeom(NamedTuple):
+    """Geometry of one image through process_cyclegan / process_local_style: the LANCZOS resize to (new_h, new_w), its offset
+    on the canvas, the crop box (left, top, crop_w, crop_h) of the output canvas, whether that crop is resized back, and the
+    size of the result."""
+    height: int
+    width: int
+    new_h: int
+    new_w: int
+    off_y: int
+    off_x: int
+    crop: tuple
+    resize_back: bool
+    out_h: int
+    out_w: int
+
+
+class DatasetGeom(NamedTuple):
+    """Geometry of one MonetPhotoDataset item: the BILINEAR shorter-side resize to (new_h, new_w) and the centre-crop origin."""
+    height: int
+    width: int
+    new_h: int
+    new_w: int
+    top: int
+    left: int
+
+
+def _sizes(sizes):
+    out = []
+    for i, s in enumerate(sizes):
+        h, w = int(s[0]), int(s[1])
+        if h < 1 or w < 1:
+            raise ValueError(f"mstg_hip image: image {i} has size {h}x{w}")
+        out.append((h, w))
+    return out
+
+
+@lru_cache(maxsize=4096)
+def _letterbox_geom(height, width, target, local_style):
+    if width > height:
+        new_width, new_height = target, int(height * (target / width))
+    else:
+        new_height, new_width = target, int(width * (target / height))
+    if new_width < 1 or new_height < 1:
+        return None
+    off_x, off_y = (target - new_width) // 2, (target - new_height) // 2
+    crop_w = crop_h = target
+    aspect = width / height
+    if (aspect != 1.0) if local_style else (width != height):
+        if aspect > 1:
+            crop_w, crop_h = target, int(target / aspect)
+        else:
+            crop_h, crop_w = target, int(target * aspect)
+        if local_style:
+            crop_w, crop_h = min(crop_w, target), min(crop_h, target)
+    if crop_w < 1 or crop_h < 1:
+        return None
+    left, top = (target - crop_w) // 2, (target - crop_h) // 2
+    back = width * height <= 1024 * 1024
+    return LetterboxGeom(height, width, new_height, new_width, off_y, off_x, (left, top, crop_w, crop_h), back,
+                         height if back else crop_h, width if back else crop_w)
+
+
+def letterbox_plan(sizes, target=256, local_style=False):
+    """Geometry of ``process_cyclegan`` (``local_style``: of ``process_local_style``) for images of ``sizes`` = (height, width)
+    pairs.  Pure Python.  Raises, naming the image, for a size whose resized or cropped side would be 0 (Pillow refuses it)."""
+    target = int(target)
+    if target < 1:
+        raise ValueError(f"mstg_hip image: target {target}")
+    plan = []
+    for i, (h, w) in enumerate(_sizes(sizes)):
+        g = _letterbox_geom(h, w, target, bool(local_style))
+        if g is None:
+            raise ValueError(f"mstg_hip image: image {i} ({h}x{w}) would be resized to a side of 0 on a {target} canvas")
+        plan.append(g)
+    return plan
+
+
+@lru_cache(maxsize=4096)
+def _dataset_geom(H, W, img_size):
+    if W <= H:  # torchvision Resize(int): the smaller edge becomes img_size, the other int(size * long / short)
+        new_w, new_h = img_size, int(img_size * H / W)
+    else:
+        new_h, new_w = img_size, int(img_size * W / H)
+    top, left = int(round((new_h - img_size) / 2.0)), int(round((new_w - img_size) / 2.0))  # torchvision center_crop
+    return DatasetGeom(H, W, new_h, new_w, top, left)
+
+
+def dataset_plan(sizes, img_size=256):
+    """Geometry of ``dataset_item`` for images of ``sizes`` = (height, width) pairs.  Pure Python."""
+    img_size = int(img_size)
+    if img_size < 1:
+        raise ValueError(f"mstg_hip image: img_size {img_size}")
+    return [_dataset_geom(h, w, img_size) for h, w in _sizes(sizes)]
+
+
+_DESC = np.dtype([("src", "<u8")] + [(n, "<i4") for n in (
+    "src_h", "src_w", "box_y", "box_x", "box_h", "box_w", "rs_h", "rs_w", "filter", "win_y", "win_x", "win_h", "win_w", "dst_y", "dst_x",
+    "fill", "ks_h", "ks_v", "y_first", "irows", "ipitch")] + [(n, "<i8") for n in (
+        "kk_h", "bounds_h", "kk_v", "bounds_v", "inter_off", "out_off")] + [("grid", "<u8")], align=True)
+assert _DESC.itemsize == C.sizeof(_lib.ImgDesc)
+
+
+@lru_cache(maxsize=4096)
+def _axes(bh, bw, rh, rw, filt, wy, wh):
+    """(ks_h, ks_v, y_first, irows): tap counts (0: the pass copies) and the box rows the vertical pass reads for window rows
+    [wy, wy + wh) -- what Pillow's horizontal pass computes."""
+    ks_h = 0 if rw == bw else _coeff_tables_host(bw, rw, filt)[0]
+    if rh == bh:
+        return ks_h, 0, wy, wh
+    ks_v, _, b = _coeff_tables_host(bh, rh, filt)
+    y_first = int(b[wy, 0])
+    return ks_h, ks_v, y_first, int(b[wy + wh - 1, 0] + b[wy + wh - 1, 1]) - y_first
+
+
+class _Direction:
+    """Descriptors of one direction (image -> canvas or canvas -> image) of one chunk."""
+
+    def __init__(self, plan, canvas):
+        self.plan, self.canvas, self.rows, self.inter_bytes, self.out_bytes, self.out_offs = plan, canvas, [], 0, 0, []
+
+    def add(self, src_ptr, src_h, src_w, box, rs, filt, win, dst=(0, 0), fill=0, grid=0):
+        (by, bx, bh, bw), (rh, rw), (wy, wx, wh, ww) = box, rs, win
+        ks_h, ks_v, y_first, irows = _axes(bh, bw, rh, rw, filt, wy, wh)
+        kk_h, bo_h = self.plan.table(bw, rw, filt) if ks_h else (0, 0)
+        kk_v, bo_v = self.plan.table(bh, rh, filt) if ks_v else (0, 0)
+        ipitch = (3 * ww + 3) & ~3
+        self.rows.append((src_ptr, src_h, src_w, by, bx, bh, bw, rh, rw, filt, wy, wx, wh, ww, dst[0], dst[1], fill, ks_h, ks_v, y_first,
+                          irows, ipitch, kk_h, bo_h, kk_v, bo_v, self.inter_bytes, self.out_bytes, grid))
+        self.out_offs.append(self.out_bytes)
+        self.inter_bytes += irows * ipitch
+        self.out_bytes += (3 * wh * ww + 15) & ~15
+
+    def _args(self, k):
+        p = self.plan
+        return (p.host + self.off_descs, len(self.rows), p.host + p.off_table, p.table_len, p.dev + self.off_descs, p.dev + self.off_tiles[k],
+                self.ntiles[k], p.dev + p.off_table)
+
+    def run_h(self, inter):
+        _lib.check(_lib.load().mstg_img_batch_resample_h(*self._args(0), _p(inter), inter.numel(), _stream()), "mstg_img_batch_resample_h")
+
+    def run_v_tensor(self, inter, out, image_out=None, mask_out=None, canvas_u8=None, use_mask=0):
+        _lib.check(_lib.load().mstg_img_batch_resample_v_tensor(*self._args(1), _p(inter), inter.numel(), self.canvas, _p(out), _p(image_out),
+                                                                _p(mask_out), _p(canvas_u8), use_mask, _stream()),
+                   "mstg_img_batch_resample_v_tensor")
+
+    def run_v_u8(self, inter, out):
+        _lib.check(_lib.load().mstg_img_batch_resample_v_u8(*self._args(1), _p(inter), inter.numel(), _p(out), out.numel(), _stream()),
+                   "mstg_img_batch_resample_v_u8")
+
+
+class _BatchPlan:
+    """Everything the kernels of one chunk read besides pixels: descriptors and tile lists per direction, and the coefficient
+    tables (each (in, out, filter) once), laid out in one pinned buffer and copied to the device in one transfer."""
+
+    def __init__(self, device):
+        self.device, self.dirs, self._parts, self._index, self.table_len = device, [], [], {}, 0
+
+    def direction(self, canvas=0):
+        self.dirs.append(_Direction(self, canvas))
+        return self.dirs[-1]
+
+    def table(self, in_size, out_size, filt):
+        key = (in_size, out_size, filt)
+        if key not in self._index:
+            _, kk, bounds = _coeff_tables_host(in_size, out_size, filt)
+            self._index[key] = (self.table_len, self.table_len + kk.size)
+            self._parts += [kk.reshape(-1), bounds.reshape(-1)]
+            self.table_len += kk.size + bounds.size
+        return self._index[key]
+
+    def upload(self):
+        lib = _lib.load()
+        table = np.concatenate(self._parts) if self._parts else np.zeros(4, dtype=np.int32)
+        self.table_len = int(table.size)
+        total = 0
+
+        def take(nbytes):
+            nonlocal total
+            off, total = total, total + ((nbytes + 15) & ~15)
+            return off
+
+        for d in self.dirs:
+            d.descs = np.array(d.rows, dtype=_DESC)
+            d.passes = (_lib.IMG_PASS_H, _lib.IMG_PASS_V_TENSOR if d.canvas else _lib.IMG_PASS_V_U8)
+            d.ntiles = []
+            for p in d.passes:
+                cnt = lib.mstg_img_batch_tiles(d.descs.ctypes.data, len(d.rows), table.ctypes.data, self.table_len, p,
+                                               d.canvas if p == _lib.IMG_PASS_V_TENSOR else 0, None, 0)
+                if cnt <= 0:
+                    _lib.check(cnt or -1, "mstg_img_batch_tiles")
+                d.ntiles.append(cnt)
+            d.off_descs = take(d.descs.nbytes)
+            d.off_tiles = [take(16 * c) for c in d.ntiles]
+        self.off_table = take(table.nbytes)
+        self._host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        hb = self._host.numpy()
+        self.host = hb.ctypes.data
+        hb[self.off_table:self.off_table + table.nbytes] = table.view(np.uint8)
+        for d in self.dirs:
+            hb[d.off_descs:d.off_descs + d.descs.nbytes] = d.descs.view(np.uint8)
+            for p, off, c in zip(d.passes, d.off_tiles, d.ntiles):
+                got = lib.mstg_img_batch_tiles(self.host + d.off_descs, len(d.rows), self.host + self.off_table, self.table_len, p,
+                                               d.canvas if p == _lib.IMG_PASS_V_TENSOR else 0, self.host + off, c)
+                if got != c:
+                    _lib.check(got if got < 0 else -1, "mstg_img_batch_tiles")
+        self._dev = self._host.to(self.device, non_blocking=True)
+        self.dev = self._dev.data_ptr()
+
+
+def upload_u8(arrays, device=None):
+    """Decoded (H, W, 3) uint8 numpy images -> GPU tensors through ONE pinned buffer and ONE host-to-device copy; the results
+    are views of one device buffer (each starts on a 16-byte boundary)."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    arrays = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrays]
+    offs, total = [], 0
+    for i, a in enumerate(arrays):
+        if a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+            raise RuntimeError(f"mstg_hip image: image {i} is not a non-empty (H, W, 3) array")
+        offs.append(total)
+        total += (a.size + 15) & ~15
+    host = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=True)
+    hb = host.numpy()
+    for a, o in zip(arrays, offs):
+        hb[o:o + a.size] = a.reshape(-1)
+    dev = host.to(device, non_blocking=True)
+    return [dev[o:o + a.size].view(a.shape) for a, o in zip(arrays, offs)]
+
+
+def _req_batch(images):
+    images = [_req_u8(im) for im in images]
+    if any(im.device != images[0].device for im in images):
+        raise RuntimeError("mstg_hip image: the images of a batch must live on one device")
+    return images
+
+
+def _process_chunk(model, images, geoms, target, mode, strength, weight_maps):
+    n, T, dev = len(images), target, images[0].device
+    blend = mode in ("simple", "weight_map")
+    plan = _BatchPlan(dev)
+    pre, post = plan.direction(canvas=T), plan.direction()
+    x = torch.empty((n, 3, T, T), dtype=torch.float32, device=dev)
+    styled = torch.empty((n, T, T, 3), dtype=torch.uint8, device=dev)
+    canvas = torch.empty_like(styled) if blend else None
+    final = torch.empty_like(styled) if blend else styled
+    for im, g in zip(images, geoms):
+        pre.add(im.data_ptr(), g.height, g.width, (0, 0, g.height, g.width), (g.new_h, g.new_w), LANCZOS, (0, 0, g.new_h, g.new_w),
+                (g.off_y, g.off_x), 255)
+    for i, g in enumerate(geoms):
+        left, top, crop_w, crop_h = g.crop
+        post.add(final.data_ptr() + i * T * T * 3, T, T, (top, left, crop_h, crop_w), (g.out_h, g.out_w), LANCZOS, (0, 0, g.out_h, g.out_w))
+    plan.upload()
+    inter = torch.empty(max(pre.inter_bytes, post.inter_bytes), dtype=torch.uint8, device=dev)
+    pre.run_h(inter)
+    pre.run_v_tensor(inter, x, canvas_u8=canvas)
+    with torch.no_grad():
+        y = model(x)
+    if not y.is_cuda or tuple(y.shape) != (n, 3, T, T):
+        raise RuntimeError(f"mstg_hip image: the model returned {tuple(y.shape)} for an input of {tuple(x.shape)}")
+    if y.dtype not in (torch.float32, torch.float16):
+        y = y.float()
+    y = y.contiguous()
+    lib = _lib.load()
+    _lib.check(lib.mstg_img_batch_tensor_to_u8(_p(y), int(y.dtype == torch.float16), n, T, T, _p(styled), _stream()),
+               "mstg_img_batch_tensor_to_u8")
+    if blend:  # the (n * T, T, 3) view of the batch is one tall image to the blend kernel
+        if mode == "weight_map":
+            wm = torch.stack([torch.as_tensor(m) for m in weight_maps]).to(device=dev, dtype=torch.float64).contiguous()
+            w0 = w1 = 0.0
+        else:
+            wm, w1 = None, float(strength)
+            w0 = 1 - w1
+        _lib.check(lib.mstg_blend_u8(_p(canvas), _p(styled), w0, w1, _p(wm), _p(final), n * T, T, _stream()), "mstg_blend_u8")
+    out = torch.empty(post.out_bytes, dtype=torch.uint8, device=dev)
+    post.run_h(inter)
+    post.run_v_u8(inter, out)
+    return [out[o:o + g.out_h * g.out_w * 3].view(g.out_h, g.out_w, 3) for o, g in zip(post.out_offs, geoms)]
+
+
+def _process_batch(model, images, target, batch_size, mode, strength, weight_maps, local_style):
+    images = _req_batch(images)
+    target, batch_size = int(target), int(batch_size)
+    if batch_size < 1:
+        raise RuntimeError(f"mstg_hip image: batch_size {batch_size}")
+    geoms = letterbox_plan([im.shape[:2] for im in images], target, local_style=local_style)
+    if mode == "weight_map":
+        if weight_maps is None or len(weight_maps) != len(images):
+            raise RuntimeError("mstg_hip blend: mode 'weight_map' needs one weight map per image")
+        for i, m in enumerate(weight_maps):
+            if tuple(m.shape) != (target, target):
+                raise RuntimeError(f"mstg_hip blend: weight map {i} {tuple(m.shape)} does not match the canvas {target}x{target}")
+    outs = []
+    for s in range(0, len(images), batch_size):
+        e = s + batch_size
+        outs += _process_chunk(model, images[s:e], geoms[s:e], target, mode, strength, None if weight_maps is None else weight_maps[s:e])
+    return outs
+
+
+def process_cyclegan_batch(model, images, target=256, batch_size=64):
+    """``process_cyclegan`` for a sequence of uint8 (H, W, 3) GPU images of any sizes: byte-identical results, ``model`` called
+    once per chunk of ``batch_size`` images on the (n, 3, target, target) batch under ``torch.no_grad()`` (fp32 or fp16 output),
+    five library launches per chunk whatever n.  Returns uint8 tensors (views of one buffer per chunk)."""
+    return _process_batch(model, images, target, batch_size, None, None, None, False)
+
+
+def process_local_style_batch(model, images, mode="simple", strength=0.8, weight_maps=None, target=256, batch_size=64):
+    """``process_local_style`` for a sequence of images, same modes: 'simple' (``strength``), 'weight_map' (``weight_maps``: one
+    (target, target) float64 map per image), anything else = the styled image.  Six library launches per chunk at most."""
+    return _process_batch(model, images, target, batch_size, mode, strength, weight_maps, True)
+
+
+def dataset_batch(images, grid_masks, img_size=256):
+    """``dataset_item`` for a sequence of decoded images and their grid masks in two launches:
+    (masked_images, images, masks), each (N, 3, img_size, img_size) fp32."""
+    images = _req_batch(images)
+    if len(grid_masks) != len(images):
+        raise RuntimeError("mstg_hip image: one grid mask per image")
+    S, n, dev = int(img_size), len(images), images[0].device
+    plan = _BatchPlan(dev)
+    pre = plan.direction(canvas=S)
+    for im, g, grid in zip(images, dataset_plan([im.shape[:2] for im in images], S), grid_masks):
+        pre.add(im.data_ptr(), g.height, g.width, (0, 0, g.height, g.width), (g.new_h, g.new_w), BILINEAR, (g.top, g.left, S, S),
+                grid=int(grid) & (2 ** 64 - 1))
+    plan.upload()
+    inter = torch.empty(pre.inter_bytes, dtype=torch.uint8, device=dev)
+    masked, image, mask = (torch.empty((n, 3, S, S), dtype=torch.float32, device=dev) for _ in range(3))
+    pre.run_h(inter)
+    pre.run_v_tensor(inter, masked, image, mask, use_mask=1)
+    return masked, image, mask
