@@ -1047,19 +1047,41 @@ static int launch_heavy_t(IGemmArgs& a, const IGemmPlan& p, float* wp, hipStream
     return MSTG_OK;
 }
 
-size_t igemm_workspace_bytes(IGemmArgs a) {
-    IGemmPlan p;
-    if (plan_igemm(a, p)) return 0;
-    const size_t alt = p32_workspace_bytes(a);  // the persistent kernel packs its filter differently (conv_p32.hip)
-    return p.ws_bytes > alt ? p.ws_bytes : alt;
+// Which kernel runs a forward or input-gradient gather, decided ONCE per IGemmArgs: the launch, the workspace query, the fusion
+// probes and the kernel name all read this struct.
+enum IGemmKind {
+    IG_NONE,       // no kernel takes it: rc says why
+    IG_IMG_DGRAD,  // 3-channel image gradient of a 4x4 stride-2 layer, no MFMA tile to fill (conv_img.hip)
+    IG_P32,        // the persistent kernels of conv_p32.hip: 4x4 stride-2 family and 1x1 at 16 / 32 / 64 channels, heads
+    IG_IGEMM       // the kernels of this file, by plan.stream / plan.heavy
+};
+struct IGemmRoute {
+    IGemmKind kind;
+    int rc;
+    P32Route p32;
+    IGemmPlan plan;
+    // Workspace query: the larger of what this file's kernels and the persistent kernel (it packs its filter differently) need, so that
+    // a caller may query, flip MSTG_P32 and launch.  0 where this file has no plan, whichever kind runs.
+    size_t ws_bytes;
+};
+
+// a: tiled for plan (plan_igemm re-derives its geometry fields; the other kinds do not read them)
+static IGemmRoute route_igemm(IGemmArgs& a) {
+    IGemmRoute r;
+    r.p32 = p32_route(a);
+    r.rc = plan_igemm(a, r.plan);
+    r.ws_bytes = r.rc ? 0 : (r.plan.ws_bytes > r.p32.pack_bytes ? r.plan.ws_bytes : r.p32.pack_bytes);
+    r.kind = img_dgrad_eligible(a) ? IG_IMG_DGRAD : (r.p32.kind != P32_NONE ? IG_P32 : (r.rc ? IG_NONE : IG_IGEMM));
+    return r;
 }
 
 int launch_igemm(IGemmArgs& a, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    if (img_dgrad_eligible(a)) return launch_img_dgrad(a, st);  // 3-channel image gradient of a 4x4 stride-2 layer: no MFMA tile to fill
-    if (p32_eligible(a)) return launch_p32(a, workspace, workspace_bytes, st);  // 4x4 stride-2 family at 16 / 32 / 64 channels
+    IGemmRoute r = route_igemm(a);
+    if (r.kind == IG_IMG_DGRAD) return launch_img_dgrad(a, st);
+    if (r.kind == IG_P32) return launch_p32(a, r.p32, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, st);
+    if (r.kind == IG_NONE) return r.rc;
     a.dbg = 0;
-    IGemmPlan p;
-    if (int rc = plan_igemm(a, p)) return rc;
+    IGemmPlan& p = r.plan;
     { const char* e = env_get(ENV_DBG); if (e) a.dbg = atoi(e); }                       // experiments only: bit 0 = one tap only
     { const char* e = env_get(ENV_DBG_LDS_KB); if (e && !p.heavy) p.lds += (size_t)atoi(e) * 1024; }  // lower the occupancy
     if (!workspace || workspace_bytes < p.ws_bytes) return fail_arg(MSTG_E_WORKSPACE, "conv: workspace too small for the packed filter");
@@ -1153,12 +1175,19 @@ int fill_dgrad_args(const mstg_conv_desc* d, IGemmArgs& a) {
     return MSTG_OK;
 }
 
+namespace {
+struct PackedScope {  // a caller that caches filter packs says the workspace still holds this call's (common.h: t_ws_packed)
+    explicit PackedScope(int packed) { mstg::t_ws_packed = packed != 0; }
+    ~PackedScope() { mstg::t_ws_packed = false; }
+};
+}  // namespace
+
 extern "C" size_t mstg_conv2d_workspace_bytes(const mstg_conv_desc* d) {
     if (check_desc(d)) return 0;
     IGemmArgs f{}, b{};
     fill_fwd_args(d, f);
     if (fill_dgrad_args(d, b)) return 0;
-    const size_t wf = igemm_workspace_bytes(f), wb = igemm_workspace_bytes(b);
+    const size_t wf = route_igemm(f).ws_bytes, wb = route_igemm(b).ws_bytes;
     return wf > wb ? wf : wb;
 }
 
@@ -1173,28 +1202,30 @@ extern "C" int mstg_conv2d_fwd(const mstg_conv_desc* d, const float* x, const fl
 }
 
 // ---- forward with InstanceNorm folded in on either side (only where the persistent kernel runs: conv_p32.hip) ----------------------
-extern "C" int mstg_conv2d_fwd_norm_supported(const mstg_conv_desc* d) {
-    if (check_desc(d)) return 0;
-    IGemmArgs a{};
+static P32Route fwd_norm_route(const mstg_conv_desc* d, IGemmArgs& a) {  // P32_GENERIC where InstanceNorm can be folded into the forward
+    if (check_desc(d)) return P32Route{};
     fill_fwd_args(d, a);
-    return p32_eligible(a) && !a.x_nchw && !a.y_nchw && a.Co != 1 ? 1 : 0;
+    const IGemmRoute r = route_igemm(a);
+    return r.kind == IG_P32 && r.p32.kind == P32_GENERIC ? r.p32 : P32Route{};
+}
+
+extern "C" int mstg_conv2d_fwd_norm_supported(const mstg_conv_desc* d) {
+    IGemmArgs a{};
+    return fwd_norm_route(d, a).kind == P32_GENERIC ? 1 : 0;
 }
 
 // 1 where taking the output's statistics in the epilogue is cheaper than a statistics pass over the output (MSTG_BSUMS_ALL=1: wherever
 // mstg_conv2d_fwd_norm_supported)
 extern "C" int mstg_conv2d_fwd_stats_pays(const mstg_conv_desc* d) {
-    if (!mstg_conv2d_fwd_norm_supported(d)) return 0;
     IGemmArgs a{};
-    fill_fwd_args(d, a);
+    const P32Route r = fwd_norm_route(d, a);
     const char* e = env_get(ENV_BSUMS_ALL);
-    return (e && e[0] == '1') || p32_stats_pays(a) ? 1 : 0;
+    return r.kind == P32_GENERIC && ((e && e[0] == '1') || r.stats_pays()) ? 1 : 0;
 }
 
 extern "C" size_t mstg_conv2d_fwd_norm_workspace_bytes(const mstg_conv_desc* d) {
-    if (check_desc(d)) return 0;
     IGemmArgs a{};
-    fill_fwd_args(d, a);
-    return p32_eligible(a) && !a.x_nchw && !a.y_nchw && a.Co != 1 ? p32_norm_workspace_bytes(a) : 0;
+    return fwd_norm_route(d, a).stats_bytes;
 }
 
 extern "C" int mstg_conv2d_fwd_norm(const mstg_conv_desc* d, const float* x, const float* in_stats, const float* w, const float* bias,
@@ -1202,10 +1233,10 @@ extern "C" int mstg_conv2d_fwd_norm(const mstg_conv_desc* d, const float* x, con
     if (int rc = check_desc(d)) return rc;
     if (!x || !w || !y) return fail_arg(MSTG_E_BADARG, "conv_fwd_norm: null pointer");
     IGemmArgs a{};
-    fill_fwd_args(d, a);
+    const P32Route r = fwd_norm_route(d, a);
     a.x = x; a.y = y; a.w = w; a.bias = bias;
-    if (!p32_eligible(a) || a.x_nchw || a.y_nchw || a.Co == 1) return fail_arg(MSTG_E_UNSUPPORTED, "conv_fwd_norm: only the layers mstg_conv2d_fwd_norm_supported() reports");
-    return launch_p32_norm(a, in_stats, out_stats, workspace, workspace_bytes, (hipStream_t)stream);
+    if (r.kind != P32_GENERIC) return fail_arg(MSTG_E_UNSUPPORTED, "conv_fwd_norm: only the layers mstg_conv2d_fwd_norm_supported() reports");
+    return launch_p32(a, r, in_stats, out_stats, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int mstg_conv2d_dgrad(const mstg_conv_desc* d, const float* dy, const float* w, float* dx, void* workspace,
@@ -1219,20 +1250,22 @@ extern "C" int mstg_conv2d_dgrad(const mstg_conv_desc* d, const float* dy, const
 }
 
 // ---- input gradient + the reductions of the norm backward it feeds (conv_p32.hip, STATS == 2) ----------------------------------------
-extern "C" int mstg_conv2d_dgrad_bsums_supported(const mstg_conv_desc* d) {
-    if (check_desc(d)) return 0;
-    IGemmArgs a{};
-    if (fill_dgrad_args(d, a)) return 0;
-    if (!(p32_generic(a) && a.Co != 1 && !d->accumulate && d->x_ctot == d->Cin && d->x_coff == 0)) return 0;
+static P32Route dgrad_bsums_route(const mstg_conv_desc* d, IGemmArgs& a) {  // P32_GENERIC where the backward-sums epilogue runs
+    if (check_desc(d) || fill_dgrad_args(d, a)) return P32Route{};
+    const IGemmRoute r = route_igemm(a);
+    if (!(r.kind == IG_P32 && r.p32.kind == P32_GENERIC && !d->accumulate && d->x_ctot == d->Cin && d->x_coff == 0)) return P32Route{};
     const char* e = env_get(ENV_BSUMS_ALL);  // MSTG_BSUMS_ALL=1: wherever the kernel can, not only where it pays (tests, A/B)
-    return (e && e[0] == '1') || p32_bsums_pays(a) ? 1 : 0;
+    return (e && e[0] == '1') || r.p32.bsums_pays() ? r.p32 : P32Route{};
+}
+
+extern "C" int mstg_conv2d_dgrad_bsums_supported(const mstg_conv_desc* d) {
+    IGemmArgs a{};
+    return dgrad_bsums_route(d, a).kind == P32_GENERIC ? 1 : 0;
 }
 
 extern "C" size_t mstg_conv2d_dgrad_bsums_workspace_bytes(const mstg_conv_desc* d) {
-    if (!mstg_conv2d_dgrad_bsums_supported(d)) return 0;
     IGemmArgs a{};
-    fill_dgrad_args(d, a);
-    return p32_norm_workspace_bytes(a);
+    return dgrad_bsums_route(d, a).stats_bytes;
 }
 
 extern "C" int mstg_conv2d_dgrad_bsums(const mstg_conv_desc* d, const float* dy, const float* w, float* dx, const float* x_raw,
@@ -1240,23 +1273,15 @@ extern "C" int mstg_conv2d_dgrad_bsums(const mstg_conv_desc* d, const float* dy,
                                        void* stream) {
     if (int rc = check_desc(d)) return rc;
     if (!dy || !w || !dx || !x_raw || !x_stats || !sums) return fail_arg(MSTG_E_BADARG, "conv_dgrad_bsums: null pointer");
-    if (!mstg_conv2d_dgrad_bsums_supported(d)) return fail_arg(MSTG_E_UNSUPPORTED, "conv_dgrad_bsums: only the layers mstg_conv2d_dgrad_bsums_supported() reports");
     IGemmArgs a{};
-    if (int rc = fill_dgrad_args(d, a)) return rc;
+    const P32Route r = dgrad_bsums_route(d, a);
+    if (r.kind != P32_GENERIC) return fail_arg(MSTG_E_UNSUPPORTED, "conv_dgrad_bsums: only the layers mstg_conv2d_dgrad_bsums_supported() reports");
     a.x = dy; a.y = dx; a.w = w; a.bias = nullptr;
-    mstg::t_ws_packed = workspace_packed != 0;
-    const int rc = launch_p32_bsums(a, x_raw, x_stats, sums, workspace, workspace_bytes, (hipStream_t)stream);
-    mstg::t_ws_packed = false;
-    return rc;
+    PackedScope scope(workspace_packed);
+    return launch_p32(a, r, nullptr, sums, x_raw, x_stats, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-// ---- the same entry points for a caller that caches filter packs (common.h: t_ws_packed) -------------------------------------------
-namespace {
-struct PackedScope {
-    explicit PackedScope(int packed) { mstg::t_ws_packed = packed != 0; }
-    ~PackedScope() { mstg::t_ws_packed = false; }
-};
-}  // namespace
+// ---- the same entry points for a caller that caches filter packs -----------------------------------------------------------------------
 extern "C" int mstg_conv2d_fwd_cached(const mstg_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* workspace,
                                       size_t workspace_bytes, int workspace_packed, void* stream) {
     PackedScope scope(workspace_packed);
@@ -1278,14 +1303,15 @@ extern "C" int mstg_conv2d_dgrad_cached(const mstg_conv_desc* d, const float* dy
 const char* igemm_kernel_name(const mstg_conv_desc* d, int pass) {
     static thread_local char name[64];
     IGemmArgs a{};
-    IGemmPlan p;
     if (check_desc(d)) return "";
     if (pass == 0) fill_fwd_args(d, a);
     else if (fill_dgrad_args(d, a)) return "";
-    if (img_dgrad_eligible(a)) { snprintf(name, sizeof(name), "conv_img_dgrad_kernel<%d>", a.Co); return name; }
-    if (plan_igemm(a, p)) return "";
-    if (p32_eligible(a)) return p32_kernel_name(a);
-    if (p.stream) snprintf(name, sizeof(name), "igemm_stream_kernel<%d, %d, %d, %d>", p.V, p.nfw, p.pf, p.src);
+    const IGemmRoute r = route_igemm(a);
+    const IGemmPlan& p = r.plan;  // the fields the MSTG_DISPATCH table of launch_igemm reads
+    if (r.kind == IG_NONE) return "";
+    if (r.kind == IG_P32) return p32_kernel_name(r.p32);
+    if (r.kind == IG_IMG_DGRAD) snprintf(name, sizeof(name), "conv_img_dgrad_kernel<%d>", a.Co);
+    else if (p.stream) snprintf(name, sizeof(name), "igemm_stream_kernel<%d, %d, %d, %d>", p.V, p.nfw, p.pf, p.src);
     else if (p.heavy) snprintf(name, sizeof(name), "igemm_heavy_kernel<%d, %d, %d>", p.V, p.nfw, p.src);
     else snprintf(name, sizeof(name), "igemm_light_kernel<%d, %d, %d>", p.V, p.nfw, p.pf);
     return name;

@@ -25,20 +25,8 @@ namespace mstg {
 struct P32True { static constexpr bool value = true; };
 struct P32False { static constexpr bool value = false; };
 
-constexpr int P32_MAX_STEPS = 64;
-constexpr int P32_MAX_SEG = 4;
 constexpr int P32_TW = 16;
-constexpr int P32_TABLE_BYTES = P32_MAX_STEPS * 4 + P32_MAX_SEG * 16;
-
-struct P32Plan {
-    int nsteps, nseg;
-    struct Seg { int s0, s1, oy, ox; } seg[P32_MAX_SEG];  // one segment per output-parity class (one in all for the stride-2 gather)
-    unsigned koff[P32_MAX_STEPS];                          // byte offset of the step's tap / channel chunk from the lane's pixel base
-    int8_t tky[P32_MAX_STEPS], tkx[P32_MAX_STEPS];         // filter tap of the step
-    int16_t tcb[P32_MAX_STEPS];                            // first source channel of the step
-    int PH, PW, pixstride, oy0, ox0, stride, up, NF, TH, npf, wlds, KW;
-    unsigned m_pw, m_ntile, m_tx;
-};
+constexpr int P32_TABLE_BYTES = P32_MAX_STEPS * 4 + P32_MAX_SEG * 16;  // P32Plan: igemm_args.h
 
 struct P32Args {
     const float* x;
@@ -758,12 +746,11 @@ static int p32d_launch_t(const P32Args& a, const P32dPlan& p, int act, size_t ld
     return MSTG_OK;
 }
 
-static int launch_p32d(const IGemmArgs& g, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    const int TH = g.Ho >= 16 ? 16 : 8;
+static int launch_p32d(const IGemmArgs& g, const P32Route& r, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const int TH = r.head_th;
     P32dPlan p;
     p32d_plan(g, p, TH);
-    const size_t need = 256 + (size_t)p.nsteps * 1024;
-    if (!workspace || workspace_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "conv_p32d: workspace too small for the packed filter");
+    if (!workspace || workspace_bytes < r.pack_bytes) return fail_arg(MSTG_E_WORKSPACE, "conv_p32d: workspace too small for the packed filter");
     P32Args a{};
     a.x = g.x; a.y = g.y;
     a.bias = (const float*)workspace;
@@ -843,8 +830,6 @@ static int launch_co1(const IGemmArgs& a, hipStream_t st) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
-static int p32_plan(const IGemmArgs& a, P32Plan& p);
-
 static bool p32i_eligible(const IGemmArgs& a) {
     return a.x_nchw && !a.y_nchw && a.Cr <= 3 && a.x_coff == 0 && a.x_ctot == a.Cr && a.Co == 16 && a.y_ctot == 16 && a.y_coff == 0 &&
            a.KH == a.KW && a.KH >= 3 && a.KH * a.KW <= 4 * P32I_MAX_STEPS && a.stride == 1 && a.dil == 1 && !a.phase && !a.accumulate &&
@@ -864,11 +849,10 @@ static void p32i_plan(const IGemmArgs& a, P32iPlan& p) {
     p.m_pw = magic_u32((unsigned)p.PW);
 }
 
-static int launch_p32i(const IGemmArgs& g, void* workspace, size_t workspace_bytes, hipStream_t st) {
+static int launch_p32i(const IGemmArgs& g, const P32Route& r, void* workspace, size_t workspace_bytes, hipStream_t st) {
     P32iPlan p;
     p32i_plan(g, p);
-    const size_t need = 256 + (size_t)p.nsteps * 1024;
-    if (!workspace || workspace_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "conv_p32i: workspace too small for the packed filter");
+    if (!workspace || workspace_bytes < r.pack_bytes) return fail_arg(MSTG_E_WORKSPACE, "conv_p32i: workspace too small for the packed filter");
     P32Args a{};
     a.x = g.x; a.y = g.y;
     a.bias = (const float*)workspace;
@@ -893,26 +877,6 @@ static int launch_p32i(const IGemmArgs& g, void* workspace, size_t workspace_byt
     MSTG_LAUNCH(conv_p32i_kernel, dim3((unsigned)g_), dim3(256), lds, st, a, p);
     MSTG_CHECK_LAUNCH("conv_p32i_kernel");
     return MSTG_OK;
-}
-
-bool p32_eligible(const IGemmArgs& a) {
-    const char* e = env_get(ENV_P32);
-    if (e && e[0] == '0') return false;
-    if (co1_eligible(a)) return true;
-    if (p32i_eligible(a)) return true;
-    if (p32d_eligible(a)) return true;
-    auto ch_ok = [](int c) { return c == 16 || c == 32 || c == 64; };
-    if (a.x_nchw || a.y_nchw || a.x_coff || a.y_coff || a.x_ctot != a.Cr || a.y_ctot != a.Co) return false;
-    if (!ch_ok(a.Cr) || !ch_ok(a.Co)) return false;
-    if (a.accumulate || a.act != MSTG_ACT_NONE) return false;
-    if (a.KH == 1 && a.KW == 1) {  // 1x1: a streaming GEMM over the pixels (forward and, through swapped strides, the input gradient)
-        if (a.phase || a.stride != 1 || a.pad != 0 || a.H != a.Ho || a.W != a.Wo) return false;
-    } else {
-        if (a.KH != 4 || a.KW != 4 || a.dil != 1 || a.flip) return false;
-        if (a.phase ? !(a.Ho == 2 * a.H && a.Wo == 2 * a.W) : !(a.stride == 2 && a.pad == 1 && a.H == 2 * a.Ho && a.W == 2 * a.Wo)) return false;
-    }
-    P32Plan p;
-    return p32_plan(a, p) == MSTG_OK;  // e.g. a 64-channel stride-2 patch does not fit the prefetch registers: igemm_light takes it
 }
 
 static int p32_plan(const IGemmArgs& a, P32Plan& p) {
@@ -993,13 +957,43 @@ static int p32_plan(const IGemmArgs& a, P32Plan& p) {
     return MSTG_OK;
 }
 
-size_t p32_workspace_bytes(const IGemmArgs& a) {
-    if (p32_eligible(a) && co1_eligible(a)) return 16;  // no packed filter
-    if (p32_eligible(a) && p32i_eligible(a)) return 256 + (size_t)cdiv(a.KH * a.KW, 4) * 1024;
-    if (p32_eligible(a) && p32d_eligible(a)) return 256 + (size_t)a.KH * cdiv(a.KW, 4) * 1024;
-    P32Plan p;
-    if (!p32_eligible(a) || p32_plan(a, p)) return 0;  // (eligible implies a plan)
-    return 256 + (size_t)p.nsteps * p.NF * 1024;
+// The one place that decides which kernel of this file (if any) takes a gather.  The packed-filter sizes are those of the kernels' pack
+// formats: [step][fragment][lane][4] floats behind a 256-byte bias block.
+P32Route p32_route(const IGemmArgs& a) {
+    P32Route r{};  // P32_NONE
+    const char* e = env_get(ENV_P32);
+    if (e && e[0] == '0') return r;
+    if (co1_eligible(a)) {
+        r.kind = P32_CO1;
+        r.pack_bytes = 16;  // no packed filter
+        return r;
+    }
+    if (p32i_eligible(a)) {
+        r.kind = P32_IMG;
+        r.pack_bytes = 256 + (size_t)cdiv(a.KH * a.KW, 4) * 1024;
+        return r;
+    }
+    if (p32d_eligible(a)) {
+        r.kind = P32_HEAD;
+        r.head_th = a.Ho >= 16 ? 16 : 8;
+        r.pack_bytes = 256 + (size_t)a.KH * cdiv(a.KW, 4) * 1024;
+        return r;
+    }
+    auto ch_ok = [](int c) { return c == 16 || c == 32 || c == 64; };
+    if (a.x_nchw || a.y_nchw || a.x_coff || a.y_coff || a.x_ctot != a.Cr || a.y_ctot != a.Co) return r;
+    if (!ch_ok(a.Cr) || !ch_ok(a.Co)) return r;
+    if (a.accumulate || a.act != MSTG_ACT_NONE) return r;
+    if (a.KH == 1 && a.KW == 1) {  // 1x1: a streaming GEMM over the pixels (forward and, through swapped strides, the input gradient)
+        if (a.phase || a.stride != 1 || a.pad != 0 || a.H != a.Ho || a.W != a.Wo) return r;
+    } else {
+        if (a.KH != 4 || a.KW != 4 || a.dil != 1 || a.flip) return r;
+        if (a.phase ? !(a.Ho == 2 * a.H && a.Wo == 2 * a.W) : !(a.stride == 2 && a.pad == 1 && a.H == 2 * a.Ho && a.W == 2 * a.Wo)) return r;
+    }
+    if (p32_plan(a, r.plan)) return r;  // e.g. a 64-channel stride-2 patch does not fit the prefetch registers: igemm_light takes it
+    r.kind = P32_GENERIC;
+    r.pack_bytes = 256 + (size_t)r.plan.nsteps * r.plan.NF * 1024;
+    r.stats_bytes = ((r.pack_bytes + 255) & ~(size_t)255) + (size_t)a.N * 1024 * 2 * a.Co * sizeof(float);
+    return r;
 }
 
 template <int RPW, int NF, int NPF>
@@ -1031,82 +1025,35 @@ static int p32_launch_t(P32Args& a, const P32Plan& p, size_t lds, long tiles, hi
     return MSTG_OK;
 }
 
+// prefetch registers per thread of the instantiation: the layers of the path need 6 (16-channel stride-2 / 32-channel class patches),
+// 8 (1x1) or 12
+static int p32_npf_regs(const P32Plan& p) { return p.npf <= 6 ? 6 : (p.npf <= 8 ? 8 : 12); }
+
 template <int RPW, int NF>
 static int p32_launch_npf(P32Args& a, const P32Plan& p, size_t lds, long tiles, hipStream_t st, float* out_stats) {
-    // prefetch registers per thread: the layers of the path need 6 (16-channel stride-2 / 32-channel class patches), 8 (1x1) or 12
-    if (p.npf <= 6) return p32_launch_t<RPW, NF, 6>(a, p, lds, tiles, st, out_stats);
-    if (p.npf <= 8) return p32_launch_t<RPW, NF, 8>(a, p, lds, tiles, st, out_stats);
+    const int regs = p32_npf_regs(p);
+    if (regs == 6) return p32_launch_t<RPW, NF, 6>(a, p, lds, tiles, st, out_stats);
+    if (regs == 8) return p32_launch_t<RPW, NF, 8>(a, p, lds, tiles, st, out_stats);
     return p32_launch_t<RPW, NF, 12>(a, p, lds, tiles, st, out_stats);
 }
 
-size_t p32_norm_workspace_bytes(const IGemmArgs& g) {  // packed filter + statistics partials [N][<= 1024 workgroups][2][Cout]
-    const size_t base = p32_workspace_bytes(g);
-    return base ? ((base + 255) & ~(size_t)255) + (size_t)g.N * 1024 * 2 * g.Co * sizeof(float) : 0;
-}
-
-int launch_p32(const IGemmArgs& g, void* workspace, size_t workspace_bytes, hipStream_t st) { return launch_p32_norm(g, nullptr, nullptr, workspace, workspace_bytes, st); }
-
-// the generic (non image-source, non packed-head) persistent kernel runs this launch: what the folded variants need
-bool p32_generic(const IGemmArgs& g) {
-    return p32_eligible(g) && !co1_eligible(g) && !p32i_eligible(g) && !p32d_eligible(g) && !g.x_nchw && !g.y_nchw;
-}
-// Where the backward-sums epilogue is worth its price.  Measured per layer (profiles/r03_bench_b32_256_kernel_table.txt): the epilogue
-// costs the launch 7-30 % where the output has <= 32 channels and the patch <= 8 prefetch registers (then it is cheaper than the
-// two-read statistics pass it replaces: 1x1 fusion convolutions, the 16 <-> 32 channel 4x4 layers), but 45-55 % on the 64-channel /
-// 12-register variants, whose 256 VGPRs it fills -- more than norm_partial_kernel<true> takes on their (small) tensors.
-bool p32_bsums_pays(const IGemmArgs& g) {
-    P32Plan p;
-    if (!p32_generic(g) || p32_plan(g, p)) return false;
-    return g.Co <= 32 && p.npf <= 8;
-}
-
-// ... and the statistics epilogue of a forward launch: 20-25 % on the 12-register variants (32 -> 64 and 64 -> 32 channel 4x4 layers:
-// 88 and 120 us a launch at batch 64, against 35 and 60 us for the statistics pass over their output), a few per cent elsewhere.
-bool p32_stats_pays(const IGemmArgs& g) {
-    P32Plan p;
-    if (!p32_eligible(g) || g.x_nchw || g.y_nchw || g.Co == 1 || p32_plan(g, p)) return false;
-    return p.npf <= 8;
-}
-
-static int launch_p32_full(const IGemmArgs& g, const float* in_stats, float* out_stats, const float* aux, const float* aux_stats,
-                           void* workspace, size_t workspace_bytes, hipStream_t st);
-
-int launch_p32_norm(const IGemmArgs& g, const float* in_stats, float* out_stats, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    return launch_p32_full(g, in_stats, out_stats, nullptr, nullptr, workspace, workspace_bytes, st);
-}
-
-// input-gradient launch whose output dz feeds the backward of ReLU(InstanceNorm(aux)): sums [N][2][Cout] = per (image, channel)
-// sum of dz [aux^ > 0] and of dz [aux^ > 0] aux^ (workspace as for the statistics-emitting forward)
-int launch_p32_bsums(const IGemmArgs& g, const float* aux, const float* aux_stats, float* sums, void* workspace, size_t workspace_bytes,
-                     hipStream_t st) {
-    if (!aux || !aux_stats || !sums) return fail_arg(MSTG_E_BADARG, "conv_p32 bsums: null pointer");
-    if (!p32_generic(g)) return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32 bsums: only the layers the generic persistent kernel runs");
-    return launch_p32_full(g, nullptr, sums, aux, aux_stats, workspace, workspace_bytes, st);
-}
-
-static int launch_p32_full(const IGemmArgs& g, const float* in_stats, float* out_stats, const float* aux, const float* aux_stats,
-                           void* workspace, size_t workspace_bytes, hipStream_t st) {
-    if (co1_eligible(g)) {
-        if (in_stats || out_stats) return fail_arg(MSTG_E_UNSUPPORTED, "conv_co1: no InstanceNorm folding");
-        return launch_co1(g, st);
+int launch_p32(const IGemmArgs& g, const P32Route& r, const float* in_stats, float* out_stats, const float* aux, const float* aux_stats,
+               void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (r.kind != P32_GENERIC) {
+        if (in_stats || out_stats) return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32: InstanceNorm folding only in the generic persistent kernel");
+        if (r.kind == P32_CO1) return launch_co1(g, st);
+        if (r.kind == P32_IMG) return launch_p32i(g, r, workspace, workspace_bytes, st);
+        if (r.kind == P32_HEAD) return launch_p32d(g, r, workspace, workspace_bytes, st);
+        return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32: not a layer of the persistent kernels");
     }
-    if (p32i_eligible(g)) {
-        if (in_stats || out_stats) return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32i: no InstanceNorm folding for the image-source variant");
-        return launch_p32i(g, workspace, workspace_bytes, st);
-    }
-    if (p32d_eligible(g)) {
-        if (in_stats || out_stats) return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32d: no InstanceNorm folding");
-        return launch_p32d(g, workspace, workspace_bytes, st);
-    }
-    P32Plan p;
-    if (int rc = p32_plan(g, p)) return rc;
-    const size_t need = out_stats ? p32_norm_workspace_bytes(g) : 256 + (size_t)p.nsteps * p.NF * 1024;
-    if (!workspace || workspace_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "conv_p32: workspace too small for the packed filter");
+    P32Plan p = r.plan;  // the launch adds the tile-count divisors
+    if (!workspace || workspace_bytes < (out_stats ? r.stats_bytes : r.pack_bytes))
+        return fail_arg(MSTG_E_WORKSPACE, "conv_p32: workspace too small for the packed filter");
     P32Args a;
     a.in_stats = in_stats;
     a.aux = aux;
     a.aux_stats = aux_stats;
-    a.partial = out_stats ? (float*)((char*)workspace + ((256 + (size_t)p.nsteps * p.NF * 1024 + 255) & ~(size_t)255)) : nullptr;
+    a.partial = out_stats ? (float*)((char*)workspace + ((r.pack_bytes + 255) & ~(size_t)255)) : nullptr;
     a.x = g.x; a.y = g.y;
     a.bias = (const float*)workspace;
     a.wpk = (const float*)((const char*)workspace + 256);
@@ -1134,15 +1081,16 @@ static int launch_p32_full(const IGemmArgs& g, const float* in_stats, float* out
     return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32: no kernel variant");
 }
 
-const char* p32_kernel_name(const IGemmArgs& a) {
+const char* p32_kernel_name(const P32Route& r) {
     static thread_local char name[64];
-    if (co1_eligible(a)) return "conv_co1_kernel";
-    if (p32i_eligible(a)) return "conv_p32i_kernel";
-    if (p32d_eligible(a)) return a.Ho >= 16 ? "conv_p32d_kernel<4, 8>" : "conv_p32d_kernel<2, 6>";
-    P32Plan p;
-    if (p32_plan(a, p)) return "";
-    snprintf(name, sizeof(name), "conv_p32_kernel<%d, %d, %d, %s, false>", p.TH / 4, p.NF, p.npf <= 6 ? 6 : (p.npf <= 8 ? 8 : 12),
-             p.wlds ? "true" : "false");  // as rocprofv3 prints it; mstg_conv2d_fwd_norm with out_stats runs the <..., true> instantiation
+    if (r.kind == P32_CO1) return "conv_co1_kernel";
+    if (r.kind == P32_IMG) return "conv_p32i_kernel";
+    if (r.kind == P32_HEAD) return r.head_th == 16 ? "conv_p32d_kernel<4, 8>" : "conv_p32d_kernel<2, 6>";
+    if (r.kind != P32_GENERIC) return "";
+    // as rocprofv3 prints it; the last argument is STATS: 0 here, 1 with the statistics epilogue (mstg_conv2d_fwd_norm with out_stats),
+    // 2 with the backward-sums epilogue (mstg_conv2d_dgrad_bsums)
+    snprintf(name, sizeof(name), "conv_p32_kernel<%d, %d, %d, %s, 0>", r.plan.TH / 4, r.plan.NF, p32_npf_regs(r.plan),
+             r.plan.wlds ? "true" : "false");
     return name;
 }
 

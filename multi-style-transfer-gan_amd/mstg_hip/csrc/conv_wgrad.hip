@@ -1029,11 +1029,6 @@ static WGradArgs wgrad_1x1_block(const WGradArgs& a, const W11Chunks& c, int ig,
     b.with_bias = a.with_bias && ig == 0;
     return b;
 }
-static size_t wgrad_1x1_workspace(const WGradArgs& a) {
-    const W11Chunks c = wgrad_1x1_chunks(a);
-    const WGradArgs b = wgrad_1x1_block(a, c, 0, 0);  // the widest block
-    return (size_t)wgrad_1x1_splits(b) * ((size_t)b.Cg * b.Ch + b.Ch) * sizeof(float);
-}
 
 // dw[gch*s_g + hch*s_h + t] = sum_split partial[split][t][gch][hch]  (+ dbias[hch] from the tail of each split's block).
 // A workgroup owns 64 consecutive outputs: thread (row = tid >> 4, q = tid & 15) sums outputs 4q .. 4q+3 of every 16th split with
@@ -1147,11 +1142,6 @@ static int launch_wgrad_t(WGradArgs& a, const WGradPlan& p, hipStream_t st) {
     return MSTG_OK;
 }
 
-static int wgrad_ts_max_ch() {
-    const char* e = env_get(ENV_WGRAD_TS_MAXCH);
-    return e ? atoi(e) : 128;  // measured: 8-18 % faster than the pixel-split kernel up to 128 grid channels (two fragments per workgroup)
-}
-
 struct TsPlan {
     int TH, NFHT, UW, S, ngroups;
     size_t lds, ws_bytes;
@@ -1160,7 +1150,7 @@ struct TsPlan {
 static TsPlan plan_ts(WGradArgs& a) {
     TsPlan p;
     p.TH = a.stride >= 2 ? 4 : 8;
-    // re-derive the tile geometry for this tile height
+    // re-derive the tile geometry for this tile height (a: tiled for the tap-split kernels from here on; route_wgrad keeps the copy apart)
     a.tiles_y = cdiv(a.hH, p.TH);
     a.ntiles = a.N * a.tiles_x * a.tiles_y;
     a.PH = (p.TH - 1) * a.stride + (a.KH - 1) * a.dil + 1;
@@ -1200,11 +1190,9 @@ static int launch_ts_t(WGradArgs& a, const TsPlan& p, hipStream_t st) {
     return MSTG_OK;
 }
 
-// the persistent kernel takes the 4x4 stride-2 family on aligned, unsliced NHWC tensors (call after plan_ts set PH for TH = 4)
+// the persistent kernel takes the 4x4 stride-2 family (16 plain taps: the caller has checked that) on aligned, unsliced NHWC tensors
 static bool wp_ok(const WGradArgs& a) {
-    const char* e = env_get(ENV_P32);
-    if (e && e[0] == '0') return false;
-    return a.Teff == 16 && a.mode == MODE_PLAIN && a.stride == 2 && a.pad == 1 && a.dil == 1 && !a.g_nchw && !a.h_nchw && !a.g_coff &&
+    return a.stride == 2 && a.pad == 1 && a.dil == 1 && !a.g_nchw && !a.h_nchw && !a.g_coff &&
            !a.h_coff && a.g_ctot == a.Cg && a.h_ctot == a.Ch && a.Cg % 16 == 0 && a.Ch % (16 * WP_NFHT) == 0 && a.gH == 2 * a.hH &&
            a.gW == 2 * a.hW && (size_t)a.gH * a.gW * a.Cg * 4 < ((size_t)1 << 32) && (size_t)a.hH * a.hW * a.Ch * 4 < ((size_t)1 << 32);
 }
@@ -1237,8 +1225,6 @@ static int launch_wp(WGradArgs& a, WpPlan& p, hipStream_t st) {
 
 // the two 7x7 layers with a 3-channel side (see wgrad7_kernel); everything else about them is fixed by the module
 static bool w7_ok(const WGradArgs& a) {
-    const char* e = env_get(ENV_P32);
-    if (e && e[0] == '0') return false;
     if (a.KH != 7 || a.KW != 7 || a.stride != 1 || a.pad != 3 || a.dil != 1 || a.gH != a.hH || a.gW != a.hW) return false;
     if ((size_t)a.hH * a.hW * 16 >= ((size_t)1 << 30)) return false;
     if (a.mode == MODE_PACKX) return a.g_nchw && a.Cg <= 3 && !a.h_nchw && a.Ch == 16 && a.h_ctot == 16 && a.h_coff == 0;
@@ -1303,62 +1289,109 @@ using namespace mstg;
 
 const char* igemm_kernel_name(const mstg_conv_desc* d, int pass);  // conv_igemm.hip
 
+// Which kernel runs a weight-gradient pass, decided ONCE per call by route_wgrad(): the launch, the workspace query, the
+// normalise-on-load probe and the kernel name all read this struct.
+enum WGradKind {
+    WG_1X1,    // wgrad_1x1_kernel, one launch per (<= 64, <= 192) channel block
+    WG_TS,     // wgrad_ts_kernel: taps split over the waves
+    WG_P32,    // wgrad_p32_kernel: the persistent, prefetching form of the tap-split kernel
+    WG_7X7,    // wgrad7_kernel: the two 7x7 layers with a 3-channel side
+    WG_PIXEL   // wgrad_kernel: pixels split over the waves; takes every shape
+};
+struct WGradRoute {
+    WGradKind kind;
+    W11Chunks c11;   // WG_1X1
+    TsPlan ts;       // WG_TS
+    WpPlan wp;       // WG_P32
+    WGradPlan px;    // WG_PIXEL
+    int S;           // partial slabs the launch writes and the reduce kernel sums (WG_1X1: of the widest block; each block has its own)
+    size_t need;     // workspace bytes the launch checks
+    size_t query;    // workspace query: the largest need among the kinds a switch could select for this shape, so that a caller may
+                     // query, flip a switch and launch
+    bool norm_ok;    // the launch can normalise + ReLU the gathered tensor on load (wgrad_p32_kernel and, on whole-image pixel runs, 1x1)
+};
+
+// a: re-tiled for the tap-split kernels where one of them runs (the only call of plan_ts), else left as fill_wgrad_args tiled it
+static WGradRoute route_wgrad(WGradArgs& a) {
+    WGradRoute r{};
+    const char *e_old = env_get(ENV_WGRAD_OLD), *e_max = env_get(ENV_WGRAD_TS_MAXCH), *e_p32 = env_get(ENV_P32);
+    const bool old = e_old && e_old[0] == '1', p32 = !(e_p32 && e_p32[0] == '0');
+    const int ts_max_ch = e_max ? atoi(e_max) : 128;  // measured: 8-18 % faster than the pixel-split kernel up to 128 grid channels (two fragments per workgroup)
+    const size_t slab = ((size_t)a.T * a.Cg * a.Ch + a.Ch) * sizeof(float);
+    // ---- the candidates of this shape
+    const bool one = wgrad_1x1_ok(a), w7 = p32 && w7_ok(a);
+    const bool ts_shape = a.Teff == 16 && a.mode == MODE_PLAIN;  // the only shapes the tap-split kernels take
+    const bool wp = ts_shape && p32 && wp_ok(a);
+    r.px = plan_wgrad(a);
+    WGradArgs t = a;
+    if (ts_shape) r.ts = plan_ts(t);
+    if (wp) r.wp = wp_plan(t);
+    size_t need_11 = 0;
+    if (one) {
+        r.c11 = wgrad_1x1_chunks(a);
+        const WGradArgs b = wgrad_1x1_block(a, r.c11, 0, 0);  // the widest block: its slabs hold every other block's
+        r.S = wgrad_1x1_splits(b);
+        need_11 = (size_t)r.S * ((size_t)b.Cg * b.Ch + b.Ch) * sizeof(float);
+    }
+    const size_t need_7 = w7 ? (size_t)w7_splits(a) * slab : 0;
+    r.query = r.px.ws_bytes;
+    for (size_t w : {ts_shape ? r.ts.ws_bytes : 0, wp ? r.wp.ws_bytes : 0, need_11, need_7})
+        if (w > r.query) r.query = w;
+    // ---- the one that runs.  Measured on MI355X: the tap-split kernel wins where a workgroup gets 32 units (16 taps x 2 column
+    // fragments: the stride-2 / transposed 4x4 layers with 17..32 grid channels); the pixel-split kernel elsewhere
+    if (one) {
+        r.kind = WG_1X1;
+        r.need = need_11;
+        r.norm_ok = a.g_coff == 0;  // for pixel runs that stay inside one image
+        for (int ig = 0; ig < r.c11.ng; ++ig)
+            for (int ih = 0; ih < r.c11.nh; ++ih) {
+                const WGradArgs b = wgrad_1x1_block(a, r.c11, ig, ih);
+                if ((a.hH * a.hW) % wgrad_1x1_tile(b.Cg, b.Ch)) r.norm_ok = false;
+            }
+    } else if (ts_shape && a.Ch > 16 && a.Ch <= ts_max_ch && !old) {
+        a = t;
+        r.kind = wp ? WG_P32 : WG_TS;
+        r.S = wp ? r.wp.S : r.ts.S;
+        r.need = wp ? r.wp.ws_bytes : r.ts.ws_bytes;
+        r.norm_ok = wp;
+    } else if (w7) {
+        r.kind = WG_7X7;
+        r.S = w7_splits(a);
+        r.need = need_7;
+    } else {
+        r.kind = WG_PIXEL;
+        r.S = r.px.S;
+        r.need = r.px.ws_bytes;
+    }
+    return r;
+}
+
 extern "C" const char* mstg_conv2d_kernel_name(const mstg_conv_desc* d, int pass) {
     if (pass != 2) return igemm_kernel_name(d, pass);
     static thread_local char name[64];
     WGradArgs a{};
     if (check_desc(d) || fill_wgrad_args(d, nullptr, nullptr, a)) return "";
-    const bool use_ts = a.Teff == 16 && a.mode == MODE_PLAIN && a.Ch > 16 && a.Ch <= wgrad_ts_max_ch();
-    if (wgrad_1x1_ok(a)) {
-        const WGradArgs b = wgrad_1x1_block(a, wgrad_1x1_chunks(a), 0, 0);
+    const WGradRoute r = route_wgrad(a);
+    if (r.kind == WG_1X1) {  // (of the first, widest channel block)
+        const WGradArgs b = wgrad_1x1_block(a, r.c11, 0, 0);
         snprintf(name, sizeof(name), "wgrad_1x1_kernel<%d, %d>", cdiv(b.Cg, 16), cdiv(cdiv(b.Ch, 16), 4));
-    } else if (use_ts) {
-        const int uw = plan_ts(a).UW;
-        if (wp_ok(a)) snprintf(name, sizeof(name), "wgrad_p32_kernel");
-        else snprintf(name, sizeof(name), "wgrad_ts_kernel<%d>", uw);
-    } else if (w7_ok(a)) {
-        snprintf(name, sizeof(name), "wgrad7_kernel<%d>", a.mode);
-    } else {
-        const WGradPlan p = plan_wgrad(a);
-        snprintf(name, sizeof(name), "wgrad_kernel<%d, %d>", p.tg, p.nfh);
-    }
+    } else if (r.kind == WG_TS) snprintf(name, sizeof(name), "wgrad_ts_kernel<%d>", r.ts.UW);
+    else if (r.kind == WG_P32) snprintf(name, sizeof(name), "wgrad_p32_kernel");
+    else if (r.kind == WG_7X7) snprintf(name, sizeof(name), "wgrad7_kernel<%d>", a.mode);
+    else snprintf(name, sizeof(name), "wgrad_kernel<%d, %d>", r.px.tg, r.px.nfh);
     return name;
 }
 
 extern "C" size_t mstg_conv2d_wgrad_workspace_bytes(const mstg_conv_desc* d) {
-    if (check_desc(d)) return 0;
     WGradArgs a{};
-    if (fill_wgrad_args(d, nullptr, nullptr, a)) return 0;
-    const size_t w_old = plan_wgrad(a).ws_bytes;
-    size_t w_ts = (a.Teff == 16 && a.mode == MODE_PLAIN) ? plan_ts(a).ws_bytes : 0;  // the only shapes the tap-split kernel takes
-    if (w_ts && wp_ok(a)) { const size_t w_p = wp_plan(a).ws_bytes; if (w_p > w_ts) w_ts = w_p; }
-    const size_t w_11 = wgrad_1x1_ok(a) ? wgrad_1x1_workspace(a) : 0;
-    size_t w = w_old > w_ts ? w_old : w_ts;
-    if (w7_ok(a)) { const size_t w_7 = (size_t)w7_splits(a) * ((size_t)a.T * a.Cg * a.Ch + a.Ch) * sizeof(float); if (w_7 > w) w = w_7; }
-    return w > w_11 ? w : w_11;
-}
-
-static bool wgrad_ts_path(const WGradArgs& a) {
-    return a.Teff == 16 && a.mode == MODE_PLAIN && a.Ch > 16 && a.Ch <= wgrad_ts_max_ch() &&
-           !(env_get(ENV_WGRAD_OLD) && env_get(ENV_WGRAD_OLD)[0] == '1');
-}
-static bool wgrad_norm_ok(const WGradArgs& a) {  // normalise-on-load exists in the persistent 4x4 stride-2 kernel and in the 1x1 kernel
-    if (!wgrad_1x1_ok(a)) return wgrad_ts_path(a) && wp_ok(a);
-    if (a.g_coff != 0) return false;  // 1x1: for pixel runs that stay inside one image
-    const W11Chunks c = wgrad_1x1_chunks(a);
-    for (int ig = 0; ig < c.ng; ++ig)
-        for (int ih = 0; ih < c.nh; ++ih) {
-            const WGradArgs b = wgrad_1x1_block(a, c, ig, ih);
-            if ((a.hH * a.hW) % wgrad_1x1_tile(b.Cg, b.Ch)) return false;
-        }
-    return true;
+    if (check_desc(d) || fill_wgrad_args(d, nullptr, nullptr, a)) return 0;
+    return route_wgrad(a).query;
 }
 
 extern "C" int mstg_conv2d_wgrad_norm_supported(const mstg_conv_desc* d) {
-    if (check_desc(d) || d->transposed) return 0;
     WGradArgs a{};
-    if (fill_wgrad_args(d, nullptr, nullptr, a)) return 0;
-    return wgrad_norm_ok(a) ? 1 : 0;
+    if (check_desc(d) || d->transposed || fill_wgrad_args(d, nullptr, nullptr, a)) return 0;
+    return route_wgrad(a).norm_ok ? 1 : 0;
 }
 
 static int conv2d_wgrad_impl(const mstg_conv_desc* d, const float* x, const float* in_stats, const float* dy, float* dw, float* dbias,
@@ -1386,16 +1419,13 @@ static int conv2d_wgrad_impl(const mstg_conv_desc* d, const float* x, const floa
     hipStream_t st = (hipStream_t)stream;
     a.partial = (float*)workspace;
     a.with_bias = dbias != nullptr;
-    int S;
-    // measured on MI355X: the tap-split kernel wins where a workgroup gets 32 units (16 taps x 2 column fragments: the
-    // stride-2 / transposed 4x4 layers with 17..32 grid channels); the pixel-split kernel elsewhere
-    const bool use_ts = a.Teff == 16 && a.mode == MODE_PLAIN && a.Ch > 16 && a.Ch <= wgrad_ts_max_ch();
-    if (in_stats && (d->transposed || !wgrad_norm_ok(a)))
+    WGradRoute r = route_wgrad(a);
+    if (in_stats && (d->transposed || !r.norm_ok))
         return fail_arg(MSTG_E_UNSUPPORTED, "conv_wgrad_norm: only the layers mstg_conv2d_wgrad_norm_supported() reports");
-    if (wgrad_1x1_ok(a)) {
-        if (workspace_bytes < wgrad_1x1_workspace(a)) return fail_arg(MSTG_E_WORKSPACE, "conv_wgrad: workspace too small");
+    if (workspace_bytes < r.need) return fail_arg(MSTG_E_WORKSPACE, "conv_wgrad: workspace too small");
+    if (r.kind == WG_1X1) {
         const long P = (long)a.N * a.hH * a.hW;
-        const W11Chunks c = wgrad_1x1_chunks(a);
+        const W11Chunks& c = r.c11;
         const int s_g = 1, s_h = d->transposed ? d->Cout : d->Cin;  // T == 1
         for (int ig = 0; ig < c.ng; ++ig)
             for (int ih = 0; ih < c.nh; ++ih) {
@@ -1416,27 +1446,17 @@ static int conv2d_wgrad_impl(const mstg_conv_desc* d, const float* x, const floa
                 MSTG_CHECK_LAUNCH("wgrad_reduce_kernel");
             }
         return MSTG_OK;
-    } else if (use_ts && !(env_get(ENV_WGRAD_OLD) && env_get(ENV_WGRAD_OLD)[0] == '1')) {
-        const TsPlan p = plan_ts(a);
-        if (wp_ok(a)) {  // persistent, prefetching form of the same kernel
-            a.g_stats = in_stats;
-            WpPlan q = wp_plan(a);
-            if (workspace_bytes < q.ws_bytes) return fail_arg(MSTG_E_WORKSPACE, "conv_wgrad: workspace too small");
-            if (int rc = launch_wp(a, q, st)) return rc;
-            S = q.S;
-        } else {
-            if (workspace_bytes < p.ws_bytes) return fail_arg(MSTG_E_WORKSPACE, "conv_wgrad: workspace too small");
-            int rc = p.UW == 4 ? launch_ts_t<4>(a, p, st) : (p.UW == 8 ? launch_ts_t<8>(a, p, st) : launch_ts_t<16>(a, p, st));
-            if (rc) return rc;
-            S = p.S;
-        }
-    } else if (w7_ok(a)) {
-        S = w7_splits(a);
-        if (workspace_bytes < (size_t)S * ((size_t)a.T * a.Cg * a.Ch + a.Ch) * sizeof(float)) return fail_arg(MSTG_E_WORKSPACE, "conv_wgrad: workspace too small");
-        if (int rc = launch_w7(a, S, st)) return rc;
+    } else if (r.kind == WG_P32) {
+        a.g_stats = in_stats;
+        if (int rc = launch_wp(a, r.wp, st)) return rc;
+        r.S = r.wp.S;  // clamped to what the CUs hold
+    } else if (r.kind == WG_TS) {
+        const TsPlan& p = r.ts;
+        if (int rc = p.UW == 4 ? launch_ts_t<4>(a, p, st) : (p.UW == 8 ? launch_ts_t<8>(a, p, st) : launch_ts_t<16>(a, p, st))) return rc;
+    } else if (r.kind == WG_7X7) {
+        if (int rc = launch_w7(a, r.S, st)) return rc;
     } else {
-        const WGradPlan p = plan_wgrad(a);
-        if (workspace_bytes < p.ws_bytes) return fail_arg(MSTG_E_WORKSPACE, "conv_wgrad: workspace too small");
+        const WGradPlan& p = r.px;
         a.TGn = p.TGn;
         int rc = MSTG_E_UNSUPPORTED;
         if (p.tg == 1 && p.nfh == 1) rc = launch_wgrad_t<1, 1>(a, p, st);
@@ -1449,14 +1469,13 @@ static int conv2d_wgrad_impl(const mstg_conv_desc* d, const float* x, const floa
         else if (p.tg == 16 && p.nfh == 1) rc = launch_wgrad_t<16, 1>(a, p, st);
         else if (p.tg == 16 && p.nfh == 2) rc = launch_wgrad_t<16, 2>(a, p, st);
         if (rc) return rc;
-        S = p.S;
     }
     const int T = a.T, total = T * a.Cg * a.Ch;
     // Conv2d: dw[co][ci][t] (gch = ci, hch = co) ; ConvTranspose2d: dw[ci][co][t] (gch = co, hch = ci)
     const int s_g = T;
     const int s_h = d->transposed ? d->Cout * T : d->Cin * T;
     const int pstride = total + (a.with_bias ? a.Ch : 0);
-    MSTG_LAUNCH(wgrad_reduce_kernel, dim3(cdiv(pstride, 64)), dim3(256), 0, st, a.partial, dw, dbias, S, T, a.Cg, a.Ch, s_g, s_h,
+    MSTG_LAUNCH(wgrad_reduce_kernel, dim3(cdiv(pstride, 64)), dim3(256), 0, st, a.partial, dw, dbias, r.S, T, a.Cg, a.Ch, s_g, s_h,
                        pstride, d->accumulate);
     MSTG_CHECK_LAUNCH("wgrad_reduce_kernel");
     return MSTG_OK;

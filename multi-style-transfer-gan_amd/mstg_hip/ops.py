@@ -456,7 +456,7 @@ class ConvStatsFn(torch.autograd.Function):
         d = make_desc(N, H, W, Cin, Ho, Wo, Cout, k, stride, pad, dil, transposed)
         ws, packed = _cached_ws((w, b), "fwd_norm", _dkey(d, 0), lib.mstg_conv2d_fwd_norm_workspace_bytes(C.byref(d)), x.device)
         fl, by = _conv_cost(d)
-        _timed(_kernel_name(d, 0).replace(", false>", ", true>"), fl, by, lambda: _lib.check(  # the STATS instantiation
+        _timed(_kernel_name(d, 0).replace(", 0>", ", 1>"), fl, by, lambda: _lib.check(  # the STATS instantiation
             lib.mstg_conv2d_fwd_norm_cached(C.byref(d), _p(x), None, _p(w), _p(b), _p(y), _p(stats), _p(ws), ws.numel() * 4, packed,
                                             _stream()), "mstg_conv2d_fwd_norm"), _conv_detail("fwd", d))
         ctx.cfg, ctx.dims, ctx.has_bias = (k, stride, pad, dil, transposed, 0, 0, ACT_NONE), (N, H, W, Cin, Ho, Wo, Cout), b is not None
@@ -505,7 +505,7 @@ class MSFusionFn(torch.autograd.Function):
         d = make_desc(N, H, W, Cn, Ho, Wo, Cout, k, stride, pad, dil)
         ws2, packed = _cached_ws((w, b), "fwd_norm", _dkey(d, 0), lib.mstg_conv2d_fwd_norm_workspace_bytes(C.byref(d)), cat.device)
         fl, by = _conv_cost(d)
-        _timed(_kernel_name(d, 0).replace(", false>", ", true>"), fl, by, lambda: _lib.check(
+        _timed(_kernel_name(d, 0).replace(", 0>", ", 1>"), fl, by, lambda: _lib.check(
             lib.mstg_conv2d_fwd_norm_cached(C.byref(d), _p(cat), _p(stats), _p(w), _p(b), _p(y), _p(ystats), _p(ws2), ws2.numel() * 4,
                                             packed, _stream()), "mstg_conv2d_fwd_norm"), _conv_detail("fwd", d))
         ctx.dims, ctx.has_bias, ctx.prefs, ctx.cfg = (N, H, W, Cn, Cout), b is not None, (w, b), tuple(cfg)

@@ -50,6 +50,7 @@ CONV_CASES = [
     ("stem7x7 3->16 nchw-in", 1, 64, 64, 3, 16, 7, 1, 3, 1, 0, 1, 0, 0),
     ("head7x7 8->3 nchw-out tanh", 2, 32, 48, 8, 3, 7, 1, 3, 1, 0, 0, 1, 3),
     ("head7x7 16->3 nchw-out tanh", 1, 64, 64, 16, 3, 7, 1, 3, 1, 0, 0, 1, 3),
+    ("head7x7 16->3 nchw-out tanh 8x12 (8-row tiles)", 1, 8, 12, 16, 3, 7, 1, 3, 1, 0, 0, 1, 3),
     ("k4s2 8->16", 2, 32, 48, 8, 16, 4, 2, 1, 1, 0, 0, 0, 0),
     ("k4s2 16->32", 1, 64, 64, 16, 32, 4, 2, 1, 1, 0, 0, 0, 0),
     ("k4s2 32->64", 2, 16, 16, 32, 64, 4, 2, 1, 1, 0, 0, 0, 0),
@@ -275,7 +276,7 @@ def test_conv_channel_slices_and_accumulate(N, H, W, ch):
 @pytest.mark.parametrize("env", ["MSTG_MS_UNFUSED=1", "MSTG_MS_WGRAD_PACKED=0", "MSTG_MS_FWD4=0", "MSTG_MS_FWD4=1", "MSTG_MS_FWD4=2", "MSTG_WGLOB=0",
                                  "MSTG_WGRAD_1X1=0", "MSTG_PF=2", "MSTG_NO_DPACK=1", "MSTG_WGRAD_PLAIN=1", "MSTG_ATTN_BLK64=0", "MSTG_ATTN_BLK4=0",
                                  "MSTG_P32=0", "MSTG_P32_TH=4", "MSTG_P32_TH=8", "MSTG_P32_TH=16", "MSTG_P32_WLDS=0", "MSTG_P32_WLDS=1",
-                                 "MSTG_ATTN_REG=0", "MSTG_ATTN_BIG32=1", "MSTG_CONV_IMG=0"])
+                                 "MSTG_ATTN_REG=0", "MSTG_ATTN_BIG32=1", "MSTG_CONV_IMG=0", "MSTG_WGRAD_OLD=1"])
 def test_kernel_selection_switches_keep_parity(env, monkeypatch):
     """Every runtime switch of INTEGRATION.md section 3 selects another kernel for the same arithmetic: the fallbacks stay correct."""
     k, v = env.split("=")
@@ -291,6 +292,10 @@ def test_kernel_selection_switches_keep_parity(env, monkeypatch):
     if k == "MSTG_CONV_IMG":  # the image-side 4x4 stride-2 layer back on the MFMA kernels
         for case in CONV_CASES:
             if case[0].startswith("img") or "D stem" in case[0]:
+                test_conv_fwd_bwd(case)
+    if k == "MSTG_WGRAD_OLD":  # the 4x4 stride-2 weight gradients back on the pixel-split kernel
+        for case in CONV_CASES:
+            if case[0].startswith(("p32 k4s2", "p32 convT", "convT", "k4s2")) and case[0] != "k4s2 16->32":
                 test_conv_fwd_bwd(case)
     if k == "MSTG_ATTN_BLK64":
         test_window_attention_core(2, 8, 8, 64)
@@ -310,6 +315,47 @@ def test_kernel_selection_switches_keep_parity(env, monkeypatch):
         import test_gpu_normfuse
         test_gpu_normfuse.test_norm_attention_fused_vs_chain_and_torch(32, 2, 24, 16)
         test_gpu_normfuse.test_norm_attention_fused_vs_chain_and_torch(32, 3, 96, 64)
+
+
+@pytest.mark.parametrize("env", ["default", "MSTG_P32=0", "MSTG_WGRAD_OLD=1", "MSTG_WGRAD_1X1=0", "MSTG_WGRAD_PLAIN=1", "MSTG_NO_DPACK=1",
+                                 "MSTG_CONV_IMG=0", "MSTG_STREAM=1f", "MSTG_IGEMM=h", "MSTG_P32_TH=4"])
+def test_kernel_name_is_the_launched_kernel(env, monkeypatch):
+    """mstg_conv2d_kernel_name reports, for each pass, a symbol the call of that pass really launches (as the library's per-launch
+    profiler records it) -- under the default routing and under every switch that re-routes a pass.  ops._dkey keys cached filter
+    packs by that name and KernelTimer books a call's work on it.  Results are not compared here (the parity tests do that)."""
+    import ctypes
+    from mstg_hip import _lib, ops
+    if env != "default":
+        monkeypatch.setenv(*env.split("="))
+    ops.refresh_env()
+    lib = _lib.load()
+    calls = []  # (case, pass, reported name, first record, one past the last record)
+    ops.KernelTimer.start()
+    try:
+        for case in CONV_CASES + STREAM_CASES:
+            name, N, H, W, Cin, Cout, k, s, p, d, tr, x_nchw, y_nchw, act = case
+            if "256x256 N4" in name:
+                continue
+            Ho, Wo = ops.conv_out_hw(H, W, k, s, p, d, tr)
+            x = rnd((N, Cin, H, W) if x_nchw else (N, H, W, Cin), 1).to(DEV)
+            dy = rnd((N, Cout, Ho, Wo) if y_nchw else (N, Ho, Wo, Cout), 2).to(DEV)
+            w = rnd((Cin, Cout, k, k) if tr else (Cout, Cin, k, k), 3, 0.1).to(DEV)
+            b = rnd((Cout,), 4, 0.3).to(DEV)
+            y, dx, dw, db = torch.empty_like(dy), torch.empty_like(x), torch.empty_like(w), torch.empty_like(b)
+            fwd = ops.make_desc(N, H, W, Cin, Ho, Wo, Cout, k, s, p, d, tr, x_nchw, y_nchw, act=act)
+            bwd = ops.make_desc(N, H, W, Cin, Ho, Wo, Cout, k, s, p, d, tr, x_nchw, y_nchw)
+            for ps, desc, run in ((0, fwd, lambda: ops.conv_fwd_raw(fwd, x, w, b, y)),
+                                  (1, bwd, lambda: ops.conv_dgrad_raw(bwd, dy, w, dx)),
+                                  (2, bwd, lambda: ops.conv_wgrad_raw(bwd, x, dy, dw, None if tr else db))):
+                c0 = lib.mstg_prof_count()
+                run()
+                calls.append((name, ps, lib.mstg_conv2d_kernel_name(ctypes.byref(desc), ps).decode(), c0, lib.mstg_prof_count()))
+        symbols = [nm for nm, _ in ops.KernelTimer.kernels()]
+    finally:
+        ops.KernelTimer.stop()
+    assert len(calls) == 3 * sum("256x256 N4" not in c[0] for c in CONV_CASES + STREAM_CASES)
+    wrong = [(name, ps, reported, symbols[c0:c1]) for name, ps, reported, c0, c1 in calls if reported not in symbols[c0:c1]]
+    assert not wrong, wrong
 
 
 NORM_CASES = [(2, 16, 24, 8, 1), (1, 64, 64, 16, 1), (3, 7, 9, 32, 2), (2, 4, 4, 64, 2), (1, 128, 128, 16, 1), (2, 2, 2, 64, 2),

@@ -17,7 +17,7 @@ dy = torch.randn((N, Ho, Wo, Cout), device=dev)
 desc = ops.make_desc(N, H, W, Cin, Ho, Wo, Cout, k, s_, p, 1, int(T), 0, 0)
 dw = torch.empty_like(conv.weight, device=dev)
 db = None if T else torch.empty(Cout, device=dev)
-print("kernel:", ops.conv_kernel_name(desc, 2) if hasattr(ops, "conv_kernel_name") else "?")
+print("kernel:", lib.mstg_conv2d_kernel_name(ctypes.byref(desc), 2).decode())
 for _ in range(3):
     ops.conv_wgrad_raw(desc, x, dy, dw, db)
 torch.cuda.synchronize()
