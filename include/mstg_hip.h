@@ -482,7 +482,7 @@ int mstg_tensor_to_u8(const float* y, int H, int W, unsigned char* dst, void* st
  * out = clip(orig * (1 - w) + styled * w, 0, 255).astype(uint8).  weight_map == NULL: w = strength everywhere and
  * one_minus_strength is the caller's double 1 - strength (process_local_style mode 'simple', batch_process_images.py:304-312);
  * else w = weight_map[y][x] (float64, H x W: the 'enhanced' / 'advanced' weight-map blend of :340-342 / :386-387 followed by the
- * clip + cast of :352 -- the masks themselves come from cv2 / scipy on the host and are not part of this library). */
+ * clip + cast of :352 -- the caller's own map, or the one mstg_local_style_weight_map builds from the canvas). */
 int mstg_blend_u8(const unsigned char* orig, const unsigned char* styled, double one_minus_strength, double strength,
                   const double* weight_map /*nullable*/, unsigned char* out, int H, int W, void* stream);
 
@@ -564,6 +564,43 @@ int mstg_img_batch_tensor_to_u8(const void* y, int is_f16, int N, int H, int W, 
 size_t mstg_image_metrics_workspace_bytes(int N, int H, int W); /* 0 for an invalid shape */
 int mstg_image_metrics_u8(const unsigned char* a, const unsigned char* b, int N, int H, int W, double* out /* [N][6] */,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The per-pixel weight map of process_local_style(mode='enhanced') (batch_process_images.py:312-342, detect_sky :126-150; the same
+ * map with coefficient 0.4 in mode 'advanced', :355-384), built on the device for N canvases (N, H, W, 3) uint8 in three launches
+ * whatever N.  OpenCV's 8-bit integer algorithms are restated from their definitions (not compared with an OpenCV binary):
+ *   gray  = cv2.cvtColor(COLOR_RGB2GRAY) (:321)        = (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14;
+ *   sky   = detect_sky's mask (:134-144)               = (v > 150) & (s < 100) with v = max(R, G, B), diff = v - min(R, G, B),
+ *           s = (diff * sdiv[v] + 2048) >> 12, sdiv[0] = 0, sdiv[i] = round-half-even(1044480 / i) (8-bit COLOR_RGB2HSV);
+ *   state = cv2.Canny(gray, 50, 150) before hysteresis (:322): 3x3 Sobel with replicated borders, m = |dx| + |dy| (0 outside the
+ *           image); for m > 50 with x = |dx|, y = |dy| << 15, t = x * 13573: y < t keeps m > m[left] && m >= m[right];
+ *           y > t + (x << 16) keeps m > m[up] && m >= m[down]; else s = (dx ^ dy) < 0 ? -1 : 1 keeps m > m[y-1][x-s] && m > m[y+1][x+s];
+ *           state byte 2 = kept and m > 150, 0 = kept (a candidate), 1 = everything else;
+ *   edge  = the hysteresis of Canny: 1 where a 2 is reached from the pixel through 8-connected states != 1;
+ *   detail = scipy.ndimage.gaussian_filter(edge.astype(float), sigma=2) > 0.1 (:327): float64, radius 8, 'reflect', axis 0 then 1;
+ *   has_sky = (double)count / (double)(H * W) > 0.7 (:147), read on the device;
+ *   weight = w_base; = w_sky where has_sky && sky (:333-334); = w_detail where detail (:337-338, assigned last).
+ * The caller computes the three weights as the reference does: strength, min(strength + 0.2, 1.0), max(strength - 0.3 * detail, 0.0).
+ * All masks are (N, H, W) bytes holding 0 / 1.  Integer arithmetic up to the Gaussian, a fixed summation order, no
+ * floating-point atomics: bit-reproducible.  The hysteresis keeps one byte per pixel of an image in LDS: H * W <=
+ * MSTG_LOCAL_STYLE_MAX_PIXELS, else MSTG_E_UNSUPPORTED (the message names the size); prepare and weights take any H, W >= 1.
+ * Out of scope: enhance_colors (cv2.convertScaleAbs), smooth (smooth_transitions) and the rest of mode 'advanced'.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_LOCAL_STYLE_MAX_PIXELS 147456 /* 144 KiB of the 160 KiB of LDS of a CU: 256 x 256, up to 384 x 384 */
+/* bytes mstg_local_style_weight_map needs for (N, H, W); 0 for an invalid or unsupported shape (mstg_last_error says which) */
+size_t mstg_local_style_workspace_bytes(int N, int H, int W);
+/* stage A: state map, sky mask, sky_count[n] = number of sky pixels of image n (zeroed here, then integer atomics), and the gray
+ * plane where gray != NULL */
+int mstg_local_style_prepare(const unsigned char* canvas, int N, int H, int W, unsigned char* state, unsigned char* sky, int* sky_count,
+                             unsigned char* gray /*nullable*/, void* stream);
+/* stage B: state map in (any byte other than 0 and 2 counts as 1), edge mask out; one workgroup per image */
+int mstg_local_style_hysteresis(const unsigned char* state, int N, int H, int W, unsigned char* edge, void* stream);
+/* stage C: weight_map (N, H, W) float64 as mstg_blend_u8 consumes it, and the detail mask where detail != NULL */
+int mstg_local_style_weights(const unsigned char* edge, const unsigned char* sky, const int* sky_count, int N, int H, int W, double w_base,
+                             double w_sky, double w_detail, double* weight_map, unsigned char* detail /*nullable*/, void* stream);
+/* the three stages on the caller's workspace (16-byte aligned, mstg_local_style_workspace_bytes) */
+int mstg_local_style_weight_map(const unsigned char* canvas, int N, int H, int W, double w_base, double w_sky, double w_detail,
+                                double* weight_map, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain

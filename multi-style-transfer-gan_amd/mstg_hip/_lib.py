@@ -185,7 +185,14 @@ SIGNATURES = {
     "mstg_img_batch_tensor_to_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mstg_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_image_metrics_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mstg_local_style_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_local_style_prepare": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mstg_local_style_hysteresis": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "mstg_local_style_weights": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "mstg_local_style_weight_map": (_i, [_vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
+
+LOCAL_STYLE_MAX_PIXELS = 147456  # MSTG_LOCAL_STYLE_MAX_PIXELS
 
 _lib = None
 

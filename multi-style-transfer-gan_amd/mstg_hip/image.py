@@ -126,7 +126,8 @@ def to_u8(y: torch.Tensor) -> torch.Tensor:
 def blend_u8(orig: torch.Tensor, styled: torch.Tensor, strength=None, weight_map=None) -> torch.Tensor:
     """``np.clip(orig * (1 - w) + styled * w, 0, 255).astype(np.uint8)`` on two (H, W, 3) uint8 images, bit for bit as numpy
     evaluates it in float64: w = the scalar ``strength`` (process_local_style mode 'simple', batch_process_images.py:304-312) or a
-    float64 (H, W) ``weight_map`` (the 'enhanced' / 'advanced' blend of :340-342, :386-387 given a mask made on the host)."""
+    float64 (H, W) ``weight_map`` (the 'enhanced' / 'advanced' blend of :340-342, :386-387; ``enhanced_weight_map`` builds the
+    'enhanced' map on the device)."""
     orig, styled = _req_u8(orig), _req_u8(styled)
     if orig.shape != styled.shape:
         raise RuntimeError(f"mstg_hip blend: shapes differ {tuple(orig.shape)} vs {tuple(styled.shape)}")
@@ -145,6 +146,49 @@ def blend_u8(orig: torch.Tensor, styled: torch.Tensor, strength=None, weight_map
         w0 = 1 - w1  # Python's double subtraction, as in the reference's expression
     _lib.check(_lib.load().mstg_blend_u8(_p(orig), _p(styled), w0, w1, _p(wm), _p(out), H, W, _stream()), "mstg_blend_u8")
     return out
+
+
+def local_style_weights(strength, detail, detail_coeff=0.3):
+    """(w_base, w_sky, w_detail) in Python's own doubles, as the reference forms them (batch_process_images.py:330, :334, :337;
+    ``detail_coeff`` is 0.3 in mode 'enhanced' and 0.4 in mode 'advanced', :383)."""
+    return float(strength), min(strength + 0.2, 1.0), max(strength - detail_coeff * detail, 0.0)
+
+
+def enhanced_weight_map(canvas_u8: torch.Tensor, strength=0.8, detail=0.7, detail_coeff=0.3, return_masks=False):
+    """The float64 weight map of ``process_local_style(mode='enhanced', enhance_colors=False, smooth=False)``
+    (batch_process_images.py:312-338) of an (H, W, 3) or (N, H, W, 3) uint8 canvas on the GPU, built there in three launches
+    whatever N (csrc/local_style.hip): ``detect_sky``'s HSV mask and its 70 % rule, ``cv2.Canny(gray, 50, 150)``,
+    ``scipy.ndimage.gaussian_filter(edges, sigma=2) > 0.1`` and the three weight levels; H * W <= 147456 per image.  OpenCV's
+    integer steps are restated from their definitions (include/mstg_hip.h), not compared with an OpenCV binary.  Returns the
+    (H, W) / (N, H, W) map; with ``return_masks`` also the sky, edge and detail masks (bool) and the ``has_sky`` flag(s), all on
+    the device.  ``enhance_colors``, ``smooth`` and the rest of mode 'advanced' are not built."""
+    single = canvas_u8.dim() == 3
+    c = canvas_u8.unsqueeze(0) if single else canvas_u8
+    if not c.is_cuda or c.dtype != torch.uint8 or c.dim() != 4 or c.shape[3] != 3 or c.shape[0] < 1:
+        raise RuntimeError("mstg_hip image: expected a uint8 (H, W, 3) or (N, H, W, 3) canvas on the GPU")
+    c = c.contiguous()
+    N, H, W = c.shape[:3]
+    w_base, w_sky, w_detail = local_style_weights(strength, detail, detail_coeff)
+    lib = _lib.load()
+    wm = torch.empty((N, H, W), dtype=torch.float64, device=c.device)
+    if not return_masks:
+        need = lib.mstg_local_style_workspace_bytes(N, H, W)  # 0: the call below names what is wrong with the shape
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=c.device)
+        _lib.check(lib.mstg_local_style_weight_map(_p(c), N, H, W, w_base, w_sky, w_detail, _p(wm), _p(ws), need, _stream()),
+                   "mstg_local_style_weight_map")
+        return wm[0] if single else wm
+    state, sky, edge, det = (torch.empty((N, H, W), dtype=torch.uint8, device=c.device) for _ in range(4))
+    count = torch.empty(N, dtype=torch.int32, device=c.device)
+    _lib.check(lib.mstg_local_style_prepare(_p(c), N, H, W, _p(state), _p(sky), _p(count), None, _stream()), "mstg_local_style_prepare")
+    _lib.check(lib.mstg_local_style_hysteresis(_p(state), N, H, W, _p(edge), _stream()), "mstg_local_style_hysteresis")
+    _lib.check(lib.mstg_local_style_weights(_p(edge), _p(sky), _p(count), N, H, W, w_base, w_sky, w_detail, _p(wm), _p(det), _stream()),
+               "mstg_local_style_weights")
+    # count / (H * W) > 0.7 in doubles, as the kernel and the reference evaluate it, is 10 * count > 7 * H * W: the quotient of an
+    # exact 7 / 10 rounds to the double 0.7 itself, and the next possible ratio lies 1 / (10 H W) above it, far more than an ulp.
+    # (A torch division by a Python scalar multiplies by the reciprocal on the device and calls 7000 / 10000 greater than 0.7.)
+    has_sky = count.long() * 10 > 7 * H * W
+    out = (wm, sky.view(torch.bool), edge.view(torch.bool), det.view(torch.bool), has_sky)
+    return tuple(t[0] for t in out) if single else out
 
 
 # ---- the callers, restated on the device ----------------------------------------------------------------------------------
@@ -195,13 +239,14 @@ def process_cyclegan(model, img_u8: torch.Tensor, target=256) -> torch.Tensor:
     return out
 
 
-def process_local_style(model, img_u8: torch.Tensor, mode="simple", strength=0.8, weight_map=None, target=256) -> torch.Tensor:
-    """``process_local_style`` of the reference (batch_process_images.py:255-441) without the file I/O, on the GPU end to end for
-    the modes that are byte arithmetic: 'simple' (strength blend of the letterboxed original with the styled image, :304-312),
-    'weight_map' (the per-pixel blend of the 'enhanced' mode, :340-342 + :352, with the (target, target) float64 weight map the
-    caller built -- cv2.Canny / scipy.gaussian_filter / the sky detector are host code outside this library), and any other mode
-    name = the reference's default branch (the styled image itself, :399-401).  Crop back to the aspect ratio and LANCZOS resize
-    back as :403-429."""
+def process_local_style(model, img_u8: torch.Tensor, mode="simple", strength=0.8, weight_map=None, target=256, detail=0.7,
+                        detail_coeff=0.3) -> torch.Tensor:
+    """``process_local_style`` of the reference (batch_process_images.py:255-441) without the file I/O, on the GPU end to end:
+    'simple' (strength blend of the letterboxed original with the styled image, :304-312), 'weight_map' (the per-pixel blend of
+    the 'enhanced' mode, :340-342 + :352: with the caller's (target, target) float64 ``weight_map``, or, when it is None, with the
+    map ``enhanced_weight_map`` builds from the letterboxed canvas, ``strength``, ``detail`` and ``detail_coeff`` -- the
+    reference's mode='enhanced', enhance_colors=False, smooth=False), and any other mode name = the reference's default branch
+    (the styled image itself, :399-401).  Crop back to the aspect ratio and LANCZOS resize back as :403-429."""
     canvas, (width, height) = letterbox(img_u8, target)
     x = to_tensor(canvas).unsqueeze(0)
     with torch.no_grad():
@@ -210,6 +255,8 @@ def process_local_style(model, img_u8: torch.Tensor, mode="simple", strength=0.8
     if mode == "simple":
         out = blend_u8(canvas, styled, strength=strength)
     elif mode == "weight_map":
+        if weight_map is None:
+            weight_map = enhanced_weight_map(canvas, strength, detail, detail_coeff)
         out = blend_u8(canvas, styled, weight_map=weight_map)
     else:
         out = styled
@@ -468,7 +515,7 @@ def _req_batch(images):
     return images
 
 
-def _process_chunk(model, images, geoms, target, mode, strength, weight_maps):
+def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, detail, detail_coeff):
     n, T, dev = len(images), target, images[0].device
     blend = mode in ("simple", "weight_map")
     plan = _BatchPlan(dev)
@@ -499,7 +546,10 @@ def _process_chunk(model, images, geoms, target, mode, strength, weight_maps):
                "mstg_img_batch_tensor_to_u8")
     if blend:  # the (n * T, T, 3) view of the batch is one tall image to the blend kernel
         if mode == "weight_map":
-            wm = torch.stack([torch.as_tensor(m) for m in weight_maps]).to(device=dev, dtype=torch.float64).contiguous()
+            if weight_maps is None:  # three launches on the canvas batch the chunk already has
+                wm = enhanced_weight_map(canvas, strength, detail, detail_coeff)
+            else:
+                wm = torch.stack([torch.as_tensor(m) for m in weight_maps]).to(device=dev, dtype=torch.float64).contiguous()
             w0 = w1 = 0.0
         else:
             wm, w1 = None, float(strength)
@@ -511,14 +561,17 @@ def _process_chunk(model, images, geoms, target, mode, strength, weight_maps):
     return [out[o:o + g.out_h * g.out_w * 3].view(g.out_h, g.out_w, 3) for o, g in zip(post.out_offs, geoms)]
 
 
-def _process_batch(model, images, target, batch_size, mode, strength, weight_maps, local_style):
+def _process_batch(model, images, target, batch_size, mode, strength, weight_maps, local_style, detail=0.7, detail_coeff=0.3):
     images = _req_batch(images)
     target, batch_size = int(target), int(batch_size)
     if batch_size < 1:
         raise RuntimeError(f"mstg_hip image: batch_size {batch_size}")
     geoms = letterbox_plan([im.shape[:2] for im in images], target, local_style=local_style)
-    if mode == "weight_map":
-        if weight_maps is None or len(weight_maps) != len(images):
+    if mode == "weight_map" and weight_maps is None and target * target > _lib.LOCAL_STYLE_MAX_PIXELS:
+        raise RuntimeError(f"mstg_hip image: the device weight map takes canvases of at most {_lib.LOCAL_STYLE_MAX_PIXELS} pixels, "
+                           f"not {target}x{target}")
+    if mode == "weight_map" and weight_maps is not None:
+        if len(weight_maps) != len(images):
             raise RuntimeError("mstg_hip blend: mode 'weight_map' needs one weight map per image")
         for i, m in enumerate(weight_maps):
             if tuple(m.shape) != (target, target):
@@ -526,7 +579,8 @@ def _process_batch(model, images, target, batch_size, mode, strength, weight_map
     outs = []
     for s in range(0, len(images), batch_size):
         e = s + batch_size
-        outs += _process_chunk(model, images[s:e], geoms[s:e], target, mode, strength, None if weight_maps is None else weight_maps[s:e])
+        outs += _process_chunk(model, images[s:e], geoms[s:e], target, mode, strength, None if weight_maps is None else weight_maps[s:e],
+                               detail, detail_coeff)
     return outs
 
 
@@ -537,10 +591,13 @@ def process_cyclegan_batch(model, images, target=256, batch_size=64):
     return _process_batch(model, images, target, batch_size, None, None, None, False)
 
 
-def process_local_style_batch(model, images, mode="simple", strength=0.8, weight_maps=None, target=256, batch_size=64):
+def process_local_style_batch(model, images, mode="simple", strength=0.8, weight_maps=None, target=256, batch_size=64, detail=0.7,
+                              detail_coeff=0.3):
     """``process_local_style`` for a sequence of images, same modes: 'simple' (``strength``), 'weight_map' (``weight_maps``: one
-    (target, target) float64 map per image), anything else = the styled image.  Six library launches per chunk at most."""
-    return _process_batch(model, images, target, batch_size, mode, strength, weight_maps, True)
+    (target, target) float64 map per image, or None: the 'enhanced' map is built on the device from the chunk's canvas batch with
+    ``strength``, ``detail`` and ``detail_coeff``, three more launches whatever the chunk size), anything else = the styled
+    image.  Six library launches per chunk at most, nine with the device-built map."""
+    return _process_batch(model, images, target, batch_size, mode, strength, weight_maps, True, detail, detail_coeff)
 
 
 def dataset_batch(images, grid_masks, img_size=256):
