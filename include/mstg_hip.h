@@ -584,7 +584,30 @@ int mstg_image_metrics_u8(const unsigned char* a, const unsigned char* b, int N,
  * All masks are (N, H, W) bytes holding 0 / 1.  Integer arithmetic up to the Gaussian, a fixed summation order, no
  * floating-point atomics: bit-reproducible.  The hysteresis keeps one byte per pixel of an image in LDS: H * W <=
  * MSTG_LOCAL_STYLE_MAX_PIXELS, else MSTG_E_UNSUPPORTED (the message names the size); prepare and weights take any H, W >= 1.
- * Out of scope: enhance_colors (cv2.convertScaleAbs), smooth (smooth_transitions) and the rest of mode 'advanced'.
+ *
+ * The finish of the mode (:342-352), one more launch: the blend with that map and the two optional steps.  Per image: orig, styled
+ * uint8 (H, W, 3), weight float64 (H, W), detail bytes 0 / 1 (H, W), flags enhance_colors and smooth.
+ *   x   = orig * (1 - w) + styled * w in float64 exactly as mstg_blend_u8 forms it: two rounded products, one rounded sum, no
+ *         fused multiply-add.  Without enhance_colors the result is mstg_blend_u8's clip and truncation, byte for byte.
+ *   e   = cv2.convertScaleAbs(x, alpha=1.1, beta=5) (:346) = sat_u8(rint_half_even(|fmaf((float)x, 1.1f, 5.0f)|)) per channel:
+ *         the double narrowed to float32 (round to nearest), ONE fused multiply-add with the float32 constants, absolute value,
+ *         round half to even, saturation to 0..255.  This restates OpenCV 4.x's cvtabs for CV_64F -> CV_8U on a build with FMA
+ *         lanes (not compared with an OpenCV binary); plain float64 or unfused float32 evaluation differs on a fraction of a
+ *         percent of the bytes, never by more than one grey level (tests/test_local_style_finish_cpu.py measures it).
+ *   smooth_transitions(e, detail, radius=3) (:152-174, :350), only together with enhance_colors, so e is uint8:
+ *         dil = max, ero = min of detail over the 9 x 9 window clipped to the image (cv2.dilate / cv2.erode with a 5 x 5 box,
+ *         two iterations, default border: neutral); boundary = dil != ero;
+ *         blur = cv2.GaussianBlur(e, (7, 7), 0), OpenCV's bit-exact 8-bit path: integer taps {8, 28, 56, 72, 56, 28, 8} (the
+ *         sigma <= 0 table of size 7 in 8.8 fixed point, sum 256) along x, then along y; BORDER_REFLECT_101 (index p outside
+ *         [0, len) mirrored without repeating the edge pixel, repeatedly if need be; len == 1 gives 0); the horizontal sums stay
+ *         exact in 16 bits (<= 65280); blur = (sum + 32768) >> 16;
+ *         out = boundary ? (e + blur) >> 1 : e for all three channels (the reference assigns the float64 0.5 * a + 0.5 * b into a
+ *         uint8 array, which truncates; its final clip + cast changes nothing).
+ * mstg_local_style_finish takes any H, W >= 1; out must not overlap an input (MSTG_E_BADARG).  Still not built:
+ *   - smooth without enhance_colors: there cv2.GaussianBlur runs on the float64 blend and is truncated right at integers that flat
+ *     regions hit exactly (the sky weight 1.0), so OpenCV's float64 summation order decides bytes: MSTG_E_UNSUPPORTED, by name;
+ *   - mode 'advanced' (the reference itself raises there: cv2.cvtColor on a float64 array, :391);
+ *   - a comparison of any of these restatements with an OpenCV binary.
  * ---------------------------------------------------------------------------------------------- */
 #define MSTG_LOCAL_STYLE_MAX_PIXELS 147456 /* 144 KiB of the 160 KiB of LDS of a CU: 256 x 256, up to 384 x 384 */
 /* bytes mstg_local_style_weight_map needs for (N, H, W); 0 for an invalid or unsupported shape (mstg_last_error says which) */
@@ -601,6 +624,17 @@ int mstg_local_style_weights(const unsigned char* edge, const unsigned char* sky
 /* the three stages on the caller's workspace (16-byte aligned, mstg_local_style_workspace_bytes) */
 int mstg_local_style_weight_map(const unsigned char* canvas, int N, int H, int W, double w_base, double w_sky, double w_detail,
                                 double* weight_map, void* workspace, size_t workspace_bytes, void* stream);
+/* stage D: blend + enhance_colors + smooth as defined above; detail may be NULL when smooth == 0 */
+int mstg_local_style_finish(const unsigned char* canvas, const unsigned char* styled, const double* weight_map,
+                            const unsigned char* detail /*nullable iff !smooth*/, int N, int H, int W, int enhance_colors, int smooth,
+                            unsigned char* out, void* stream);
+/* bytes mstg_local_style_enhanced needs for (N, H, W); 0 for an invalid or unsupported shape (mstg_last_error says which) */
+size_t mstg_local_style_enhanced_workspace_bytes(int N, int H, int W);
+/* process_local_style(mode='enhanced') from the canvas: stages A-C and the finish on the caller's workspace (16-byte aligned; it
+ * holds the map and the detail mask), four launches whatever N; same MSTG_LOCAL_STYLE_MAX_PIXELS limit as the weight map */
+int mstg_local_style_enhanced(const unsigned char* canvas, const unsigned char* styled, int N, int H, int W, double w_base, double w_sky,
+                              double w_detail, int enhance_colors, int smooth, unsigned char* out, void* workspace,
+                              size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain

@@ -190,6 +190,9 @@ SIGNATURES = {
     "mstg_local_style_hysteresis": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mstg_local_style_weights": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
     "mstg_local_style_weight_map": (_i, [_vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "mstg_local_style_finish": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mstg_local_style_enhanced_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_local_style_enhanced": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 LOCAL_STYLE_MAX_PIXELS = 147456  # MSTG_LOCAL_STYLE_MAX_PIXELS

@@ -26,6 +26,17 @@
 //    outermost inwards, no fused multiply-add); detail = g > 0.1; has_sky is formed from the image's count on the device.
 //
 // Everything before the Gaussian is integer, nothing uses floating-point atomics, so the three outputs are bit-reproducible.
+//
+// D  local_style_finish_kernel   the blend with that map and the two finishing steps of the mode (:342-352), one workgroup of 256
+//    threads per 32 x 64 tile: x = orig * (1 - w) + styled * w as blend_u8_kernel forms it (float64, every product and the sum
+//    rounded); enhance_colors = cv2.convertScaleAbs(x, alpha=1.1, beta=5) restated as narrow to float32, ONE fused multiply-add,
+//    |.|, round half to even, saturate; smooth = smooth_transitions(radius=3): boundary = dilate != erode of the detail mask over
+//    the 9 x 9 window clipped to the image (two iterations of a 5 x 5 box), the 8-bit GaussianBlur 7 x 7 (sigma 0) in OpenCV's
+//    8.8 fixed point with BORDER_REFLECT_101, and (e + blur) >> 1 on the boundary.  The smoothing variant keeps the enhanced
+//    patch with 3 pixels of halo (recomputed from the mirrored source pixels), the detail patch with 4 (outside the image a pixel
+//    is neutral) and the 16-bit horizontally filtered rows in LDS; without smooth the kernel is the per-pixel blend and uses no
+//    LDS.  Integer after the colour step, no atomics: bit-reproducible.  Restated from the definitions (include/mstg_hip.h),
+//    not compared with an OpenCV binary.
 #include "common.h"
 
 namespace mstg {
@@ -287,6 +298,152 @@ __global__ __launch_bounds__(LC_THREADS) void local_style_weights_kernel(const u
     }
 }
 
+constexpr int LD_TH = LA_TH, LD_TW = LA_TW, LD_THREADS = 256;
+constexpr int LD_RB = 3, LD_RM = 4;                              // blur radius (7 taps), morphology radius (9 x 9)
+constexpr int LD_EH = LD_TH + 2 * LD_RB, LD_EW = LD_TW + 2 * LD_RB;  // enhanced patch
+constexpr int LD_EWP = LD_TW + 8;  // its row pitch in LDS: the item of the last four columns reads three whole dwords
+constexpr int LD_DH = LD_TH + 2 * LD_RM, LD_DW = LD_TW + 2 * LD_RM;  // detail patch
+static_assert(LD_EWP >= LD_EW && LD_EWP % 4 == 0 && LD_DW == LD_TW + 8 && LD_TW % 4 == 0, "dword passes of the finish kernel");
+// OpenCV's table for getGaussianKernel(7, sigma <= 0), {0.03125, 0.109375, 0.21875, 0.28125, ...}, in 8.8 fixed point; sum 256
+__device__ __forceinline__ int ld_tap(int k) {
+    constexpr int t[7] = {8, 28, 56, 72, 56, 28, 8};
+    return t[k];
+}
+
+// cv2.BORDER_REFLECT_101 (d c b | a b c d | c b a), for any distance from the array; n == 1 gives 0
+__device__ __forceinline__ int reflect101_index(int i, int n) {
+    if (n == 1) return 0;
+    const int p = 2 * n - 2;
+    i %= p;
+    if (i < 0) i += p;
+    return i < n ? i : p - i;
+}
+
+// One channel of one pixel: the blend in float64 as blend_u8_kernel forms it, then either its clip and truncation or the
+// convertScaleAbs restatement.
+template <bool ENHANCE>
+__device__ __forceinline__ unsigned char finish_channel(unsigned char o, unsigned char s, double w0, double w1) {
+#pragma clang fp contract(off)  // numpy rounds each product and the sum
+    const double a = (double)o * w0;
+    const double b = (double)s * w1;
+    double r = a + b;
+    if (!ENHANCE) {
+        r = r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r);
+        if (!(r == r)) r = 0.0;  // a NaN weight: keep the byte defined, as blend_u8_kernel does
+        return (unsigned char)r;
+    }
+    float t = fabsf(__builtin_fmaf((float)r, 1.1f, 5.0f));  // the one fused multiply-add of the definition
+    if (!(t == t)) t = 0.f;                                 // a NaN weight: keep the byte defined here too
+    t = fminf(__builtin_rintf(t), 255.f);                   // round half to even, saturate (t >= 0)
+    return (unsigned char)t;
+}
+
+template <bool ENHANCE, bool SMOOTH>
+__global__ __launch_bounds__(LD_THREADS) void local_style_finish_kernel(const unsigned char* __restrict__ canvas,
+                                                                        const unsigned char* __restrict__ styled,
+                                                                        const double* __restrict__ wmap,
+                                                                        const unsigned char* __restrict__ detail, int H, int W, int tiles_x,
+                                                                        int tiles, unsigned char* __restrict__ out) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int y0 = ty * LD_TH, x0 = tx * LD_TW;
+    const size_t plane = (size_t)n * H * W;
+    const unsigned char* c_img = canvas + plane * 3;
+    const unsigned char* s_img = styled + plane * 3;
+    const double* w_img = wmap + plane;
+    unsigned char* o_img = out + plane * 3;
+    if (!SMOOTH) {
+        for (int e = tid; e < LD_TH * LD_TW; e += LD_THREADS) {
+            const int r = e / LD_TW, c = e - r * LD_TW;
+            const int py = y0 + r, px = x0 + c;
+            if (py >= H || px >= W) continue;
+            const size_t i = (size_t)py * W + px;
+            const double w1 = w_img[i], w0 = 1.0 - w1;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) o_img[i * 3 + ch] = finish_channel<ENHANCE>(c_img[i * 3 + ch], s_img[i * 3 + ch], w0, w1);
+        }
+        return;
+    }
+    // LDS: planes per channel, rows padded to whole dwords, so the two horizontal passes read dwords and make four outputs each
+    __shared__ __align__(16) unsigned char en[3 * LD_EH * LD_EWP];    // the enhanced image, halo 3
+    __shared__ __align__(16) unsigned char dm[LD_DH * LD_DW];         // detail: 1 = set, 2 = clear, 0 = outside the image (neutral)
+    __shared__ __align__(16) unsigned char dh[LD_DH * LD_TW];         // OR of dm over the 9 columns of the window
+    __shared__ __align__(16) unsigned short hz[3 * LD_EH * LD_TW];    // the horizontally filtered rows, exact (<= 65280)
+    const unsigned char* d_img = detail + plane;
+    for (int e = tid; e < LD_EH * LD_EW; e += LD_THREADS) {
+        const int r = e / LD_EW, c = e - r * LD_EW;
+        int sy = y0 - LD_RB + r, sx = x0 - LD_RB + c;
+        if ((unsigned)sy >= (unsigned)H) sy = reflect101_index(sy, H);
+        if ((unsigned)sx >= (unsigned)W) sx = reflect101_index(sx, W);
+        const size_t i = (size_t)sy * W + sx;
+        const double w1 = w_img[i], w0 = 1.0 - w1;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            en[(ch * LD_EH + r) * LD_EWP + c] = finish_channel<true>(c_img[i * 3 + ch], s_img[i * 3 + ch], w0, w1);
+    }
+    for (int e = tid; e < LD_DH * LD_DW; e += LD_THREADS) {
+        const int r = e / LD_DW, c = e - r * LD_DW;
+        const int py = y0 - LD_RM + r, px = x0 - LD_RM + c;
+        unsigned char v = 0;
+        if ((unsigned)py < (unsigned)H && (unsigned)px < (unsigned)W) v = d_img[(size_t)py * W + px] != 0 ? 1 : 2;
+        dm[e] = v;
+    }
+    __syncthreads();
+    for (int e = tid; e < LD_DH * (LD_TW / 4); e += LD_THREADS) {  // four columns per item: bytes c .. c + 11 of the row
+        const int r = e / (LD_TW / 4), c = 4 * (e - r * (LD_TW / 4));
+        const unsigned* p = reinterpret_cast<const unsigned*>(&dm[r * LD_DW + c]);
+        const unsigned a = p[0], b = p[1], d = p[2];
+        const unsigned mid = (a >> 24) | b | (b >> 8) | (b >> 16) | (b >> 24) | d;  // bytes 3 .. 8 (in the low byte)
+        const unsigned o0 = a | (a >> 8) | (a >> 16) | mid;                          // 0 .. 8
+        const unsigned o1 = (a >> 8) | (a >> 16) | mid | (d >> 8);                   // 1 .. 9
+        const unsigned o2 = (a >> 16) | mid | (d >> 8) | (d >> 16);                  // 2 .. 10
+        const unsigned o3 = mid | (d >> 8) | (d >> 16) | (d >> 24);                  // 3 .. 11
+        *reinterpret_cast<unsigned*>(&dh[r * LD_TW + c]) = (o0 & 3u) | (o1 & 3u) << 8 | (o2 & 3u) << 16 | (o3 & 3u) << 24;
+    }
+    for (int e = tid; e < 3 * LD_EH * (LD_TW / 4); e += LD_THREADS) {  // four columns per item: bytes c .. c + 9 of the plane row
+        const int row = e / (LD_TW / 4), c = 4 * (e - row * (LD_TW / 4));  // row = channel * LD_EH + patch row
+        const unsigned* p = reinterpret_cast<const unsigned*>(&en[row * LD_EWP + c]);
+        const unsigned w[3] = {p[0], p[1], p[2]};
+        int px[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) px[k] = (int)((w[k >> 2] >> (8 * (k & 3))) & 0xffu);
+        unsigned short o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int sum = 0;
+#pragma unroll
+            for (int k = 0; k < 7; ++k) sum += ld_tap(k) * px[j + k];
+            o[j] = (unsigned short)sum;
+        }
+        *reinterpret_cast<uint2*>(&hz[row * LD_TW + c]) = make_uint2((unsigned)o[0] | (unsigned)o[1] << 16, (unsigned)o[2] | (unsigned)o[3] << 16);
+    }
+    __syncthreads();
+    for (int e = tid; e < LD_TH * LD_TW; e += LD_THREADS) {
+        const int r = e / LD_TW, c = e - r * LD_TW;
+        const int py = y0 + r, px = x0 + c;
+        if (py >= H || px >= W) continue;
+        unsigned v = 0;
+#pragma unroll
+        for (int k = 0; k <= 2 * LD_RM; ++k) v |= dh[(r + k) * LD_TW + c];
+        const bool boundary = v == 3u;  // the window holds a set and a clear pixel: dilate != erode
+        const size_t i = ((size_t)py * W + px) * 3;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            int o = en[(ch * LD_EH + r + LD_RB) * LD_EWP + c + LD_RB];
+            if (boundary) {
+                const unsigned short* hp = &hz[(ch * LD_EH + r) * LD_TW + c];
+                int sum = 0;
+#pragma unroll
+                for (int k = 0; k < 7; ++k) sum += ld_tap(k) * (int)hp[k * LD_TW];
+                o = (o + ((sum + 32768) >> 16)) >> 1;
+            }
+            o_img[i + ch] = (unsigned char)o;
+        }
+    }
+}
+
 // 0 = fine, else the error code (message set)
 static int ls_shape(const char* who, int N, int H, int W) {
     char msg[200];
@@ -352,6 +509,38 @@ static int ls_weights(const unsigned char* edge, const unsigned char* sky, const
     return MSTG_OK;
 }
 
+static int ls_finish(const unsigned char* canvas, const unsigned char* styled, const double* weight_map, const unsigned char* detail, int N,
+                     int H, int W, int enhance, int smooth, unsigned char* out, hipStream_t st) {
+    const int tx = cdiv(W, LD_TW), tiles = tx * cdiv(H, LD_TH);
+    const dim3 grid((unsigned)(N * tiles)), block(LD_THREADS);
+    if (smooth)
+        MSTG_LAUNCH((local_style_finish_kernel<true, true>), grid, block, 0, st, canvas, styled, weight_map, detail, H, W, tx, tiles, out);
+    else if (enhance)
+        MSTG_LAUNCH((local_style_finish_kernel<true, false>), grid, block, 0, st, canvas, styled, weight_map, detail, H, W, tx, tiles, out);
+    else
+        MSTG_LAUNCH((local_style_finish_kernel<false, false>), grid, block, 0, st, canvas, styled, weight_map, detail, H, W, tx, tiles, out);
+    MSTG_CHECK_LAUNCH("local_style_finish_kernel");
+    return MSTG_OK;
+}
+
+// smooth without enhance_colors is refused by name; 0 = fine
+static int ls_flags(const char* who, int enhance, int smooth) {
+    if (smooth && !enhance) {
+        char msg[256];
+        snprintf(msg, sizeof(msg),
+                 "%s: smooth without enhance_colors is not built: there cv2.GaussianBlur runs on the float64 blend and OpenCV's "
+                 "summation order decides bytes",
+                 who);
+        return fail_arg(MSTG_E_UNSUPPORTED, msg);
+    }
+    return MSTG_OK;
+}
+
+static bool ls_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
 }  // namespace mstg
 
 using namespace mstg;
@@ -408,5 +597,57 @@ extern "C" int mstg_local_style_weight_map(const unsigned char* canvas, int N, i
     rc = ls_prepare(canvas, N, H, W, state, sky, count, nullptr, st);
     if (rc == MSTG_OK) rc = ls_hysteresis(state, N, H, W, edge, st);
     if (rc == MSTG_OK) rc = ls_weights(edge, sky, count, N, H, W, w_base, w_sky, w_detail, weight_map, nullptr, st);
+    return rc;
+}
+
+extern "C" int mstg_local_style_finish(const unsigned char* canvas, const unsigned char* styled, const double* weight_map,
+                                       const unsigned char* detail, int N, int H, int W, int enhance_colors, int smooth, unsigned char* out,
+                                       void* stream) {
+    if (!canvas || !styled || !weight_map || !out) return fail_arg(MSTG_E_BADARG, "local_style_finish: null canvas, styled, map or out pointer");
+    int rc = ls_shape("local_style_finish", N, H, W);
+    if (rc == MSTG_OK) rc = ls_flags("local_style_finish", enhance_colors, smooth);
+    if (rc != MSTG_OK) return rc;
+    if (smooth && !detail) return fail_arg(MSTG_E_BADARG, "local_style_finish: smooth needs the detail mask");
+    if ((uintptr_t)weight_map & 7) return fail_arg(MSTG_E_ALIGN, "local_style_finish: weight_map not 8-byte aligned");
+    const size_t px = (size_t)N * H * W;
+    if (ls_overlap(out, px * 3, canvas, px * 3) || ls_overlap(out, px * 3, styled, px * 3) || ls_overlap(out, px * 3, weight_map, px * 8) ||
+        (smooth && ls_overlap(out, px * 3, detail, px)))
+        return fail_arg(MSTG_E_BADARG, "local_style_finish: out overlaps an input (the smoothing reads neighbours of every pixel)");
+    return ls_finish(canvas, styled, weight_map, detail, N, H, W, enhance_colors, smooth, out, (hipStream_t)stream);
+}
+
+extern "C" size_t mstg_local_style_enhanced_workspace_bytes(int N, int H, int W) {
+    if (ls_shape("local_style_enhanced_workspace_bytes", N, H, W) != MSTG_OK ||
+        ls_fits_lds("local_style_enhanced_workspace_bytes", H, W) != MSTG_OK)
+        return 0;
+    const size_t px = (size_t)N * H * W;
+    return ls_align(px * sizeof(double)) + 4 * ls_align(px) + ls_align((size_t)N * sizeof(int));
+}
+
+extern "C" int mstg_local_style_enhanced(const unsigned char* canvas, const unsigned char* styled, int N, int H, int W, double w_base,
+                                         double w_sky, double w_detail, int enhance_colors, int smooth, unsigned char* out, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    if (!canvas || !styled || !out) return fail_arg(MSTG_E_BADARG, "local_style_enhanced: null canvas, styled or out pointer");
+    int rc = ls_shape("local_style_enhanced", N, H, W);
+    if (rc == MSTG_OK) rc = ls_fits_lds("local_style_enhanced", H, W);
+    if (rc == MSTG_OK) rc = ls_flags("local_style_enhanced", enhance_colors, smooth);
+    if (rc != MSTG_OK) return rc;
+    const size_t px = (size_t)N * H * W, plane = ls_align(px), mapb = ls_align(px * sizeof(double));
+    const size_t need = mapb + 4 * plane + ls_align((size_t)N * sizeof(int));
+    if (!workspace || workspace_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "local_style_enhanced: workspace too small");
+    if ((uintptr_t)workspace & 15) return fail_arg(MSTG_E_ALIGN, "local_style_enhanced: workspace not 16-byte aligned");
+    if (ls_overlap(out, px * 3, canvas, px * 3) || ls_overlap(out, px * 3, styled, px * 3) || ls_overlap(out, px * 3, workspace, need))
+        return fail_arg(MSTG_E_BADARG, "local_style_enhanced: out overlaps an input or the workspace");
+    double* wm = (double*)workspace;
+    unsigned char* state = (unsigned char*)workspace + mapb;
+    unsigned char* sky = state + plane;
+    unsigned char* edge = sky + plane;
+    unsigned char* det = edge + plane;
+    int* count = (int*)(det + plane);
+    hipStream_t st = (hipStream_t)stream;
+    rc = ls_prepare(canvas, N, H, W, state, sky, count, nullptr, st);
+    if (rc == MSTG_OK) rc = ls_hysteresis(state, N, H, W, edge, st);
+    if (rc == MSTG_OK) rc = ls_weights(edge, sky, count, N, H, W, w_base, w_sky, w_detail, wm, det, st);
+    if (rc == MSTG_OK) rc = ls_finish(canvas, styled, wm, det, N, H, W, enhance_colors, smooth, out, st);
     return rc;
 }

@@ -161,7 +161,8 @@ def enhanced_weight_map(canvas_u8: torch.Tensor, strength=0.8, detail=0.7, detai
     ``scipy.ndimage.gaussian_filter(edges, sigma=2) > 0.1`` and the three weight levels; H * W <= 147456 per image.  OpenCV's
     integer steps are restated from their definitions (include/mstg_hip.h), not compared with an OpenCV binary.  Returns the
     (H, W) / (N, H, W) map; with ``return_masks`` also the sky, edge and detail masks (bool) and the ``has_sky`` flag(s), all on
-    the device.  ``enhance_colors``, ``smooth`` and the rest of mode 'advanced' are not built."""
+    the device.  ``local_style_finish`` applies the map with the mode's ``enhance_colors`` and ``smooth`` steps; not built:
+    ``smooth`` without ``enhance_colors``, mode 'advanced', and a comparison with an OpenCV binary."""
     single = canvas_u8.dim() == 3
     c = canvas_u8.unsqueeze(0) if single else canvas_u8
     if not c.is_cuda or c.dtype != torch.uint8 or c.dim() != 4 or c.shape[3] != 3 or c.shape[0] < 1:
@@ -189,6 +190,57 @@ def enhanced_weight_map(canvas_u8: torch.Tensor, strength=0.8, detail=0.7, detai
     has_sky = count.long() * 10 > 7 * H * W
     out = (wm, sky.view(torch.bool), edge.view(torch.bool), det.view(torch.bool), has_sky)
     return tuple(t[0] for t in out) if single else out
+
+
+def _req_canvases(t, what):
+    if not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or t.shape[0] < 1:
+        raise RuntimeError(f"mstg_hip image: expected a uint8 (H, W, 3) or (N, H, W, 3) {what} on the GPU")
+    return t.contiguous()
+
+
+def local_style_finish(canvas_u8, styled_u8, weight_map, detail_mask, enhance_colors=True, smooth=True) -> torch.Tensor:
+    """The end of ``process_local_style(mode='enhanced')`` (batch_process_images.py:342-352) for an (H, W, 3) or (N, H, W, 3)
+    uint8 canvas and styled image, the float64 ``weight_map`` and the ``detail_mask`` (bool or 0 / 1 bytes; may be None without
+    ``smooth``) of ``enhanced_weight_map``, in one launch whatever N: the float64 blend of ``blend_u8``, ``enhance_colors`` =
+    ``cv2.convertScaleAbs(alpha=1.1, beta=5)`` and ``smooth`` = ``smooth_transitions(radius=3)``, restated from their
+    definitions (include/mstg_hip.h; not compared with an OpenCV binary).  Both flags off equals ``blend_u8`` byte for byte;
+    ``smooth`` without ``enhance_colors`` is not built and raises."""
+    single = canvas_u8.dim() == 3
+    c = _req_canvases(canvas_u8.unsqueeze(0) if single else canvas_u8, "canvas")
+    st = _req_canvases(styled_u8.unsqueeze(0) if single else styled_u8, "styled image")
+    if c.shape != st.shape:
+        raise RuntimeError(f"mstg_hip local style: shapes differ {tuple(c.shape)} vs {tuple(st.shape)}")
+    N, H, W = c.shape[:3]
+    wm = torch.as_tensor(weight_map).to(device=c.device, dtype=torch.float64)
+    if single:
+        wm = wm.unsqueeze(0)
+    if tuple(wm.shape) != (N, H, W):
+        raise RuntimeError(f"mstg_hip local style: weight map {tuple(wm.shape)} does not match the canvases {(N, H, W)}")
+    wm = wm.contiguous()
+    det = None
+    if detail_mask is not None:
+        det = torch.as_tensor(detail_mask).to(device=c.device)
+        if det.numel() != N * H * W:
+            raise RuntimeError(f"mstg_hip local style: detail mask {tuple(det.shape)} does not match the canvases {(N, H, W)}")
+        det = (det if det.dtype == torch.uint8 else det.to(torch.uint8)).contiguous()
+    out = torch.empty_like(c)
+    _lib.check(_lib.load().mstg_local_style_finish(_p(c), _p(st), _p(wm), _p(det), N, H, W, int(bool(enhance_colors)), int(bool(smooth)),
+                                                   _p(out), _stream()), "mstg_local_style_finish")
+    return out[0] if single else out
+
+
+def _local_style_enhanced(canvas, styled, strength, detail, detail_coeff, enhance_colors, smooth, out=None):
+    """mode 'enhanced' for (N, H, W, 3) canvases that are already checked: four launches on one workspace"""
+    N, H, W = canvas.shape[:3]
+    w_base, w_sky, w_detail = local_style_weights(strength, detail, detail_coeff)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(canvas)
+    need = lib.mstg_local_style_enhanced_workspace_bytes(N, H, W)  # 0: the call below names what is wrong with the shape
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=canvas.device)
+    _lib.check(lib.mstg_local_style_enhanced(_p(canvas), _p(styled), N, H, W, w_base, w_sky, w_detail, int(bool(enhance_colors)),
+                                             int(bool(smooth)), _p(out), _p(ws), need, _stream()), "mstg_local_style_enhanced")
+    return out
 
 
 # ---- the callers, restated on the device ----------------------------------------------------------------------------------
@@ -240,13 +292,16 @@ def process_cyclegan(model, img_u8: torch.Tensor, target=256) -> torch.Tensor:
 
 
 def process_local_style(model, img_u8: torch.Tensor, mode="simple", strength=0.8, weight_map=None, target=256, detail=0.7,
-                        detail_coeff=0.3) -> torch.Tensor:
+                        detail_coeff=0.3, enhance_colors=True, smooth=True) -> torch.Tensor:
     """``process_local_style`` of the reference (batch_process_images.py:255-441) without the file I/O, on the GPU end to end:
     'simple' (strength blend of the letterboxed original with the styled image, :304-312), 'weight_map' (the per-pixel blend of
     the 'enhanced' mode, :340-342 + :352: with the caller's (target, target) float64 ``weight_map``, or, when it is None, with the
     map ``enhanced_weight_map`` builds from the letterboxed canvas, ``strength``, ``detail`` and ``detail_coeff`` -- the
-    reference's mode='enhanced', enhance_colors=False, smooth=False), and any other mode name = the reference's default branch
-    (the styled image itself, :399-401).  Crop back to the aspect ratio and LANCZOS resize back as :403-429."""
+    reference's mode='enhanced', enhance_colors=False, smooth=False), 'enhanced' (the reference's default mode, :312-353, with
+    its keywords ``enhance_colors`` and ``smooth``, both on by default as there: the device map, then ``local_style_finish`` in
+    place of the blend, so as many launches as 'weight_map' without a map; ``smooth`` without ``enhance_colors`` is not built and
+    raises; the two keywords matter in this mode only), and any other mode name, 'advanced' included = the reference's default
+    branch (the styled image itself, :399-401).  Crop back to the aspect ratio and LANCZOS resize back as :403-429."""
     canvas, (width, height) = letterbox(img_u8, target)
     x = to_tensor(canvas).unsqueeze(0)
     with torch.no_grad():
@@ -258,6 +313,8 @@ def process_local_style(model, img_u8: torch.Tensor, mode="simple", strength=0.8
         if weight_map is None:
             weight_map = enhanced_weight_map(canvas, strength, detail, detail_coeff)
         out = blend_u8(canvas, styled, weight_map=weight_map)
+    elif mode == "enhanced":
+        out = _local_style_enhanced(canvas.unsqueeze(0), styled.unsqueeze(0), strength, detail, detail_coeff, enhance_colors, smooth)[0]
     else:
         out = styled
     aspect = width / height
@@ -515,9 +572,9 @@ def _req_batch(images):
     return images
 
 
-def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, detail, detail_coeff):
+def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, detail, detail_coeff, enhance_colors, smooth):
     n, T, dev = len(images), target, images[0].device
-    blend = mode in ("simple", "weight_map")
+    blend = mode in ("simple", "weight_map", "enhanced")
     plan = _BatchPlan(dev)
     pre, post = plan.direction(canvas=T), plan.direction()
     x = torch.empty((n, 3, T, T), dtype=torch.float32, device=dev)
@@ -544,7 +601,9 @@ def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, de
     lib = _lib.load()
     _lib.check(lib.mstg_img_batch_tensor_to_u8(_p(y), int(y.dtype == torch.float16), n, T, T, _p(styled), _stream()),
                "mstg_img_batch_tensor_to_u8")
-    if blend:  # the (n * T, T, 3) view of the batch is one tall image to the blend kernel
+    if mode == "enhanced":  # stages A-C and the finish on the canvas batch the chunk already has: four launches
+        _local_style_enhanced(canvas, styled, strength, detail, detail_coeff, enhance_colors, smooth, out=final)
+    elif blend:  # the (n * T, T, 3) view of the batch is one tall image to the blend kernel
         if mode == "weight_map":
             if weight_maps is None:  # three launches on the canvas batch the chunk already has
                 wm = enhanced_weight_map(canvas, strength, detail, detail_coeff)
@@ -561,13 +620,15 @@ def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, de
     return [out[o:o + g.out_h * g.out_w * 3].view(g.out_h, g.out_w, 3) for o, g in zip(post.out_offs, geoms)]
 
 
-def _process_batch(model, images, target, batch_size, mode, strength, weight_maps, local_style, detail=0.7, detail_coeff=0.3):
+def _process_batch(model, images, target, batch_size, mode, strength, weight_maps, local_style, detail=0.7, detail_coeff=0.3,
+                   enhance_colors=True, smooth=True):
     images = _req_batch(images)
     target, batch_size = int(target), int(batch_size)
     if batch_size < 1:
         raise RuntimeError(f"mstg_hip image: batch_size {batch_size}")
     geoms = letterbox_plan([im.shape[:2] for im in images], target, local_style=local_style)
-    if mode == "weight_map" and weight_maps is None and target * target > _lib.LOCAL_STYLE_MAX_PIXELS:
+    device_map = mode == "enhanced" or (mode == "weight_map" and weight_maps is None)
+    if device_map and target * target > _lib.LOCAL_STYLE_MAX_PIXELS:
         raise RuntimeError(f"mstg_hip image: the device weight map takes canvases of at most {_lib.LOCAL_STYLE_MAX_PIXELS} pixels, "
                            f"not {target}x{target}")
     if mode == "weight_map" and weight_maps is not None:
@@ -580,7 +641,7 @@ def _process_batch(model, images, target, batch_size, mode, strength, weight_map
     for s in range(0, len(images), batch_size):
         e = s + batch_size
         outs += _process_chunk(model, images[s:e], geoms[s:e], target, mode, strength, None if weight_maps is None else weight_maps[s:e],
-                               detail, detail_coeff)
+                               detail, detail_coeff, enhance_colors, smooth)
     return outs
 
 
@@ -592,12 +653,14 @@ def process_cyclegan_batch(model, images, target=256, batch_size=64):
 
 
 def process_local_style_batch(model, images, mode="simple", strength=0.8, weight_maps=None, target=256, batch_size=64, detail=0.7,
-                              detail_coeff=0.3):
+                              detail_coeff=0.3, enhance_colors=True, smooth=True):
     """``process_local_style`` for a sequence of images, same modes: 'simple' (``strength``), 'weight_map' (``weight_maps``: one
     (target, target) float64 map per image, or None: the 'enhanced' map is built on the device from the chunk's canvas batch with
-    ``strength``, ``detail`` and ``detail_coeff``, three more launches whatever the chunk size), anything else = the styled
-    image.  Six library launches per chunk at most, nine with the device-built map."""
-    return _process_batch(model, images, target, batch_size, mode, strength, weight_maps, True, detail, detail_coeff)
+    ``strength``, ``detail`` and ``detail_coeff``, three more launches whatever the chunk size), 'enhanced' (the reference's
+    default mode with its ``enhance_colors`` and ``smooth`` keywords: the device map and the finish launch in place of the
+    blend), anything else = the styled image.  Six library launches per chunk at most, nine with the device-built map."""
+    return _process_batch(model, images, target, batch_size, mode, strength, weight_maps, True, detail, detail_coeff, enhance_colors,
+                          smooth)
 
 
 def dataset_batch(images, grid_masks, img_size=256):

@@ -10,6 +10,10 @@ Three ways through the same chunk, each ending in the same blended (N, 256, 256,
               host -> device copy of the float64 maps, the blend -- what a caller of mode="weight_map" had to do before;
   floor       the blend with maps computed beforehand: ``floor_upload`` stacks and uploads host maps as the batched pipeline does
               for caller-supplied maps, ``floor_resident`` has them on the device already.
+A further row is the reference's default mode, ``mode="enhanced"`` with enhance_colors and smooth: ``enhanced`` is the four
+launches from the canvas batch to the finished bytes (mstg_local_style_enhanced), ``finish`` the fourth launch alone on a resident
+map and detail mask (``finish_no_smooth``: the same without the smoothing, which then pays for no halo), checked against
+tests/local_style_finish_ref.py on the first four canvases.
 Device timings are device events around windows long enough to fill ``--seconds``, after a warm-up, with a synchronise at both
 ends; the host path is wall time around a call that ends in a synchronise.  Each figure is reported as min / median / max over
 its repeats.  Stage B (the hysteresis, one workgroup per image) is also timed alone through the library's per-launch profiler for
@@ -133,6 +137,22 @@ def main():
     def map_only():
         return dimg.enhanced_weight_map(canvas)
 
+    import local_style_finish_ref as FR
+    wm_dev, _, _, det_dev, _ = dimg.enhanced_weight_map(canvas, return_masks=True)
+
+    def enhanced():
+        return dimg._local_style_enhanced(canvas, styled, 0.8, 0.7, 0.3, True, True)
+
+    def finish():
+        return dimg.local_style_finish(canvas, styled, wm_dev, det_dev)
+
+    def finish_no_smooth():
+        return dimg.local_style_finish(canvas, styled, wm_dev, None, smooth=False)
+
+    enh = enhanced()
+    same_enh = bool(torch.equal(enh, finish())) and all(
+        np.array_equal(enh[i].cpu().numpy(), FR.enhanced_ref(canv_np[i], styled_np[i])[0]) for i in range(min(N, 4)))
+
     out_dev = device_path()
     same_map = bool(torch.equal(dimg.enhanced_weight_map(canvas), maps_dev))
     same_bytes = bool(torch.equal(out_dev, host_path()) and torch.equal(out_dev, floor_resident()))
@@ -142,15 +162,21 @@ def main():
               "floor_resident": device_stats(floor_resident, args.seconds, args.repeats),
               "floor_upload": wall_stats(floor_upload, args.repeats),
               "host": wall_stats(host_path, args.host_repeats)}
+    result["enhanced_equals_host_restatement"] = same_enh
+    result["enhanced"] = device_stats(enhanced, args.seconds, args.repeats)
+    result["finish"] = device_stats(finish, args.seconds, args.repeats)
+    result["finish_no_smooth"] = device_stats(finish_no_smooth, args.seconds, args.repeats)
     result["host_over_device"] = result["host"]["median_ms"] / result["device"]["median_ms"]
     natural = torch.from_numpy(np.stack([LR.state_map(LR.gray_u8(canv_np[0]))] * N)).to(DEV)
     spiral = torch.from_numpy(np.stack([LR.spiral_state(T, T)] * N)).to(DEV)
     result["stage_b_natural"] = stage_b_stats(lib, natural, args.repeats)
     result["stage_b_spiral"] = stage_b_stats(lib, spiral, args.repeats)
-    for k in ("device", "device_map_only", "floor_resident", "floor_upload", "host", "stage_b_natural", "stage_b_spiral"):
+    for k in ("device", "device_map_only", "floor_resident", "floor_upload", "host", "enhanced", "finish", "finish_no_smooth", "stage_b_natural",
+              "stage_b_spiral"):
         r = result[k]
         print(f"{k:16s} {r['median_ms']:10.3f} ms  [{r['min_ms']:.3f} .. {r['max_ms']:.3f}]", file=sys.stderr)
-    print(f"host / device = {result['host_over_device']:.0f}x   map equal: {same_map}   bytes equal: {same_bytes}", file=sys.stderr)
+    print(f"host / device = {result['host_over_device']:.0f}x   map equal: {same_map}   bytes equal: {same_bytes}   enhanced equal: {same_enh}",
+          file=sys.stderr)
     line = json.dumps(result)
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
