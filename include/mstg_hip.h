@@ -637,6 +637,74 @@ int mstg_local_style_enhanced(const unsigned char* canvas, const unsigned char* 
                               size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The finish of the STANDARD mode of the reference's application (gan_login_gui.py:817-868, standard_process_thread; every option
+ * of that tab is on by default, :542, :554, :594, :612, :616), on the device for N images (N, H, W, 3) uint8, any H, W >= 1, N
+ * images per launch, 64-bit offsets.  The OpenCV steps are restated from the definitions below (tests/standard_mode_ref.py is the
+ * same restatement in numpy); NONE OF THEM HAS BEEN COMPARED WITH AN OPENCV BINARY.  For every neighbourhood stage (median,
+ * bilateral, blur) `out` must not overlap an input: MSTG_E_BADARG.
+ *
+ *   blend (:820-828)     x = clip(styled * (1 - r) + canvas * r, 0, 255) truncated, in float64 with two rounded products and one
+ *         rounded sum: mstg_blend_u8 with the operands swapped (orig = styled, styled = canvas, strength = r), byte for byte.  The
+ *         caller passes 1 - r as its own double; r <= 0 skips the step, as the reference does.
+ *   median (:835)        cv2.medianBlur(x, 3): per channel the median of the 9 samples of the 3 x 3 window, BORDER_REPLICATE
+ *         (coordinates clamped to the image), integers; H or W of 1 follows from the same rule.
+ *   bilateral (:838)     cv2.bilateralFilter(x, d, sigmaColor, sigmaSpace), OpenCV 4.x bilateralFilter_8u for three channels as
+ *         recalled from its source:
+ *           radius = max(d / 2, 1); d must be 3, 5, 7 or 9 (else MSTG_E_UNSUPPORTED, the message names d: d <= 0 would derive the
+ *           radius from sigmaSpace, and improved_smooth.py:106 would need radius 90); a sigma <= 0 counts as 1;
+ *           border: BORDER_REFLECT_101 (index p outside [0, len) mirrored without repeating the edge pixel, repeatedly for sides
+ *           shorter than the radius; len == 1 gives 0);
+ *           taps: (i, j) for i, then j, in -radius .. radius with sqrt(i * i + j * j) <= radius (49 taps at d = 9), sample
+ *           (y + i, x + j); space[k] = (float)exp((i * i + j * j) * (-0.5 / sigmaSpace^2)) and
+ *           color[t] = (float)exp(t * t * (-0.5 / sigmaColor^2)) for t = 0 .. 767, both evaluated in double on the HOST with
+ *           std::exp (mstg_bilateral_tables) and uploaded by the caller: the device never evaluates exp;
+ *           per pixel, in float32 and in tap order, with (b0, g0, r0) the centre sample: t = |b - b0| + |g - g0| + |r - r0|,
+ *           w = space[k] * color[t] (one rounded product), wsum += w, sum_c = fmaf((float)c, w, sum_c) for the three channels;
+ *           then inv = 1.0f / wsum (IEEE division) and out_c = sat_u8(rint_half_even(sum_c * inv)).
+ *         This is the SIMD path of an OpenCV build with FMA lanes (the stance taken for convertScaleAbs above); an unfused sum, a
+ *         division by wsum or a float64 evaluation differ on a fraction of the bytes, never by more than one grey level
+ *         (tests/test_standard_mode_cpu.py measures the shares).
+ *   colour step (:843-857) one 256-entry table per channel, lut[256 * channel + v], built on the host by mstg_standard_color_lut:
+ *           photo_to_monet: channel 0 = (u8)clip(v * 1.1, 0, 255), channel 1 = (u8)clip(v * 1.05, 0, 255) in float64, truncated,
+ *           channel 2 = v (the indices of the reference's code, not its comments);
+ *           monet_to_photo: cv2.convertScaleAbs(alpha=1.1, beta=5) = sat_u8(rint_half_even(|fmaf((float)v, 1.1f, 5.0f)|)) on all
+ *           three channels: the definition mstg_local_style_finish uses, here on uint8 input.
+ *   blur (:859-868)      cv2.GaussianBlur(x, (k, k), 0) with k = 2 * smooth_level + 1, OpenCV's bit-exact 8-bit path: taps in 8.8
+ *         fixed point, k = 3: {64, 128, 64}; k = 5: {16, 64, 96, 64, 16}; k = 7: {8, 28, 56, 72, 56, 28, 8}; along x, then along
+ *         y; BORDER_REFLECT_101 as above; the row sums stay exact in 16 bits; out = (sum + 32768) >> 16.  smooth_level 4 .. 7
+ *         (k = 9 .. 15) needs the taps of OpenCV's softfloat kernel generator, which are not restated: MSTG_E_UNSUPPORTED, the
+ *         message names the level; the blur is never approximated.  Level 0 skips the step.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_BILATERAL_COLOR_WEIGHTS 768
+#define MSTG_BILATERAL_MAX_TAPS 49
+#define MSTG_BILATERAL_TABLE_FLOATS (MSTG_BILATERAL_COLOR_WEIGHTS + MSTG_BILATERAL_MAX_TAPS)
+#define MSTG_STANDARD_PHOTO_TO_MONET 0
+#define MSTG_STANDARD_MONET_TO_PHOTO 1
+/* Host only: table[0 .. 767] = color[t], table[768 + k] = space[k] in tap order (entries past the last tap 0).  Returns the number of
+ * taps (5, 13, 29, 49 for d = 3, 5, 7, 9) or a negative code. */
+int mstg_bilateral_tables(int d, double sigma_color, double sigma_space, float* table /* [MSTG_BILATERAL_TABLE_FLOATS] */);
+/* Host only: the colour step's three tables for MSTG_STANDARD_PHOTO_TO_MONET / MSTG_STANDARD_MONET_TO_PHOTO; anything else BADARG */
+int mstg_standard_color_lut(int model_type, unsigned char* lut /* [768] */);
+int mstg_median3_u8(const unsigned char* in, int N, int H, int W, unsigned char* out, void* stream);
+/* table: the MSTG_BILATERAL_TABLE_FLOATS floats of mstg_bilateral_tables(d, sigmaColor, sigmaSpace) on the device */
+int mstg_bilateral_u8(const unsigned char* in, int N, int H, int W, int d, const float* table, unsigned char* out, void* stream);
+/* out = lut[256 * channel + in]; lut: 768 bytes on the device; out must not overlap in */
+int mstg_lut_u8(const unsigned char* in, int N, int H, int W, const unsigned char* lut, unsigned char* out, void* stream);
+/* ksize 3, 5 or 7; 9 .. 15 MSTG_E_UNSUPPORTED (names smooth_level = ksize / 2) */
+int mstg_gaussian_u8(const unsigned char* in, int N, int H, int W, int ksize, unsigned char* out, void* stream);
+/* bytes mstg_standard_finish needs for (N, H, W): two image batches; 0 for an invalid shape (mstg_last_error says which) */
+size_t mstg_standard_finish_workspace_bytes(int N, int H, int W);
+/* The enabled steps in the reference's order on the caller's workspace (16-byte aligned), byte for byte the composition of the
+ * stage entries, in at most three launches whatever N: with fix_blocks the median (the blend fused into its load), the bilateral
+ * filter (the colour table fused into its store) and the blur; without fix_blocks the blend and the table in one point-wise launch
+ * and the blur.  canvas may be NULL when blend_ratio <= 0; bilateral_table and d are read with fix_blocks only; color_lut NULL =
+ * no colour step; smooth_level 0 = no blur (the reference's adaptive_smooth=False).  out must not overlap anything else. */
+int mstg_standard_finish(const unsigned char* canvas, const unsigned char* styled, int N, int H, int W, double one_minus_ratio,
+                         double blend_ratio, int fix_blocks, int d, const float* bilateral_table /*nullable iff !fix_blocks*/,
+                         const unsigned char* color_lut /*nullable*/, int smooth_level, unsigned char* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain
  * (enhanced_generator.py:4; call shape :115, :218-225) -- parity unpinned; definition in structural_transformer.py.
  * The block's Linear layers go through mstg_conv2d_* (a Linear over tokens (N, L, dim) is a 1x1 convolution on NHWC).

@@ -193,9 +193,19 @@ SIGNATURES = {
     "mstg_local_style_finish": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mstg_local_style_enhanced_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_local_style_enhanced": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _i, _i, _vp, _vp, _sz, _vp]),
+    "mstg_bilateral_tables": (_i, [_i, C.c_double, C.c_double, _vp]),
+    "mstg_standard_color_lut": (_i, [_i, _vp]),
+    "mstg_median3_u8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "mstg_bilateral_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mstg_lut_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "mstg_gaussian_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "mstg_standard_finish_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_standard_finish": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
 }
 
 LOCAL_STYLE_MAX_PIXELS = 147456  # MSTG_LOCAL_STYLE_MAX_PIXELS
+BILATERAL_COLOR_WEIGHTS, BILATERAL_MAX_TAPS = 768, 49  # MSTG_BILATERAL_COLOR_WEIGHTS, MSTG_BILATERAL_MAX_TAPS
+STANDARD_MODEL_TYPES = {"photo_to_monet": 0, "monet_to_photo": 1}  # MSTG_STANDARD_PHOTO_TO_MONET, MSTG_STANDARD_MONET_TO_PHOTO
 
 _lib = None
 

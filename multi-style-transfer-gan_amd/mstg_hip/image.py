@@ -243,6 +243,119 @@ def _local_style_enhanced(canvas, styled, strength, detail, detail_coeff, enhanc
     return out
 
 
+# ---- the standard mode's finish (csrc/standard_mode.hip) -------------------------------------------------------------------
+_std_tables = {}
+
+
+def _bilateral_table(d, sigma_color, sigma_space, device):
+    """the host-built weight tables of ``mstg_bilateral_tables`` on ``device`` (built and uploaded once per parameter set)"""
+    key = ("bilateral", int(d), float(sigma_color), float(sigma_space), str(device))
+    if key not in _std_tables:
+        table = np.zeros(_lib.BILATERAL_COLOR_WEIGHTS + _lib.BILATERAL_MAX_TAPS, dtype=np.float32)
+        taps = _lib.load().mstg_bilateral_tables(int(d), float(sigma_color), float(sigma_space), table.ctypes.data)
+        if taps <= 0:
+            _lib.check(taps or -1, "mstg_bilateral_tables")
+        _std_tables[key] = torch.from_numpy(table).to(device)
+    return _std_tables[key]
+
+
+def _standard_model_type(model_type):
+    if model_type not in _lib.STANDARD_MODEL_TYPES:
+        raise ValueError(f"mstg_hip image: model_type {model_type!r} is neither 'photo_to_monet' nor 'monet_to_photo'")
+    return _lib.STANDARD_MODEL_TYPES[model_type]
+
+
+def _color_lut(model_type, device):
+    """the colour step's three 256-entry tables of ``mstg_standard_color_lut`` on ``device``"""
+    key = ("lut", _standard_model_type(model_type), str(device))
+    if key not in _std_tables:
+        lut = np.zeros(768, dtype=np.uint8)
+        _lib.check(_lib.load().mstg_standard_color_lut(key[1], lut.ctypes.data), "mstg_standard_color_lut")
+        _std_tables[key] = torch.from_numpy(lut).to(device)
+    return _std_tables[key]
+
+
+def _stage_u8(img, what):
+    single = img.dim() == 3
+    return single, _req_canvases(img.unsqueeze(0) if single else img, what)
+
+
+def median3_u8(img: torch.Tensor) -> torch.Tensor:
+    """``cv2.medianBlur(img, 3)`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU (gan_login_gui.py:835): per channel the
+    median of the 3 x 3 window with replicated borders, one launch whatever N.  Restated from the definition
+    (include/mstg_hip.h), not compared with an OpenCV binary."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_median3_u8(_p(x), N, H, W, _p(out), _stream()), "mstg_median3_u8")
+    return out[0] if single else out
+
+
+def bilateral_u8(img: torch.Tensor, d=9, sigma_color=75, sigma_space=75) -> torch.Tensor:
+    """``cv2.bilateralFilter(img, d, sigma_color, sigma_space)`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU
+    (gan_login_gui.py:838, :1423, :2560): OpenCV 4.x's 8-bit three-channel filter as include/mstg_hip.h defines it (float32 in tap
+    order, fused channel sums, one reciprocal, BORDER_REFLECT_101; the weight tables are built on the host), one launch whatever
+    N.  ``d`` must be 3, 5, 7 or 9; anything else raises, naming d.  Not compared with an OpenCV binary."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    table = _bilateral_table(d, sigma_color, sigma_space, x.device)
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_bilateral_u8(_p(x), N, H, W, int(d), _p(table), _p(out), _stream()), "mstg_bilateral_u8")
+    return out[0] if single else out
+
+
+def gaussian_u8(img: torch.Tensor, ksize) -> torch.Tensor:
+    """``cv2.GaussianBlur(img, (ksize, ksize), 0)`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU (gan_login_gui.py:865)
+    in OpenCV's bit-exact 8.8 fixed point, for ksize 3, 5 and 7; 9 to 15 (smooth_level 4 to 7) raise, naming the level: their
+    taps are not restated and the blur is never approximated.  Not compared with an OpenCV binary."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_gaussian_u8(_p(x), N, H, W, int(ksize), _p(out), _stream()), "mstg_gaussian_u8")
+    return out[0] if single else out
+
+
+def _standard_finish(canvas, styled, model_type, blend_ratio, fix_blocks, enhance_colors, smooth_level, adaptive_smooth, out=None):
+    """the standard mode's finish for (N, H, W, 3) batches that are already checked: at most three launches on one workspace"""
+    N, H, W = styled.shape[:3]
+    lib = _lib.load()
+    _standard_model_type(model_type)  # a bad name raises whatever the flags
+    lut = _color_lut(model_type, styled.device) if enhance_colors else None
+    table = _bilateral_table(9, 75, 75, styled.device) if fix_blocks else None
+    level = int(smooth_level) if adaptive_smooth and smooth_level > 0 else 0
+    w1 = float(blend_ratio) if blend_ratio > 0 else 0.0
+    w0 = 1 - w1  # Python's double subtraction, as in the reference's expression
+    if out is None:
+        out = torch.empty_like(styled)
+    need = lib.mstg_standard_finish_workspace_bytes(N, H, W)  # 0: the call below names what is wrong with the shape
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=styled.device)
+    _lib.check(lib.mstg_standard_finish(_p(canvas), _p(styled), N, H, W, w0, w1, int(bool(fix_blocks)), 9, _p(table), _p(lut), level,
+                                        _p(out), _p(ws), need, _stream()), "mstg_standard_finish")
+    return out
+
+
+def standard_finish(canvas_u8, styled_u8, model_type, blend_ratio=0.3, fix_blocks=True, enhance_colors=True, smooth_level=3,
+                    adaptive_smooth=True) -> torch.Tensor:
+    """Everything the standard mode of the reference's application does between the forward pass and the crop
+    (gan_login_gui.py:817-868) for an (H, W, 3) or (N, H, W, 3) uint8 canvas and styled image on the GPU, with that tab's options
+    and defaults: the ``blend_ratio`` blend with the canvas (0 skips it), ``fix_blocks`` = ``cv2.medianBlur(3)`` then
+    ``cv2.bilateralFilter(d=9, 75, 75)``, ``enhance_colors`` = the colour step of ``model_type`` ('photo_to_monet' or
+    'monet_to_photo'; anything else raises ValueError), and ``cv2.GaussianBlur`` of size ``2 * smooth_level + 1`` (level 0 or
+    ``adaptive_smooth=False`` skips it; levels above 3 raise, naming the level).  At most three launches whatever N, byte for byte
+    the composition of ``blend_u8``, ``median3_u8``, ``bilateral_u8``, the table lookup and ``gaussian_u8``.  The OpenCV steps are
+    restated from their definitions (include/mstg_hip.h), not compared with an OpenCV binary."""
+    _standard_model_type(model_type)
+    single, st = _stage_u8(styled_u8, "styled image")
+    _, c = _stage_u8(canvas_u8, "canvas")
+    if c.shape != st.shape:
+        raise RuntimeError(f"mstg_hip standard mode: shapes differ {tuple(c.shape)} vs {tuple(st.shape)}")
+    out = _standard_finish(c, st, model_type, blend_ratio, fix_blocks, enhance_colors, smooth_level, adaptive_smooth)
+    return out[0] if single else out
+
+
+_STANDARD = object()  # the mode of the batched pipeline that runs _standard_finish (not reachable through a mode name)
+
+
 # ---- the callers, restated on the device ----------------------------------------------------------------------------------
 def dataset_item(img_u8: torch.Tensor, grid_mask: int, img_size: int = 256):
     """MonetPhotoDataset.__getitem__ (pretrain.py:41-57) from a decoded uint8 image on the GPU: Resize(img_size) (shorter side,
@@ -324,6 +437,33 @@ def process_local_style(model, img_u8: torch.Tensor, mode="simple", strength=0.8
         else:
             crop_h, crop_w = target, int(target * aspect)
         crop_w, crop_h = min(crop_w, target), min(crop_h, target)
+        left, top = (target - crop_w) // 2, (target - crop_h) // 2
+        out = crop_u8(out, left, top, left + crop_w, top + crop_h)
+    if width * height <= 1024 * 1024:
+        out = resize_u8(out, (width, height), LANCZOS)
+    return out
+
+
+def process_standard(model, img_u8: torch.Tensor, model_type, blend_ratio=0.3, fix_blocks=True, enhance_colors=True, smooth_level=3,
+                     adaptive_smooth=True, target=256) -> torch.Tensor:
+    """The standard mode of the reference's application (gan_login_gui.py:769-889, standard_process_thread) without the file I/O,
+    on the GPU end to end: the letterbox and forward pass of ``process_cyclegan``, ``standard_finish`` with the tab's options (its
+    defaults: every step on), then the crop back to the aspect ratio and the LANCZOS resize back of :870-889.  The reference's
+    ``strength`` argument is never read there and is not taken."""
+    _standard_model_type(model_type)
+    canvas, (width, height) = letterbox(img_u8, target)
+    x = to_tensor(canvas).unsqueeze(0)
+    with torch.no_grad():
+        y = model(x)
+    styled = to_u8(y[0])
+    out = _standard_finish(canvas.unsqueeze(0), styled.unsqueeze(0), model_type, blend_ratio, fix_blocks, enhance_colors, smooth_level,
+                           adaptive_smooth)[0]
+    if width != height:
+        aspect = width / height
+        if aspect > 1:
+            crop_w, crop_h = target, int(target / aspect)
+        else:
+            crop_h, crop_w = target, int(target * aspect)
         left, top = (target - crop_w) // 2, (target - crop_h) // 2
         out = crop_u8(out, left, top, left + crop_w, top + crop_h)
     if width * height <= 1024 * 1024:
@@ -572,9 +712,9 @@ def _req_batch(images):
     return images
 
 
-def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, detail, detail_coeff, enhance_colors, smooth):
+def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, detail, detail_coeff, enhance_colors, smooth, standard=None):
     n, T, dev = len(images), target, images[0].device
-    blend = mode in ("simple", "weight_map", "enhanced")
+    blend = mode in ("simple", "weight_map", "enhanced") or mode is _STANDARD
     plan = _BatchPlan(dev)
     pre, post = plan.direction(canvas=T), plan.direction()
     x = torch.empty((n, 3, T, T), dtype=torch.float32, device=dev)
@@ -601,7 +741,9 @@ def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, de
     lib = _lib.load()
     _lib.check(lib.mstg_img_batch_tensor_to_u8(_p(y), int(y.dtype == torch.float16), n, T, T, _p(styled), _stream()),
                "mstg_img_batch_tensor_to_u8")
-    if mode == "enhanced":  # stages A-C and the finish on the canvas batch the chunk already has: four launches
+    if mode is _STANDARD:  # the standard mode's finish on the canvas batch the chunk already has: at most three launches
+        _standard_finish(canvas, styled, out=final, **standard)
+    elif mode == "enhanced":  # stages A-C and the finish on the canvas batch the chunk already has: four launches
         _local_style_enhanced(canvas, styled, strength, detail, detail_coeff, enhance_colors, smooth, out=final)
     elif blend:  # the (n * T, T, 3) view of the batch is one tall image to the blend kernel
         if mode == "weight_map":
@@ -621,7 +763,7 @@ def _process_chunk(model, images, geoms, target, mode, strength, weight_maps, de
 
 
 def _process_batch(model, images, target, batch_size, mode, strength, weight_maps, local_style, detail=0.7, detail_coeff=0.3,
-                   enhance_colors=True, smooth=True):
+                   enhance_colors=True, smooth=True, standard=None):
     images = _req_batch(images)
     target, batch_size = int(target), int(batch_size)
     if batch_size < 1:
@@ -641,7 +783,7 @@ def _process_batch(model, images, target, batch_size, mode, strength, weight_map
     for s in range(0, len(images), batch_size):
         e = s + batch_size
         outs += _process_chunk(model, images[s:e], geoms[s:e], target, mode, strength, None if weight_maps is None else weight_maps[s:e],
-                               detail, detail_coeff, enhance_colors, smooth)
+                               detail, detail_coeff, enhance_colors, smooth, standard)
     return outs
 
 
@@ -661,6 +803,17 @@ def process_local_style_batch(model, images, mode="simple", strength=0.8, weight
     blend), anything else = the styled image.  Six library launches per chunk at most, nine with the device-built map."""
     return _process_batch(model, images, target, batch_size, mode, strength, weight_maps, True, detail, detail_coeff, enhance_colors,
                           smooth)
+
+
+def process_standard_batch(model, images, model_type, blend_ratio=0.3, fix_blocks=True, enhance_colors=True, smooth_level=3,
+                           adaptive_smooth=True, target=256, batch_size=64):
+    """``process_standard`` for a sequence of uint8 (H, W, 3) GPU images of any sizes: byte-identical results, ``model`` called
+    once per chunk of ``batch_size`` images, the five launches of ``process_cyclegan_batch`` plus at most three for the finish
+    per chunk, whatever the chunk size."""
+    _standard_model_type(model_type)
+    standard = dict(model_type=model_type, blend_ratio=blend_ratio, fix_blocks=fix_blocks, enhance_colors=enhance_colors,
+                    smooth_level=smooth_level, adaptive_smooth=adaptive_smooth)
+    return _process_batch(model, images, target, batch_size, _STANDARD, None, None, False, standard=standard)
 
 
 def dataset_batch(images, grid_masks, img_size=256):
