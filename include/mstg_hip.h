@@ -705,6 +705,87 @@ int mstg_standard_finish(const unsigned char* canvas, const unsigned char* style
                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The LOCAL-STYLE tab and the COMPARE tab of the reference's application (gan_login_gui.py:1259-1530 local_style_process_thread,
+ * :2423-2638 compare_process_thread; the tab's defaults :1051-1116) between the forward pass and the crop, on the device for N
+ * images (N, H, W, 3) uint8, any H, W >= 1 unless stated, 64-bit offsets.  This is NOT the chain of mstg_local_style_enhanced,
+ * which restates batch_process_images.py (another sky rule, another edge weight, another finish).  The OpenCV steps are restated
+ * from the definitions below (tests/app_local_style_ref.py is the same restatement in numpy); NONE OF THEM HAS BEEN COMPARED WITH
+ * AN OPENCV BINARY.  No floating-point atomics, a fixed summation order: bit-reproducible and independent of N.
+ *
+ *   1. sky mask m (:1337-1355, :2483-2501), uint8 (N, H, W).  The 8-bit COLOR_RGB2HSV of the canvas: v, diff and s as defined for
+ *        the weight map above (sdiv, (diff * sdiv[v] + 2048) >> 12); hue: hdiv[0] = 0, hdiv[i] = round-half-even(122880 / i)
+ *        (= (180 << 12) / (6 i)); h0 = (v == R) ? G - B : (v == G) ? B - R + 2 * diff : R - G + 4 * diff (the test on R first);
+ *        h = (h0 * hdiv[diff] + 2048) >> 12 with an arithmetic shift of the signed product; h < 0: h += 180.
+ *        blue = 90 <= h <= 130 && s >= 30 && v >= 140 (cv2.inRange [90, 30, 140] .. [130, 255, 255]) and only for rows y < H / 2;
+ *        dil  = 255 where any blue lies in the 9 x 9 window clipped to the image, else 0 (cv2.dilate with a 5 x 5 box, two
+ *        iterations, default border: neutral);
+ *        m    = cv2.GaussianBlur(dil, (15, 15), 0), OpenCV's bit-exact 8-bit path: taps in 8.8 fixed point
+ *        {1, 3, 6, 12, 20, 30, 36, 40, 36, 30, 20, 12, 6, 3, 1} (sum 256) along x, then along y; BORDER_REFLECT_101 of dil (index p
+ *        outside [0, len) mirrored without repeating the edge pixel, repeatedly for sides shorter than 7; len == 1 gives 0); the
+ *        row sums are exact in 16 bits; m = (sum + 32768) >> 16.  The taps are OpenCV's generator as recalled: sigma =
+ *        ((15 - 1) * 0.5 - 1) * 0.3 + 0.8, t_i = exp(-0.5 x_i^2 / sigma^2) normalised by the left-to-right sum, then for the first
+ *        seven taps error diffusion a = t_i * 256 + err, q = round(a), err = a - q, and the centre = 256 - 2 * their sum.  The
+ *        smallest distance of any a from a rounding tie is 0.158 (tests/test_app_local_style_cpu.py regenerates the table and
+ *        asserts the margin), so a last-bit difference in exp cannot change a tap.  mstg_gaussian_u8 still refuses ksize 9 .. 15.
+ *   2. sky blend (:1358-1367): w = (double)m / 255.0; x = img * (1 - w) + orig * w in float64, two rounded products and one rounded
+ *        sum, no fused multiply-add; clip to [0, 255], truncate: the form of mstg_blend_u8 with orig := img (the styled image so
+ *        far) and styled := the canvas.
+ *   3. edge weight a (:1375-1391, :2520-2537), float64 (N, H, W).  edge = cv2.Canny(gray, 50, 150) of the canvas as
+ *        mstg_local_style_prepare and mstg_local_style_hysteresis compute it; ed = 1.0 where any edge lies in the 3 x 3 window
+ *        clipped to the image, else 0.0 (255 / 255.0 is exactly 1.0); ew = cv2.GaussianBlur(ed, (21, 21), 0) in float64, sigma 3.5,
+ *        BORDER_REFLECT_101 of ed, with OpenCV's generic row filter and symmetric column filter for CV_64F as recalled:
+ *          kernel k[0 .. 20] from the HOST (mstg_gaussian_kernel_f64): std::exp(x * x * (-0.5 / sigma^2)), x = i - 10, summed left
+ *          to right, every tap multiplied by 1 / sum; the caller uploads it, the device never evaluates exp;
+ *          row pass    r = k[0] * S[0]; r += k[j] * S[j] for j = 1 .. 20, left to right (the products are exact: S is 0 or 1);
+ *          column pass c = k[10] * R[0]; c += k[10 + j] * (R[+j] + R[-j]) for j = 1 .. 10, the nearest pair first;
+ *          every operation rounded, no fused multiply-add.
+ *        a = ew * detail (one rounded product); the blend is the form of 2 with w = a.  On images whose styled part equals the
+ *        canvas (where truncation is sensitive) a fused column pass changes 0.35 % of the bytes after this blend, the
+ *        outermost-pair-first order 0.85 %, scipy.ndimage.correlate1d(mode="mirror") 0.95 %, never by more than one level
+ *        (tests/test_app_local_style_cpu.py measures the shares).
+ *   4. strength blend (:1404-1408), only when strength < 0.3: bf = strength / 0.3; x = img * bf + orig * (1 - bf), clip, truncate;
+ *        the caller passes bf and 1 - bf as its own doubles (w_styled, w_canvas).
+ *   5. colour step (:1411-1418): the table of mstg_standard_color_lut for the direction.
+ *   6. smoothing (:1423): cv2.bilateralFilter(d=9, 75, 75) = mstg_bilateral_u8.
+ *   modes of the tab (:1315, :1328, :1428; named here simple, enhanced, advanced in the tab's order).  simple:
+ *        r = max(0.05, min(1.0 - strength, 0.95)), styled * (1 - r) + canvas * r, clip, truncate = step 4's form with
+ *        w_styled = 1 - r, w_canvas = r.  enhanced: 2 if ignore_sky and photo_to_monet, 3 if auto_select, 4, 5 if enhance_colors,
+ *        6 if smooth_transitions.  advanced (checked with a search of the file for the four helper names): every
+ *        helper it calls is guarded by hasattr(self, ...) and the class defines none of them, so it is step 4 alone.  Any other
+ *        name: the styled image.  The compare tab (:2475-2560) is the enhanced chain with auto_select, enhance_colors and
+ *        smooth_transitions on and detail = 0.6, beside the plain generator's output.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_APP_EDGE_KSIZE 21
+/* Host only: cv2.getGaussianKernel(ksize, sigma, CV_64F) as defined in 3 (sigma <= 0: ((ksize - 1) * 0.5 - 1) * 0.3 + 0.8);
+ * ksize odd, 1 .. 255 */
+int mstg_gaussian_kernel_f64(int ksize, double sigma, double* out /* [ksize] */);
+/* step 1: mask (N, H, W) bytes; one launch whatever N */
+int mstg_app_sky_mask(const unsigned char* canvas, int N, int H, int W, unsigned char* mask, void* stream);
+/* step 3 after Canny: edge = the (N, H, W) 0 / 1 mask of mstg_local_style_hysteresis, kernel_f64 = the MSTG_APP_EDGE_KSIZE doubles of
+ * mstg_gaussian_kernel_f64(21, 0) on the device, weight = a, float64 (N, H, W); one launch whatever N */
+int mstg_app_edge_weight(const unsigned char* edge, int N, int H, int W, const double* kernel_f64, double detail, double* weight,
+                         void* stream);
+/* the point-wise part, one launch: blend 2 with sky_mask (NULL: off), blend 3 with edge_weight (NULL: off), blend 4 with
+ * (w_styled, w_canvas) if use_strength, each clipped and truncated to a byte before the next, then the table (NULL: off).  canvas
+ * may be NULL when no blend is on; out must not overlap an input */
+int mstg_app_chain(const unsigned char* canvas, const unsigned char* styled, int N, int H, int W, const unsigned char* sky_mask /*nullable*/,
+                   const double* edge_weight /*nullable*/, int use_strength, double w_styled, double w_canvas,
+                   const unsigned char* color_lut /*nullable*/, unsigned char* out, void* stream);
+/* bytes mstg_app_local_style_finish needs for (N, H, W); 0 for an invalid shape (mstg_last_error says which) */
+size_t mstg_app_local_style_workspace_bytes(int N, int H, int W);
+/* The enabled steps in the reference's order on the caller's workspace (16-byte aligned), byte for byte the composition of the stage
+ * entries, in at most six launches whatever N: prepare, hysteresis, edge weight (auto_select), sky mask (ignore_sky: the caller
+ * passes ignore_sky && photo_to_monet), the point-wise chain, the bilateral filter (smooth).  With auto_select H * W <=
+ * MSTG_LOCAL_STYLE_MAX_PIXELS, else MSTG_E_UNSUPPORTED (the message names the size); without it any size.  kernel_f64 is read with
+ * auto_select only, bilateral_table (d = 9) with smooth only, color_lut NULL = no colour step.  out must not overlap an input, a
+ * table or the workspace: MSTG_E_BADARG. */
+int mstg_app_local_style_finish(const unsigned char* canvas, const unsigned char* styled, int N, int H, int W, int ignore_sky,
+                                int auto_select, int use_strength, int smooth, double detail, double w_styled, double w_canvas,
+                                const double* kernel_f64 /*nullable iff !auto_select*/, const unsigned char* color_lut /*nullable*/,
+                                const float* bilateral_table /*nullable iff !smooth*/, unsigned char* out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain
  * (enhanced_generator.py:4; call shape :115, :218-225) -- parity unpinned; definition in structural_transformer.py.
  * The block's Linear layers go through mstg_conv2d_* (a Linear over tokens (N, L, dim) is a 1x1 convolution on NHWC).

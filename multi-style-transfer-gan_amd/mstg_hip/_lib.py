@@ -201,8 +201,16 @@ SIGNATURES = {
     "mstg_gaussian_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mstg_standard_finish_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_standard_finish": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "mstg_gaussian_kernel_f64": (_i, [_i, C.c_double, _vp]),
+    "mstg_app_sky_mask": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "mstg_app_edge_weight": (_i, [_vp, _i, _i, _i, _vp, C.c_double, _vp, _vp]),
+    "mstg_app_chain": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "mstg_app_local_style_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_app_local_style_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                         _sz, _vp]),
 }
 
+APP_EDGE_KSIZE = 21  # MSTG_APP_EDGE_KSIZE
 LOCAL_STYLE_MAX_PIXELS = 147456  # MSTG_LOCAL_STYLE_MAX_PIXELS
 BILATERAL_COLOR_WEIGHTS, BILATERAL_MAX_TAPS = 768, 49  # MSTG_BILATERAL_COLOR_WEIGHTS, MSTG_BILATERAL_MAX_TAPS
 STANDARD_MODEL_TYPES = {"photo_to_monet": 0, "monet_to_photo": 1}  # MSTG_STANDARD_PHOTO_TO_MONET, MSTG_STANDARD_MONET_TO_PHOTO

@@ -834,3 +834,211 @@ def dataset_batch(images, grid_masks, img_size=256):
     pre.run_h(inter)
     pre.run_v_tensor(inter, masked, image, mask, use_mask=1)
     return masked, image, mask
+
+
+# ---- the application's local-style and compare tabs (csrc/app_local_style.hip) -----------------------------------------------
+APP_MODES = ("simple", "enhanced", "advanced")  # the tab's three modes in its order (gan_login_gui.py:1315, :1328, :1428)
+
+
+def _edge_kernel(device):
+    """the 21 float64 taps of ``mstg_gaussian_kernel_f64(21, 0)`` on ``device`` (built on the host and uploaded once)"""
+    key = ("edge_kernel", str(device))
+    if key not in _std_tables:
+        k = np.zeros(_lib.APP_EDGE_KSIZE, dtype=np.float64)
+        _lib.check(_lib.load().mstg_gaussian_kernel_f64(_lib.APP_EDGE_KSIZE, 0.0, k.ctypes.data), "mstg_gaussian_kernel_f64")
+        _std_tables[key] = torch.from_numpy(k).to(device)
+    return _std_tables[key]
+
+
+def app_sky_mask(canvas_u8: torch.Tensor) -> torch.Tensor:
+    """The sky mask of the application's local-style tab (gan_login_gui.py:1337-1355) of an (H, W, 3) or (N, H, W, 3) uint8 canvas
+    on the GPU -> uint8 (H, W) / (N, H, W): the 8-bit ``COLOR_RGB2HSV``, ``cv2.inRange([90, 30, 140], [130, 255, 255])`` on the
+    upper half, two ``cv2.dilate`` with a 5 x 5 box and ``cv2.GaussianBlur((15, 15), 0)`` in OpenCV's 8.8 fixed point, one launch
+    whatever N.  Restated from the definitions (include/mstg_hip.h), not compared with an OpenCV binary."""
+    single, c = _stage_u8(canvas_u8, "canvas")
+    N, H, W = c.shape[:3]
+    mask = torch.empty((N, H, W), dtype=torch.uint8, device=c.device)
+    _lib.check(_lib.load().mstg_app_sky_mask(_p(c), N, H, W, _p(mask), _stream()), "mstg_app_sky_mask")
+    return mask[0] if single else mask
+
+
+def app_edge_weight(canvas_u8: torch.Tensor, detail=0.6) -> torch.Tensor:
+    """The edge weight of the application's local-style tab (gan_login_gui.py:1375-1391) of an (H, W, 3) or (N, H, W, 3) uint8 canvas
+    on the GPU -> float64 (H, W) / (N, H, W): ``cv2.Canny(gray, 50, 150)`` (the two launches of ``enhanced_weight_map``, so H * W
+    <= 147456), ``cv2.dilate`` with a 3 x 3 box, ``cv2.GaussianBlur((21, 21), 0)`` in float64 in OpenCV's summation order, times
+    ``detail``; three launches whatever N.  Restated from the definitions (include/mstg_hip.h), not compared with an OpenCV
+    binary."""
+    single, c = _stage_u8(canvas_u8, "canvas")
+    N, H, W = c.shape[:3]
+    lib = _lib.load()
+    state, sky, edge = (torch.empty((N, H, W), dtype=torch.uint8, device=c.device) for _ in range(3))
+    count = torch.empty(N, dtype=torch.int32, device=c.device)
+    weight = torch.empty((N, H, W), dtype=torch.float64, device=c.device)
+    _lib.check(lib.mstg_local_style_prepare(_p(c), N, H, W, _p(state), _p(sky), _p(count), None, _stream()), "mstg_local_style_prepare")
+    _lib.check(lib.mstg_local_style_hysteresis(_p(state), N, H, W, _p(edge), _stream()), "mstg_local_style_hysteresis")
+    _lib.check(lib.mstg_app_edge_weight(_p(edge), N, H, W, _p(_edge_kernel(c.device)), float(detail), _p(weight), _stream()),
+               "mstg_app_edge_weight")
+    return weight[0] if single else weight
+
+
+def _app_plan(model_type, mode, strength, detail, auto_select, ignore_sky, enhance_colors, smooth_transitions):
+    """the switches and doubles of ``mstg_app_local_style_finish`` for a mode of the tab, or None for the styled image itself; the
+    doubles are formed with Python's own double arithmetic, as the reference's expressions"""
+    mt = _standard_model_type(model_type)  # a bad name raises whatever the mode
+    if mode not in APP_MODES:
+        return None
+    strength, detail = float(strength), float(detail)
+    if mode == "simple":
+        r = max(0.05, min(1.0 - strength, 0.95))
+        return dict(sky=False, auto=False, use_strength=True, w_styled=1 - r, w_canvas=r, colors=False, smooth=False, detail=detail)
+    low = strength < 0.3
+    bf = strength / 0.3 if low else 1.0
+    plan = dict(sky=False, auto=False, use_strength=low, w_styled=bf, w_canvas=1 - bf, colors=False, smooth=False, detail=detail)
+    if mode == "enhanced":
+        plan.update(sky=bool(ignore_sky) and mt == _lib.STANDARD_MODEL_TYPES["photo_to_monet"], auto=bool(auto_select),
+                    colors=bool(enhance_colors), smooth=bool(smooth_transitions))
+    return plan
+
+
+def _app_finish(canvas, styled, model_type, plan, out=None):
+    """``mstg_app_local_style_finish`` for (N, H, W, 3) batches that are already checked: at most six launches on one workspace"""
+    N, H, W = styled.shape[:3]
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty_like(styled)
+    dev = styled.device
+    kern = _edge_kernel(dev) if plan["auto"] else None
+    lut = _color_lut(model_type, dev) if plan["colors"] else None
+    table = _bilateral_table(9, 75, 75, dev) if plan["smooth"] else None
+    need = lib.mstg_app_local_style_workspace_bytes(N, H, W)  # 0: the call below names what is wrong with the shape
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mstg_app_local_style_finish(_p(canvas), _p(styled), N, H, W, int(plan["sky"]), int(plan["auto"]), int(plan["use_strength"]),
+                                               int(plan["smooth"]), plan["detail"], plan["w_styled"], plan["w_canvas"], _p(kern), _p(lut),
+                                               _p(table), _p(out), _p(ws), need, _stream()), "mstg_app_local_style_finish")
+    return out
+
+
+def app_local_style_finish(canvas_u8, styled_u8, model_type, mode="enhanced", strength=0.5, detail=0.6, auto_select=True, ignore_sky=True,
+                           enhance_colors=True, smooth_transitions=True) -> torch.Tensor:
+    """Everything the local-style tab of the reference's application does between the forward pass and the crop
+    (gan_login_gui.py:1315-1478) for an (H, W, 3) or (N, H, W, 3) uint8 canvas and styled image on the GPU, with that tab's
+    options and defaults (:1051-1116).  ``mode`` names the tab's three modes in English:
+
+    'simple'    ``styled * (1 - r) + canvas * r`` with ``r = max(0.05, min(1.0 - strength, 0.95))``;
+    'enhanced'  the sky blend (``ignore_sky`` and 'photo_to_monet': ``app_sky_mask``), the edge blend (``auto_select``:
+                ``app_edge_weight``; then H * W <= 147456, a larger canvas raises, naming the size), the strength blend (only for
+                ``strength < 0.3``), the colour step of ``model_type`` (``enhance_colors``) and ``cv2.bilateralFilter(9, 75, 75)``
+                (``smooth_transitions``); every blend is float64, clipped and truncated before the next;
+    'advanced'  the strength blend alone: every helper the reference calls in this mode is guarded by ``hasattr(self, ...)`` and
+                its class defines none of them;
+    any other name: the styled image.
+
+    At most six launches whatever N, byte for byte the composition of the stage functions.  ``model_type`` other than
+    'photo_to_monet' / 'monet_to_photo' raises ValueError.  This is not ``process_local_style``'s chain, which restates
+    batch_process_images.py.  Restated from the definitions (include/mstg_hip.h), not compared with an OpenCV binary."""
+    plan = _app_plan(model_type, mode, strength, detail, auto_select, ignore_sky, enhance_colors, smooth_transitions)
+    single, st = _stage_u8(styled_u8, "styled image")
+    _, c = _stage_u8(canvas_u8, "canvas")
+    if c.shape != st.shape:
+        raise RuntimeError(f"mstg_hip app local style: shapes differ {tuple(c.shape)} vs {tuple(st.shape)}")
+    out = st.clone() if plan is None else _app_finish(c, st, model_type, plan)
+    return out[0] if single else out
+
+
+def _app_chunk(models, images, geoms, target, model_type, plan):
+    """one chunk of the two tabs: the launches of ``_process_chunk`` with every model of ``models`` called on the same input batch;
+    the first model's output goes through ``_app_finish`` (``plan`` None: it stays as it is), the others are converted only; every
+    output is cropped and resized back alike.  Returns one list of images per model."""
+    n, T, dev = len(images), target, images[0].device
+    plan_b = _BatchPlan(dev)
+    pre = plan_b.direction(canvas=T)
+    posts = [plan_b.direction() for _ in models]
+    x = torch.empty((n, 3, T, T), dtype=torch.float32, device=dev)
+    canvas = torch.empty((n, T, T, 3), dtype=torch.uint8, device=dev)
+    finals = [torch.empty_like(canvas) for _ in models]
+    for im, g in zip(images, geoms):
+        pre.add(im.data_ptr(), g.height, g.width, (0, 0, g.height, g.width), (g.new_h, g.new_w), LANCZOS, (0, 0, g.new_h, g.new_w),
+                (g.off_y, g.off_x), 255)
+    for post, final in zip(posts, finals):
+        for i, g in enumerate(geoms):
+            left, top, crop_w, crop_h = g.crop
+            post.add(final.data_ptr() + i * T * T * 3, T, T, (top, left, crop_h, crop_w), (g.out_h, g.out_w), LANCZOS,
+                     (0, 0, g.out_h, g.out_w))
+    plan_b.upload()
+    inter = torch.empty(max([pre.inter_bytes] + [p.inter_bytes for p in posts]), dtype=torch.uint8, device=dev)
+    pre.run_h(inter)
+    pre.run_v_tensor(inter, x, canvas_u8=canvas)
+    lib = _lib.load()
+    for k, (model, final) in enumerate(zip(models, finals)):
+        with torch.no_grad():
+            y = model(x)
+        if not y.is_cuda or tuple(y.shape) != (n, 3, T, T):
+            raise RuntimeError(f"mstg_hip image: the model returned {tuple(y.shape)} for an input of {tuple(x.shape)}")
+        if y.dtype not in (torch.float32, torch.float16):
+            y = y.float()
+        y = y.contiguous()
+        styled = torch.empty_like(canvas) if k == 0 and plan is not None else final
+        _lib.check(lib.mstg_img_batch_tensor_to_u8(_p(y), int(y.dtype == torch.float16), n, T, T, _p(styled), _stream()),
+                   "mstg_img_batch_tensor_to_u8")
+        if styled is not final:
+            _app_finish(canvas, styled, model_type, plan, out=final)
+    results = []
+    for post in posts:
+        out = torch.empty(post.out_bytes, dtype=torch.uint8, device=dev)
+        post.run_h(inter)
+        post.run_v_u8(inter, out)
+        results.append([out[o:o + g.out_h * g.out_w * 3].view(g.out_h, g.out_w, 3) for o, g in zip(post.out_offs, geoms)])
+    return results
+
+
+def _app_batch(models, images, model_type, plan, target, batch_size):
+    images = _req_batch(images)
+    target, batch_size = int(target), int(batch_size)
+    if batch_size < 1:
+        raise RuntimeError(f"mstg_hip image: batch_size {batch_size}")
+    geoms = letterbox_plan([im.shape[:2] for im in images], target, local_style=True)
+    if plan is not None and plan["auto"] and target * target > _lib.LOCAL_STYLE_MAX_PIXELS:
+        raise RuntimeError(f"mstg_hip image: with auto_select the edge weight takes canvases of at most {_lib.LOCAL_STYLE_MAX_PIXELS} "
+                           f"pixels, not {target}x{target}")
+    outs = [[] for _ in models]
+    for s in range(0, len(images), batch_size):
+        for acc, part in zip(outs, _app_chunk(models, images[s:s + batch_size], geoms[s:s + batch_size], target, model_type, plan)):
+            acc += part
+    return outs
+
+
+def process_app_local_style_batch(model, images, model_type, mode="enhanced", strength=0.5, detail=0.6, auto_select=True, ignore_sky=True,
+                                  enhance_colors=True, smooth_transitions=True, target=256, batch_size=64):
+    """The local-style tab of the reference's application (gan_login_gui.py:1259-1530, local_style_process_thread) without the file
+    I/O for a sequence of uint8 (H, W, 3) GPU images of any sizes, on the GPU end to end: the letterbox on white and the forward
+    pass of ``process_cyclegan_batch`` (``model`` called once per chunk of ``batch_size`` images), ``app_local_style_finish`` with
+    the tab's options, then the crop back to the aspect ratio (with the tab's ``min`` clamps) and the LANCZOS resize back.  The
+    five launches of ``process_cyclegan_batch`` plus at most six per chunk, whatever the chunk size."""
+    plan = _app_plan(model_type, mode, strength, detail, auto_select, ignore_sky, enhance_colors, smooth_transitions)
+    return _app_batch([model], images, model_type, plan, target, batch_size)[0]
+
+
+def process_app_local_style(model, img_u8: torch.Tensor, model_type, mode="enhanced", strength=0.5, detail=0.6, auto_select=True,
+                            ignore_sky=True, enhance_colors=True, smooth_transitions=True, target=256) -> torch.Tensor:
+    """``process_app_local_style_batch`` for one image."""
+    return process_app_local_style_batch(model, [img_u8], model_type, mode, strength, detail, auto_select, ignore_sky, enhance_colors,
+                                         smooth_transitions, target, 1)[0]
+
+
+def process_compare_batch(enhanced_model, cyclegan_model, images, model_type, blend_strength=0.5, sky_handling=True, target=256,
+                          batch_size=64):
+    """The compare tab of the reference's application (gan_login_gui.py:2423-2638, compare_process_thread) without the file I/O
+    for a sequence of images: both models are called on the same letterboxed input batch; the first output goes through the
+    'enhanced' chain of ``app_local_style_finish`` with ``auto_select``, ``enhance_colors`` and ``smooth_transitions`` on,
+    ``detail = 0.6``, ``strength = blend_strength`` and ``ignore_sky = sky_handling``, the second is the plain generator's
+    ``to_u8`` output; both are cropped and resized back alike.  The reference's ``smooth_level`` and ``fix_blocks`` arguments are
+    never read there and are not taken.  Returns (local_style, cyclegan), two lists."""
+    plan = _app_plan(model_type, "enhanced", blend_strength, 0.6, True, sky_handling, True, True)
+    local, plain = _app_batch([enhanced_model, cyclegan_model], images, model_type, plan, target, batch_size)
+    return local, plain
+
+
+def process_compare(enhanced_model, cyclegan_model, img_u8: torch.Tensor, model_type, blend_strength=0.5, sky_handling=True, target=256):
+    """``process_compare_batch`` for one image -> (local_style, cyclegan)."""
+    local, plain = process_compare_batch(enhanced_model, cyclegan_model, [img_u8], model_type, blend_strength, sky_handling, target, 1)
+    return local[0], plain[0]
