@@ -3,6 +3,8 @@ dispatch to) and against the golden vectors of the reference's LocalAttention / 
 
 Tolerance: the north star asks for 1e-3 relative; the fp32 MFMA path is an exact fmaf chain, so these tests hold the
 kernels to 2e-5 relative L2 (1e-4 for gradients that sum ~1e5 products) and print the measured error.
+What "every C-ABI kernel" leaves out here -- parameter gradients added in place under ops.direct_param_grads(), and the reduction,
+element-wise, loss and optimizer kernels at their tails and past one grid -- is in test_gpu_direct_grads.py and test_gpu_reductions.py.
 """
 import os
 

@@ -79,6 +79,150 @@ def test_flash_attention_vs_torch(N, L, heads, D):
     report(f"flash attention L{L} heads{heads} D{D} dqkv", rel_l2(gg, gr), 2e-5)
 
 
+# ---- the edges of the token kernels ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(1, 3, 4, 4), (3, 3, 20, 36)])
+def test_structure_map_borders(shape):
+    """The right and bottom borders drop their forward difference; a single-cell image is all border."""
+    from mstg_hip import ops
+    from oracle import restatement as R
+    x = R.make_input(shape, 2)
+    s = ops.structure_map(x.to(DEV))
+    report(f"structure_map {shape}", rel_l2(s.reshape(shape[0], -1, 4), R.structure_map(x.double())), 1e-6)
+
+
+# ln_mod_bwd_kernel splits L into chunks of up to 512 tokens (at most 64 of them) and ln_mod_reduce_kernel adds them; a thread row
+# serves 64 channels at a time, so dim = 96, 160, 200, 252 leave the last 64-channel chunk partly filled
+LN_EDGES = [(1, 1, 4, True), (3, 5, 8, True), (2, 33, 96, True), (1, 70, 160, False), (2, 17, 200, True), (1, 40, 252, True),
+            (2, 1100, 32, True),   # three chunks, the last one shorter
+            (1, 513, 64, False),   # two chunks
+            (1, 33000, 32, True)]  # the cap of 64 chunks
+
+
+@pytest.mark.parametrize("N,L,dim,mod", LN_EDGES)
+def test_layer_norm_mod_edges_vs_fp64(N, L, dim, mod):
+    """Against fp64 F.layer_norm plus modulation at the bars of test_layer_norm_mod_vs_torch.  dgamma and dbeta of the two long cases
+    add N * L >= 2200 products in fp32: their bar is max(2e-5, 4 * d32), d32 the distance of torch's own fp32 evaluation on the CPU
+    from fp64 (printed; the margin of 4 is test_generator_with_block_vs_oracle's for one fp32 evaluation against another).
+    The MI355X run printed d32 = 2.1e-07 / 1.7e-07 (L = 1100) and 9.7e-07 / 1.3e-06 (L = 33000), so the bar stayed 2e-5; the kernel
+    sat at 1.3e-07 / 1.1e-07 and 1.6e-07 / 2.6e-07."""
+    from mstg_hip import ops
+    x, ga, be = rnd((N, L, dim), 1) * 2 + 0.3, 1 + 0.1 * rnd((dim,), 2), 0.1 * rnd((dim,), 3)
+    ts = [x, ga, be] + ([0.2 * rnd((N, dim), 4), 0.2 * rnd((N, dim), 5)] if mod else [])
+    gy = rnd((N, L, dim), 6)
+
+    def ref(dtype):
+        leaves = [t.to(dtype).requires_grad_(True) for t in ts]
+        y = F.layer_norm(leaves[0], (dim,), leaves[1], leaves[2], 1e-5)
+        if mod:
+            y = y * (1 + leaves[3][:, None]) + leaves[4][:, None]
+        return y.detach(), torch.autograd.grad((y * gy.to(dtype)).sum(), leaves)
+
+    yr, gr = ref(torch.float64)
+    dl = [t.to(DEV).requires_grad_(True) for t in ts]
+    y = ops.layer_norm_mod(dl[0], dl[1], dl[2], dl[3] if mod else None, dl[4] if mod else None)
+    gg = torch.autograd.grad((y * gy.to(DEV)).sum(), dl)
+    report(f"ln_mod N{N} L{L} dim{dim} y", rel_l2(y, yr), 1e-5)
+    tols = {}
+    if N * L >= 2200:
+        _, g32 = ref(torch.float32)
+        for j, name in ((1, "dgamma"), (2, "dbeta")):
+            d32 = rel_l2(g32[j], gr[j])
+            print(f"  [parity] ln_mod N{N} L{L} dim{dim} {name}: torch fp32 (CPU) vs fp64 {d32:.2e}")
+            tols[name] = max(2e-5, 4.0 * d32)
+    for name, a, b in zip(("dx", "dgamma", "dbeta", "dgmod", "dbmod"), gg, gr):
+        report(f"ln_mod N{N} L{L} dim{dim} {name}", rel_l2(a, b), tols.get(name, 2e-5))
+
+
+def _flash_ref(qkv, gy, heads, dtype):
+    N, L, C3 = qkv.shape
+    dim = C3 // 3
+    D = dim // heads
+    t = qkv.to(dtype).requires_grad_(True)
+    q, k, v = (u.reshape(N, L, heads, D).transpose(1, 2) for u in t.chunk(3, dim=-1))
+    a = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(D), dim=-1) @ v
+    y = a.transpose(1, 2).reshape(N, L, dim)
+    (g,) = torch.autograd.grad((y * gy.to(dtype)).sum(), [t])
+    return y.detach(), g
+
+
+def _flash_hip(qkv, gy, heads):
+    from mstg_hip import ops
+    tg = qkv.to(DEV).requires_grad_(True)
+    y = ops.flash_attention(tg, heads)
+    (gg,) = torch.autograd.grad((y * gy.to(DEV)).sum(), [tg])
+    return y.detach(), gg
+
+
+@pytest.mark.parametrize("N,L,heads,D", [(2, 130, 2, 16), (3, 5, 1, 8), (2, 127, 1, 64), (1, 65, 4, 32), (2, 15, 4, 8)])
+def test_flash_attention_ragged_tiles_of_several_images(N, L, heads, D):
+    """N > 1 with L % 64 != 0: the tail of an image's last key tile lies in the next image's tokens, whose scores are masked; L < 16 is
+    less than one MFMA tile of keys."""
+    dim = heads * D
+    qkv, gy = rnd((N, L, 3 * dim), 1, 0.8), rnd((N, L, dim), 2)
+    yr, gr = _flash_ref(qkv, gy, heads, torch.float64)
+    y, gg = _flash_hip(qkv, gy, heads)
+    report(f"flash attention N{N} L{L} heads{heads} D{D} out", rel_l2(y, yr), 1e-5)
+    report(f"flash attention N{N} L{L} heads{heads} D{D} dqkv", rel_l2(gg, gr), 2e-5)
+
+
+def test_flash_attention_single_token():
+    """One token: the softmax is exactly 1, so out == v and dv == d_out bit for bit, and nothing reaches q and k."""
+    qkv, gy = rnd((1, 1, 24), 3, 0.8), rnd((1, 1, 8), 4)
+    y, gg = _flash_hip(qkv, gy, 1)
+    assert torch.equal(y.cpu(), qkv[..., 16:])
+    assert torch.equal(gg[..., 16:].cpu(), gy)
+    assert float(gg[..., :16].abs().max()) <= 1e-5
+
+
+def test_flash_attention_large_logits():
+    """q and k scaled by 6 (v left alone): the logits reach about +-100 and the softmax is nearly one-hot, so the running maximum
+    carries the result.  The rounding of a logit of size 100 alone moves a probability by 1e-5: the bar is max(existing bar,
+    4 * d32), d32 the distance of torch's own fp32 evaluation on the CPU from fp64 (printed).  The MI355X run printed max |logit|
+    111.2, d32 = 1.17e-06 (out) and 3.17e-06 (dqkv) -- the existing bars stood -- and the kernel at 1.17e-06 and 3.55e-06."""
+    N, L, heads, D = 1, 200, 2, 64
+    dim = heads * D
+    qkv, gy = rnd((N, L, 3 * dim), 1, 0.8), rnd((N, L, dim), 2)
+    qkv[..., :2 * dim] *= 6.0
+    yr, gr = _flash_ref(qkv, gy, heads, torch.float64)
+    q, k = (u.reshape(N, L, heads, D).transpose(1, 2).double() for u in qkv.chunk(3, dim=-1)[:2])
+    big = float((q @ k.transpose(-1, -2) / math.sqrt(D)).abs().max())
+    print(f"  [parity] flash attention large logits: max |logit| {big:.1f}")
+    assert big > 80
+    y32, g32 = _flash_ref(qkv, gy, heads, torch.float32)
+    d32y, d32g = rel_l2(y32, yr), rel_l2(g32, gr)
+    print(f"  [parity] flash attention large logits: torch fp32 (CPU) vs fp64 out {d32y:.2e} dqkv {d32g:.2e}")
+    y, gg = _flash_hip(qkv, gy, heads)
+    assert bool(torch.isfinite(y).all()) and bool(torch.isfinite(gg).all())
+    report("flash attention large logits out", rel_l2(y, yr), max(1e-5, 4.0 * d32y))
+    report("flash attention large logits dqkv", rel_l2(gg, gr), max(2e-5, 4.0 * d32g))
+
+
+def test_flash_attention_reads_no_token_past_the_last():
+    """The kernels mask the scores of keys past L, so what a key tile's tail holds cannot show in the result as long as it is
+    finite (0 * finite = 0) -- the next image's tokens are.  What fa_stage's own bound (t0 + t < L) keeps out is memory behind the
+    tensor: here qkv and d_out are the heads of larger buffers whose tails (64 token rows, one full tile) hold NaN, handed to the C
+    ABI as pointers.  A staged row from there turns every output into NaN (0 * NaN)."""
+    from mstg_hip import _lib
+    lib = _lib.load()
+    N, L, heads, D = 2, 70, 2, 16
+    dim = heads * D
+    qkv, gy = rnd((N, L, 3 * dim), 7, 0.8), rnd((N, L, dim), 8)
+    yr, gr = _flash_ref(qkv, gy, heads, torch.float64)
+    nan = float("nan")
+    qkv_b = torch.cat([qkv.reshape(-1), torch.full((64 * 3 * dim,), nan)]).to(DEV)
+    gy_b = torch.cat([gy.reshape(-1), torch.full((64 * dim,), nan)]).to(DEV)
+    out = torch.empty((N, L, dim), device=DEV)
+    lse, delta = torch.empty((N, heads, L), device=DEV), torch.empty((N, heads, L), device=DEV)
+    dqkv = torch.empty((N, L, 3 * dim), device=DEV)
+    st = torch.cuda.current_stream().cuda_stream
+    _lib.check(lib.mstg_flash_attn_fwd(qkv_b.data_ptr(), out.data_ptr(), lse.data_ptr(), N, L, heads, D, st), "mstg_flash_attn_fwd")
+    _lib.check(lib.mstg_flash_attn_bwd(qkv_b.data_ptr(), out.data_ptr(), lse.data_ptr(), gy_b.data_ptr(), dqkv.data_ptr(), delta.data_ptr(),
+                                       N, L, heads, D, st), "mstg_flash_attn_bwd")
+    assert bool(torch.isfinite(out).all()) and bool(torch.isfinite(dqkv).all())
+    report("flash attention, NaN behind the tensor: out", rel_l2(out, yr), 1e-5)
+    report("flash attention, NaN behind the tensor: dqkv", rel_l2(dqkv, gr), 2e-5)
+
+
 @pytest.mark.parametrize("C_,shape", [(8, (2, 3, 32, 32)), (16, (1, 3, 64, 48))])
 def test_block_vs_oracle(C_, shape):
     from oracle import restatement as R
