@@ -686,7 +686,8 @@ int mstg_bilateral_tables(int d, double sigma_color, double sigma_space, float* 
 /* Host only: the colour step's three tables for MSTG_STANDARD_PHOTO_TO_MONET / MSTG_STANDARD_MONET_TO_PHOTO; anything else BADARG */
 int mstg_standard_color_lut(int model_type, unsigned char* lut /* [768] */);
 int mstg_median3_u8(const unsigned char* in, int N, int H, int W, unsigned char* out, void* stream);
-/* table: the MSTG_BILATERAL_TABLE_FLOATS floats of mstg_bilateral_tables(d, sigmaColor, sigmaSpace) on the device */
+/* table: the MSTG_BILATERAL_TABLE_FLOATS floats of mstg_bilateral_tables(d, sigmaColor, sigmaSpace) on the device.  Any other d,
+ * d <= 0 and radii up to 90 (improved_smooth.py:106): mstg_bilateral_wide_u8 below, the same definition */
 int mstg_bilateral_u8(const unsigned char* in, int N, int H, int W, int d, const float* table, unsigned char* out, void* stream);
 /* out = lut[256 * channel + in]; lut: 768 bytes on the device; out must not overlap in */
 int mstg_lut_u8(const unsigned char* in, int N, int H, int W, const unsigned char* lut, unsigned char* out, void* stream);
@@ -784,6 +785,94 @@ int mstg_app_local_style_finish(const unsigned char* canvas, const unsigned char
                                 const double* kernel_f64 /*nullable iff !auto_select*/, const unsigned char* color_lut /*nullable*/,
                                 const float* bilateral_table /*nullable iff !smooth*/, unsigned char* out, void* workspace,
                                 size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The COLOUR-BLOCK REPAIR of the reference (improved_smooth.py:137-164 fix_color_blocks_improved), on the device for N images
+ * (N, H, W, 3) uint8 RGB, any H, W >= 1, N images per launch, 64-bit offsets.  The OpenCV steps are restated from the definitions
+ * below, as recalled (tests/color_blocks_ref.py is the same restatement in numpy); NONE OF THEM HAS BEEN COMPARED WITH AN OPENCV
+ * BINARY.  No floating-point atomics, a fixed summation order: bit-reproducible and independent of N.  `out` (and a workspace) must
+ * not overlap an input: MSTG_E_BADARG.  The device never evaluates exp, pow or cbrt: the tables come from host-only entries.  A
+ * parameter outside what is built is refused with MSTG_E_UNSUPPORTED and a message naming it, never approximated.
+ *
+ *   1. block mask (:53-95 detect_color_blocks; threshold 30, kernel_size 11), bytes 0 / 1 (N, H, W).
+ *        a, b of the 8-bit COLOR_RGB2LAB (L is never used), OpenCV's integer path as recalled.  Tables, built on the host in
+ *        double (mstg_lab_tables):
+ *          gamma[v] = round(2040 * lin(v / 255)), v = 0 .. 255, lin(x) = x <= 0.04045 ? x / 12.92 : ((x + 0.055) / 1.055)^2.4;
+ *          cbrt[i]  = round(32768 * f(i / 2040)), i = 0 .. 3071, f(x) = x < 0.008856 ? 7.787 x + 16 / 116 : cbrt(x);
+ *          C[r][k]  = round(4096 * M[r][k] / white[r]), M = {0.412453, 0.357580, 0.180423; 0.212671, 0.715160, 0.072169;
+ *          0.019334, 0.119193, 0.950227}, white = {0.950456, 1, 1.088754}: C = {1777, 1541, 778; 871, 2929, 296; 73, 448, 3575},
+ *          every row sums to 4096; max gamma = 2040, max cbrt = 37555 (16 bits), the index below stays <= 2040.
+ *        Per pixel, with R' = gamma[R] and so on: fX = cbrt[(R' C00 + G' C01 + B' C02 + 2048) >> 12], fY, fZ from rows 1 and 2;
+ *          a = sat_u8((500 (fX - fY) + 128 * 32768 + 16384) >> 15), b = sat_u8((200 (fY - fZ) + 128 * 32768 + 16384) >> 15),
+ *          arithmetic shifts.  White and black give (128, 128), (255, 0, 0) gives (208, 195), (0, 255, 0) (42, 211), (0, 0, 255)
+ *          (207, 20).  Over all 2^24 colours a lies within 2.67 and b within 1.70 of float64 CIE Lab.  The smallest distance of
+ *          an unrounded gamma or cbrt entry from a rounding tie is 4.7e-6 (asserted above 1e-9: a last-bit difference of pow or
+ *          cbrt cannot change an entry).  OpenCV 4 builds these tables in 32-bit soft-float: evaluated in float32 instead of
+ *          double, 0 of the 256 gamma entries and 2 of the 3072 cbrt entries change, by one unit
+ *          (tests/test_color_blocks_cpu.py measures both).
+ *        gradient: on the a and b planes as float32, cv2.Sobel(ksize=3) in x and in y, BORDER_REFLECT_101 (all values are integers
+ *          of at most 1020, any summation order is exact); m = sqrt_rn_f32(gx^2 + gy^2) (the argument is an integer below 2^24);
+ *          c = fl32(m_a + m_b) * 0.5f; edge = c > threshold (float32).
+ *        dilation: mask = 1 where any edge lies in the k x k window clipped to the image (cv2.dilate with a box, default border:
+ *          neutral); k odd, 1 .. MSTG_COLOR_BLOCK_MAX_KERNEL, anything else refused (the message names kernel_size).
+ *   2. correction (:10-51 adaptive_color_correction; radius 50).  For a flagged pixel and every channel: sum and count over the
+ *        (2 r + 1)^2 window of the INPUT clipped to the image (exact integers; uint32, so H * W * 255 < 2^32, else refused by
+ *        name); mean = (double)sum / (double)count (one IEEE division); v = 0.5 * px + 0.5 * mean (both products exact, one
+ *        rounded sum); the byte is v truncated (the reference assigns float64 into a uint8 array).  Unflagged pixels are copied;
+ *        with no flagged pixel the stage is the identity, which is the reference's blocks_detected.any() branch.
+ *   3. wide bilateral (:97-112 edge_preserving_smoothing; cv2.bilateralFilter(img, 0, 0.4 * 255, 60)): the definition of
+ *        mstg_bilateral_u8 above word for word (tap order i, then j, with sqrt(i^2 + j^2) <= radius; float32, contraction off;
+ *        w = space * color[t] one rounded product; wsum += w; three fmaf channel sums; inv = 1.0f / wsum; rint, saturate;
+ *        BORDER_REFLECT_101 repeated for sides shorter than the radius; a sigma <= 0 counts as 1), extended in two ways:
+ *          radius: d <= 0: radius = cvRound(sigmaSpace * 1.5) (round half to even), at least 1; d > 0: radius = max(d / 2, 1);
+ *          radii 1 .. MSTG_BILATERAL_WIDE_MAX_RADIUS are built, above that refused (the message names the radius).  sigmaSpace 60
+ *          gives radius 90: 25 445 taps;
+ *          space weights: space(i, j) = (float)exp((i^2 + j^2) * (-0.5 / sigmaSpace^2)) in double on the host, a function of
+ *          i^2 + j^2 alone, so the device table is indexed by it (8101 floats at radius 90).
+ *        At d = 3, 5, 7, 9 the result equals mstg_bilateral_u8 byte for byte.
+ *   4. detail blend (:114-135 detail_enhancing_blend; alpha 0.1, beta 0.5 in the chain), on float64: blurred =
+ *        cv2.GaussianBlur(orig, (0, 0), 3): for a depth other than 8 bits ksize = cvRound(sigma * 4 * 2 + 1) | 1 = 25; the kernel is
+ *        mstg_gaussian_kernel_f64(25, 3); row pass and column pass exactly as defined for step 3 of the application's local-style
+ *        chain above (row pass left to right; column pass centre first, then the nearest pair; every operation rounded, no fused
+ *        multiply-add; BORDER_REFLECT_101 repeated for sides shorter than 12), here per channel on byte-valued input;
+ *        detail = orig - blurred; x = ((img * w_img) + (orig * alpha)) + (detail * beta), every operation rounded; the caller
+ *        passes w_img = 1 - alpha as its own double; clip to [0, 255], truncate.  ksize odd, 1 .. MSTG_DETAIL_BLEND_MAX_KSIZE,
+ *        anything else refused (the message names ksize).  A caller resizes an original of another size first (Lanczos,
+ *        mstg_resample_*).
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_LAB_TABLE_U16 3340 /* gamma[256], cbrt[3072], C[9] row by row, 3 entries of padding */
+#define MSTG_COLOR_BLOCK_MAX_KERNEL 31
+#define MSTG_BILATERAL_WIDE_MAX_RADIUS 90
+#define MSTG_BILATERAL_WIDE_TABLE_FLOATS (MSTG_BILATERAL_COLOR_WEIGHTS + MSTG_BILATERAL_WIDE_MAX_RADIUS * MSTG_BILATERAL_WIDE_MAX_RADIUS + 1)
+#define MSTG_DETAIL_BLEND_MAX_KSIZE 31
+/* Host only: the tables of step 1 */
+int mstg_lab_tables(unsigned short* table /* [MSTG_LAB_TABLE_U16] */);
+/* Host only: table[0 .. 767] = color[t], table[768 + q] = space weight of i^2 + j^2 = q for q <= radius^2 (0 beyond).  Returns the
+ * radius (1 .. 90) that d and sigma_space give, or a negative code. */
+int mstg_bilateral_wide_tables(int d, double sigma_color, double sigma_space, float* table /* [MSTG_BILATERAL_WIDE_TABLE_FLOATS] */);
+/* step 1: lab_table = the MSTG_LAB_TABLE_U16 entries of mstg_lab_tables on the device; mask (N, H, W) bytes; workspace: N * H * W
+ * bytes (the undilated edges); two launches whatever N */
+int mstg_color_block_mask(const unsigned char* in, int N, int H, int W, const unsigned short* lab_table, float threshold, int kernel_size,
+                          unsigned char* mask, void* workspace, size_t workspace_bytes, void* stream);
+/* step 2: mask (N, H, W) bytes, nonzero = flagged; workspace: N * H * W * 12 bytes, 4-byte aligned (the window's row sums); two
+ * launches whatever N */
+int mstg_color_correct_u8(const unsigned char* in, const unsigned char* mask, int N, int H, int W, int radius, unsigned char* out,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* step 3: radius and table (on the device) from mstg_bilateral_wide_tables; one launch whatever N */
+int mstg_bilateral_wide_u8(const unsigned char* in, int N, int H, int W, int radius, const float* table, unsigned char* out, void* stream);
+/* step 4: kernel_f64 = the ksize doubles of mstg_gaussian_kernel_f64 on the device; workspace: N * H * W * 24 bytes, 8-byte aligned
+ * (the row pass); two launches whatever N, the blend fused into the column pass */
+int mstg_detail_blend_u8(const unsigned char* img, const unsigned char* orig, int N, int H, int W, const double* kernel_f64, int ksize,
+                         double w_img, double alpha, double beta, unsigned char* out, void* workspace, size_t workspace_bytes, void* stream);
+/* bytes mstg_color_block_fix needs for (N, H, W), with or without an original; 0 for an invalid shape (mstg_last_error says which) */
+size_t mstg_color_block_fix_workspace_bytes(int N, int H, int W, int with_orig);
+/* Steps 1 to 3, and step 4 when orig != NULL, on the caller's workspace (16-byte aligned), byte for byte the composition of the
+ * stage entries: five launches without an original, seven with one, whatever N.  kernel_f64, ksize, w_img, alpha and beta are
+ * read with an original only. */
+int mstg_color_block_fix(const unsigned char* in, const unsigned char* orig /*nullable*/, int N, int H, int W,
+                         const unsigned short* lab_table, float threshold, int kernel_size, int correct_radius, int bilateral_radius,
+                         const float* bilateral_table, const double* kernel_f64 /*nullable iff !orig*/, int ksize, double w_img,
+                         double alpha, double beta, unsigned char* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain

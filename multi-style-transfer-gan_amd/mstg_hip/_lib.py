@@ -208,11 +208,23 @@ SIGNATURES = {
     "mstg_app_local_style_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_app_local_style_finish": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp,
                                          _sz, _vp]),
+    "mstg_lab_tables": (_i, [_vp]),
+    "mstg_bilateral_wide_tables": (_i, [_i, C.c_double, C.c_double, _vp]),
+    "mstg_color_block_mask": (_i, [_vp, _i, _i, _i, _vp, _f, _i, _vp, _vp, _sz, _vp]),
+    "mstg_color_correct_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mstg_bilateral_wide_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mstg_detail_blend_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "mstg_color_block_fix_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mstg_color_block_fix": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _i, _i, _i, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                  _sz, _vp]),
 }
 
 APP_EDGE_KSIZE = 21  # MSTG_APP_EDGE_KSIZE
 LOCAL_STYLE_MAX_PIXELS = 147456  # MSTG_LOCAL_STYLE_MAX_PIXELS
 BILATERAL_COLOR_WEIGHTS, BILATERAL_MAX_TAPS = 768, 49  # MSTG_BILATERAL_COLOR_WEIGHTS, MSTG_BILATERAL_MAX_TAPS
+LAB_TABLE_U16 = 3340  # MSTG_LAB_TABLE_U16
+BILATERAL_WIDE_MAX_RADIUS = 90  # MSTG_BILATERAL_WIDE_MAX_RADIUS
+BILATERAL_WIDE_TABLE_FLOATS = 768 + 90 * 90 + 1  # MSTG_BILATERAL_WIDE_TABLE_FLOATS
 STANDARD_MODEL_TYPES = {"photo_to_monet": 0, "monet_to_photo": 1}  # MSTG_STANDARD_PHOTO_TO_MONET, MSTG_STANDARD_MONET_TO_PHOTO
 
 _lib = None

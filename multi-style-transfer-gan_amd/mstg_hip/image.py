@@ -1042,3 +1042,155 @@ def process_compare(enhanced_model, cyclegan_model, img_u8: torch.Tensor, model_
     """``process_compare_batch`` for one image -> (local_style, cyclegan)."""
     local, plain = process_compare_batch(enhanced_model, cyclegan_model, [img_u8], model_type, blend_strength, sky_handling, target, 1)
     return local[0], plain[0]
+
+
+# ---- the colour-block repair of improved_smooth.py (csrc/color_blocks.hip) --------------------------------------------------
+def _lab_table(device):
+    """the 16-bit gamma, cube-root and coefficient tables of ``mstg_lab_tables`` on ``device`` (built on the host, uploaded once)"""
+    key = ("lab", str(device))
+    if key not in _std_tables:
+        t = np.zeros(_lib.LAB_TABLE_U16, dtype=np.uint16)
+        _lib.check(_lib.load().mstg_lab_tables(t.ctypes.data), "mstg_lab_tables")
+        _std_tables[key] = torch.from_numpy(t.view(np.int16)).to(device)  # the same bits: torch has no uint16 on every build
+    return _std_tables[key]
+
+
+def _bilateral_wide_table(d, sigma_color, sigma_space, device):
+    """(radius, table): the host-built weight tables of ``mstg_bilateral_wide_tables`` on ``device`` (once per parameter set); a
+    radius above 90 raises, naming it"""
+    key = ("bilateral_wide", int(d), float(sigma_color), float(sigma_space), str(device))
+    if key not in _std_tables:
+        table = np.zeros(_lib.BILATERAL_WIDE_TABLE_FLOATS, dtype=np.float32)
+        radius = _lib.load().mstg_bilateral_wide_tables(int(d), float(sigma_color), float(sigma_space), table.ctypes.data)
+        if radius <= 0:
+            _lib.check(radius or -1, "mstg_bilateral_wide_tables")
+        _std_tables[key] = (radius, torch.from_numpy(table).to(device))
+    return _std_tables[key]
+
+
+def _detail_ksize(sigma):
+    """cv2.GaussianBlur's size for ksize = (0, 0) on float64: cvRound(sigma * 4 * 2 + 1) | 1 (round half to even)"""
+    return int(round(float(sigma) * 4 * 2 + 1)) | 1
+
+
+def _detail_kernel(ksize, sigma, device):
+    """the float64 taps of ``mstg_gaussian_kernel_f64(ksize, sigma)`` on ``device`` (built on the host and uploaded once)"""
+    key = ("detail_kernel", int(ksize), float(sigma), str(device))
+    if key not in _std_tables:
+        k = np.zeros(int(ksize), dtype=np.float64)
+        _lib.check(_lib.load().mstg_gaussian_kernel_f64(int(ksize), float(sigma), k.ctypes.data), "mstg_gaussian_kernel_f64")
+        _std_tables[key] = torch.from_numpy(k).to(device)
+    return _std_tables[key]
+
+
+def detect_color_blocks(img: torch.Tensor, threshold=30, kernel_size=11) -> torch.Tensor:
+    """``detect_color_blocks`` of the reference (improved_smooth.py:53-95) for an (H, W, 3) or (N, H, W, 3) uint8 RGB image on the
+    GPU -> bool (H, W) / (N, H, W): a and b of the 8-bit ``COLOR_RGB2LAB``, ``cv2.Sobel(ksize=3)`` on both, the mean of the two
+    magnitudes ``> threshold``, ``cv2.dilate`` with a ``kernel_size`` box (odd, at most 31; anything else raises, naming
+    kernel_size); two launches whatever N.  Restated from the definitions (include/mstg_hip.h), not compared with an OpenCV
+    binary."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    mask = torch.empty((N, H, W), dtype=torch.uint8, device=x.device)
+    ws = torch.empty((N, H, W), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().mstg_color_block_mask(_p(x), N, H, W, _p(_lab_table(x.device)), float(threshold), int(kernel_size), _p(mask),
+                                                 _p(ws), ws.numel(), _stream()), "mstg_color_block_mask")
+    mask = mask != 0
+    return mask[0] if single else mask
+
+
+def adaptive_color_correction(img: torch.Tensor, blocks_detected=None, radius=50) -> torch.Tensor:
+    """``adaptive_color_correction`` of the reference (improved_smooth.py:10-51) for an (H, W, 3) or (N, H, W, 3) uint8 image on the
+    GPU: every pixel flagged in ``blocks_detected`` (bool or bytes, (H, W) / (N, H, W); None: ``detect_color_blocks(img)``) becomes
+    ``0.5 * px + 0.5 * mean`` of its ``(2 radius + 1)^2`` window of the input clipped to the image, in float64, truncated; the
+    others are copied.  Two launches whatever N and no host synchronisation: with nothing flagged the result is the input."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    if blocks_detected is None:
+        m = detect_color_blocks(x)
+    else:
+        m = blocks_detected.unsqueeze(0) if blocks_detected.dim() == 2 else blocks_detected
+        if not m.is_cuda or tuple(m.shape) != (N, H, W):
+            raise RuntimeError(f"mstg_hip colour blocks: expected a mask of shape {(N, H, W)} on the GPU, got {tuple(m.shape)}")
+    m = m.to(torch.uint8).contiguous()
+    out = torch.empty_like(x)
+    ws = torch.empty(N * H * W * 3, dtype=torch.int32, device=x.device)
+    _lib.check(_lib.load().mstg_color_correct_u8(_p(x), _p(m), N, H, W, int(radius), _p(out), _p(ws), ws.numel() * 4, _stream()),
+               "mstg_color_correct_u8")
+    return out[0] if single else out
+
+
+def edge_preserving_smoothing(img: torch.Tensor, sigma_s=60, sigma_r=0.4) -> torch.Tensor:
+    """``edge_preserving_smoothing`` of the reference (improved_smooth.py:97-112) for an (H, W, 3) or (N, H, W, 3) uint8 image on
+    the GPU: ``cv2.bilateralFilter(img, 0, sigma_r * 255, sigma_s)`` as include/mstg_hip.h defines it, the radius derived from
+    ``sigma_s`` (90 and 25 445 taps at the default; above 90, sigma_s >= 61, raises, naming the radius); one launch whatever N.  Not
+    compared with an OpenCV binary."""
+    return bilateral_wide_u8(img, 0, sigma_r * 255, sigma_s)
+
+
+def bilateral_wide_u8(img: torch.Tensor, d=0, sigma_color=102.0, sigma_space=60) -> torch.Tensor:
+    """``cv2.bilateralFilter(img, d, sigma_color, sigma_space)`` for any ``d`` (``d <= 0``: the radius is ``cvRound(sigma_space *
+    1.5)``) up to radius 90, the definition of ``bilateral_u8`` through ``mstg_bilateral_wide_u8``; at d = 3, 5, 7, 9 the same
+    bytes as ``bilateral_u8``."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    radius, table = _bilateral_wide_table(d, sigma_color, sigma_space, x.device)
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_bilateral_wide_u8(_p(x), N, H, W, radius, _p(table), _p(out), _stream()), "mstg_bilateral_wide_u8")
+    return out[0] if single else out
+
+
+def _same_size(original, x):
+    """``original`` as an (N, H, W, 3) batch of the size of ``x``: an original of another size goes through the Lanczos resize"""
+    o = original.unsqueeze(0) if original.dim() == 3 else original
+    H, W = x.shape[1:3]
+    if tuple(o.shape[1:3]) != (H, W):
+        o = torch.stack([resize_u8(im, (W, H), LANCZOS) for im in o])
+    o = _req_canvases(o, "original")
+    if o.shape != x.shape:
+        raise RuntimeError(f"mstg_hip colour blocks: shapes differ {tuple(o.shape)} vs {tuple(x.shape)}")
+    return o
+
+
+def detail_enhancing_blend(img: torch.Tensor, original: torch.Tensor, alpha=0.3, beta=1.5, sigma=3.0) -> torch.Tensor:
+    """``detail_enhancing_blend`` of the reference (improved_smooth.py:114-135) for (H, W, 3) or (N, H, W, 3) uint8 images on the
+    GPU: ``img * (1 - alpha) + original * alpha + (original - GaussianBlur(original, (0, 0), sigma)) * beta`` in float64 in
+    OpenCV's summation order, clipped and truncated; an ``original`` of another size is resized first (Lanczos).  ``sigma`` is 3
+    in the reference (25 taps); a size above 31 (sigma above 3.81) raises, naming ksize.  Two launches whatever N."""
+    single, x = _stage_u8(img, "image")
+    o = _same_size(original, x)
+    N, H, W = x.shape[:3]
+    ksize = _detail_ksize(sigma)
+    lib = _lib.load()
+    if ksize > 31:  # before the taps are built: the refusal names the size
+        _lib.check(lib.mstg_detail_blend_u8(None, None, N, H, W, None, ksize, 0.0, 0.0, 0.0, None, None, 0, None), "mstg_detail_blend_u8")
+    kern = _detail_kernel(ksize, sigma, x.device)
+    out = torch.empty_like(x)
+    ws = torch.empty(N * H * W * 3, dtype=torch.float64, device=x.device)
+    alpha, beta = float(alpha), float(beta)
+    _lib.check(lib.mstg_detail_blend_u8(_p(x), _p(o), N, H, W, _p(kern), ksize, 1 - alpha, alpha, beta, _p(out), _p(ws), ws.numel() * 8,
+                                        _stream()), "mstg_detail_blend_u8")
+    return out[0] if single else out
+
+
+def fix_color_blocks(img: torch.Tensor, original=None) -> torch.Tensor:
+    """``fix_color_blocks_improved`` of the reference (improved_smooth.py:137-164) between decoding and encoding, for an (H, W, 3)
+    or (N, H, W, 3) uint8 image on the GPU with the reference's constants: ``detect_color_blocks`` (30, 11),
+    ``adaptive_color_correction`` (radius 50), ``edge_preserving_smoothing`` (60, 0.4) and, with an ``original``,
+    ``detail_enhancing_blend`` (alpha 0.1, beta 0.5).  Five launches on one workspace (seven with an original) whatever N, byte
+    for byte the composition of the four stage functions.  Restated from the definitions (include/mstg_hip.h), not compared with
+    an OpenCV binary."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    lib = _lib.load()
+    dev = x.device
+    o = _same_size(original, x) if original is not None else None
+    radius, table = _bilateral_wide_table(0, 0.4 * 255, 60, dev)
+    ksize, alpha, beta = _detail_ksize(3.0), 0.1, 0.5
+    kern = _detail_kernel(ksize, 3.0, dev) if o is not None else None
+    out = torch.empty_like(x)
+    need = lib.mstg_color_block_fix_workspace_bytes(N, H, W, int(o is not None))  # 0: the call below names what is wrong
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _lib.check(lib.mstg_color_block_fix(_p(x), _p(o), N, H, W, _p(_lab_table(dev)), 30.0, 11, 50, radius, _p(table), _p(kern), ksize,
+                                        1 - alpha, alpha, beta, _p(out), _p(ws), need, _stream()), "mstg_color_block_fix")
+    return out[0] if single else out
