@@ -27,7 +27,7 @@
 // Integer arithmetic or a fixed float64 order everywhere, no atomics in these kernels: bit-reproducible and independent of N.
 #include <cmath>
 
-#include "common.h"
+#include "u8_image.h"
 
 namespace mstg {
 
@@ -46,21 +46,6 @@ static_assert(AE_TAPS == 2 * AE_RB + 1, "the edge blur has 21 taps");
 static_assert(AS_DWP >= AS_DW && AS_DWP % 4 == 0 && AS_TW % 4 == 0 && AE_DW % 4 == 0 && AE_TW == 64 && AE_TH == 16 && AP_THREADS == 256,
               "dword passes; one column and four rows per thread in the edge weight's column pass");
 
-// OpenCV's getGaussianKernel(15, sigma <= 0) in 8.8 fixed point (softfloat generator with error diffusion, see the header); sum 256
-__device__ __forceinline__ int as_tap(int k) {
-    constexpr int t[15] = {1, 3, 6, 12, 20, 30, 36, 40, 36, 30, 20, 12, 6, 3, 1};
-    return t[k];
-}
-
-// cv2.BORDER_REFLECT_101 (d c b | a b c d | c b a), for any distance from the array; n == 1 gives 0
-__device__ __forceinline__ int ap_reflect101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
 // round-half-even(num / i) in integers, 0 for i == 0
 __device__ __forceinline__ int ap_div_rhe(int num, int i) {
     if (i == 0) return 0;
@@ -76,9 +61,7 @@ __global__ __launch_bounds__(AP_THREADS) void app_sky_mask_kernel(const unsigned
     __shared__ __align__(16) unsigned char dl[AS_DH * AS_DWP];  // the dilated mask, 0 / 255, mirrored outside the image
     __shared__ __align__(16) unsigned short hz[AS_DH * AS_TW];  // the horizontally filtered rows, exact (<= 65280)
     const int tid = threadIdx.x;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * AS_TH, x0 = tx * AS_TW;
+    const auto [n, y0, x0] = tile_of<AS_TH, AS_TW>(tiles, tiles_x);
     const size_t plane = (size_t)n * H * W;
     const unsigned char* img = canvas + plane * 3;
     unsigned char* m_img = mask + plane;
@@ -106,7 +89,7 @@ __global__ __launch_bounds__(AP_THREADS) void app_sky_mask_kernel(const unsigned
             const int py = y0 - AS_HALO + r, px = x0 - AS_HALO + c;
             ok[k] = e < AS_BH * AS_BW && (unsigned)py < (unsigned)half && (unsigned)px < (unsigned)W;  // only the upper half can be sky
             const unsigned char* p = img + (ok[k] ? ((size_t)py * W + px) * 3 : 0);
-            rgb[k] = (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16;
+            rgb[k] = load_px(p);
         }
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
@@ -144,7 +127,7 @@ __global__ __launch_bounds__(AP_THREADS) void app_sky_mask_kernel(const unsigned
         const int r = e / AS_DW, c = e - r * AS_DW;
         const int py = y0 - AS_RB + r, px = x0 - AS_RB + c;
         if ((unsigned)py < (unsigned)H && (unsigned)px < (unsigned)W) continue;
-        const int my = ap_reflect101(py, H), mx = ap_reflect101(px, W);
+        const int my = reflect101(py, H), mx = reflect101(px, W);
         const int mr = min(max(my - (y0 - AS_RB), 0), AS_DH - 1), mc = min(max(mx - (x0 - AS_RB), 0), AS_DW - 1);
         dl[r * AS_DWP + c] = dl[mr * AS_DWP + mc];
     }
@@ -161,7 +144,7 @@ __global__ __launch_bounds__(AP_THREADS) void app_sky_mask_kernel(const unsigned
         for (int j = 0; j < 4; ++j) {
             int sum = 0;
 #pragma unroll
-            for (int k = 0; k <= 2 * AS_RB; ++k) sum += as_tap(k) * px[j + k];
+            for (int k = 0; k <= 2 * AS_RB; ++k) sum += gauss_q8_tap<2 * AS_RB + 1>(k) * px[j + k];
             o[j] = (unsigned)sum;  // <= 65280
         }
         *reinterpret_cast<uint2*>(&hz[r * AS_TW + c]) = make_uint2(o[0] | o[1] << 16, o[2] | o[3] << 16);
@@ -175,10 +158,10 @@ __global__ __launch_bounds__(AP_THREADS) void app_sky_mask_kernel(const unsigned
 #pragma unroll
         for (int k = 0; k <= 2 * AS_RB; ++k) {
             const uint2 h = *reinterpret_cast<const uint2*>(&hz[(r + k) * AS_TW + c]);
-            sum[0] += as_tap(k) * (int)(h.x & 0xffffu);
-            sum[1] += as_tap(k) * (int)(h.x >> 16);
-            sum[2] += as_tap(k) * (int)(h.y & 0xffffu);
-            sum[3] += as_tap(k) * (int)(h.y >> 16);
+            sum[0] += gauss_q8_tap<2 * AS_RB + 1>(k) * (int)(h.x & 0xffffu);
+            sum[1] += gauss_q8_tap<2 * AS_RB + 1>(k) * (int)(h.x >> 16);
+            sum[2] += gauss_q8_tap<2 * AS_RB + 1>(k) * (int)(h.y & 0xffffu);
+            sum[3] += gauss_q8_tap<2 * AS_RB + 1>(k) * (int)(h.y >> 16);
         }
         unsigned o[4];
 #pragma unroll
@@ -201,9 +184,7 @@ __global__ __launch_bounds__(AP_THREADS) void app_edge_weight_kernel(const unsig
     __shared__ __align__(16) unsigned char ed[AE_DH * AE_DW];  // the dilated mask, 0 / 1, mirrored outside the image
     __shared__ __align__(16) double rw[AE_DH * AE_TW];         // the row pass
     const int tid = threadIdx.x;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * AE_TH, x0 = tx * AE_TW;
+    const auto [n, y0, x0] = tile_of<AE_TH, AE_TW>(tiles, tiles_x);
     const size_t plane = (size_t)n * H * W;
     const unsigned char* e_img = edge + plane;
     constexpr int NB = 7;  // batches of unconditional loads, as in the sky mask: a position outside the image reads pixel 0, counts as 0
@@ -230,8 +211,8 @@ __global__ __launch_bounds__(AP_THREADS) void app_edge_weight_kernel(const unsig
     for (int e = tid; e < AE_DH * AE_DW; e += AP_THREADS) {
         const int r = e / AE_DW, c = e - r * AE_DW;
         int py = y0 - AE_RB + r, px = x0 - AE_RB + c;
-        if ((unsigned)py >= (unsigned)H) py = ap_reflect101(py, H);
-        if ((unsigned)px >= (unsigned)W) px = ap_reflect101(px, W);
+        if ((unsigned)py >= (unsigned)H) py = reflect101(py, H);
+        if ((unsigned)px >= (unsigned)W) px = reflect101(px, W);
         const int mr = min(max(py - (y0 - AE_HALO), 1), AE_EH - 2), mc = min(max(px - (x0 - AE_HALO), 1), AE_EW - 2);
         const unsigned char* p = &eg[(mr - 1) * AE_EW + mc - 1];
         ed[e] = p[0] | p[1] | p[2] | p[AE_EW] | p[AE_EW + 1] | p[AE_EW + 2] | p[2 * AE_EW] | p[2 * AE_EW + 1] | p[2 * AE_EW + 2];
@@ -275,17 +256,6 @@ __global__ __launch_bounds__(AP_THREADS) void app_edge_weight_kernel(const unsig
     }
 }
 
-// one byte of img * w_img + orig * w_orig as blend_u8_kernel forms it: two rounded products, one rounded sum, clip, truncate
-__device__ __forceinline__ unsigned ap_blend_byte(unsigned img, unsigned orig, double w_img, double w_orig) {
-#pragma clang fp contract(off)  // numpy rounds each product and the sum
-    const double a = (double)img * w_img;
-    const double b = (double)orig * w_orig;
-    double r = a + b;
-    r = r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r);
-    if (!(r == r)) r = 0.0;  // a NaN weight: keep the byte defined, as blend_u8_kernel does
-    return (unsigned)(unsigned char)r;
-}
-
 // flat pixel streams of npix pixels; four pixels (12 bytes) per thread
 template <bool SKY, bool EDGE, bool STRENGTH, bool LUT>
 __global__ __launch_bounds__(AP_THREADS) void app_chain_kernel(const unsigned char* __restrict__ canvas,
@@ -298,7 +268,7 @@ __global__ __launch_bounds__(AP_THREADS) void app_chain_kernel(const unsigned ch
     __shared__ unsigned char slut[LUT ? 768 : 4];
     const int tid = threadIdx.x;
     if (LUT) {
-        for (int e = tid; e < 768; e += AP_THREADS) slut[e] = lut[e];
+        stage_lut768<AP_THREADS>(lut, slut, tid);
         __syncthreads();
     }
     const size_t p0 = ((size_t)blockIdx.x * AP_THREADS + tid) * 4;
@@ -335,10 +305,10 @@ __global__ __launch_bounds__(AP_THREADS) void app_chain_kernel(const unsigned ch
         const unsigned c = (vc[b >> 2] >> (8 * (b & 3))) & 0xffu;
         if (SKY) {
             const double w = (double)((vm >> (8 * k)) & 0xffu) / 255.0;  // IEEE division, as numpy's
-            v = ap_blend_byte(v, c, 1.0 - w, w);
+            v = blend_byte(v, c, 1.0 - w, w);
         }
-        if (EDGE) v = ap_blend_byte(v, c, 1.0 - wa[k], wa[k]);
-        if (STRENGTH) v = ap_blend_byte(v, c, w_img, w_orig);
+        if (EDGE) v = blend_byte(v, c, 1.0 - wa[k], wa[k]);
+        if (STRENGTH) v = blend_byte(v, c, w_img, w_orig);
         if (LUT) v = slut[256 * ch + v];
         vo[b >> 2] |= v << (8 * (b & 3));
     }
@@ -351,44 +321,8 @@ __global__ __launch_bounds__(AP_THREADS) void app_chain_kernel(const unsigned ch
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-// 0 = fine, else the error code (message set)
-static int ap_shape(const char* who, int N, int H, int W) {
-    char msg[200];
-    if (N < 1 || H < 1 || W < 1) {
-        snprintf(msg, sizeof(msg), "%s: N = %d, H = %d, W = %d: need at least one image of at least one pixel", who, N, H, W);
-        return fail_arg(MSTG_E_BADARG, msg);
-    }
-    if ((long long)H * W * 3 >= (1ll << 31)) {
-        snprintf(msg, sizeof(msg), "%s: H * W * 3 = %lld does not fit 31 bits", who, (long long)H * W * 3);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    const long long blocks = (long long)N * cdiv(H, AE_TH) * cdiv(W, AE_TW);  // the finest tiling; the point-wise grid is no finer
-    if (blocks >= (1ll << 24)) {
-        snprintf(msg, sizeof(msg), "%s: N * tiles = %lld, more than 2^24 - 1 workgroups in one launch", who, blocks);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    return MSTG_OK;
-}
-
-static int ap_fits_lds(const char* who, int H, int W) {
-    if ((long long)H * W > MSTG_LOCAL_STYLE_MAX_PIXELS) {
-        char msg[220];
-        snprintf(msg, sizeof(msg),
-                 "%s: a %d x %d image has %lld pixels; with auto_select the hysteresis keeps one byte per pixel in LDS and takes at most %d",
-                 who, H, W, (long long)H * W, MSTG_LOCAL_STYLE_MAX_PIXELS);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    return MSTG_OK;
-}
-
-static bool ap_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-static size_t ap_align(size_t b) { return (b + 15) & ~(size_t)15; }
-static bool ap_al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
+// the shape check is check_shape_16x64: the edge weight's tiling (AE_TH x AE_TW, asserted above) is the finest, the point-wise grid
+// is no finer
 static int ap_sky_mask(const unsigned char* canvas, int N, int H, int W, unsigned char* mask, hipStream_t st) {
     const int tx = cdiv(W, AS_TW), tiles = tx * cdiv(H, AS_TH);
     MSTG_LAUNCH(app_sky_mask_kernel, dim3((unsigned)(N * tiles)), dim3(AP_THREADS), 0, st, canvas, H, W, tx, tiles, mask);
@@ -428,7 +362,7 @@ static int ap_chain(const unsigned char* canvas, const unsigned char* styled, co
                     double w_img, double w_orig, const unsigned char* color_lut, size_t npix, unsigned char* out, hipStream_t st) {
     const dim3 grid((unsigned)cdivz(npix, (size_t)AP_THREADS * 4));
     const bool blend = sky || edge_w || strength;
-    const int aligned = ap_al4(styled) && ap_al4(out) && (!blend || ap_al4(canvas)) && (!sky || ap_al4(sky));
+    const int aligned = aligned4(styled) && aligned4(out) && (!blend || aligned4(canvas)) && (!sky || aligned4(sky));
     const bool lut = color_lut != nullptr;
     if (sky && edge_w)
         ap_chain_se<true, true>(strength, lut, grid, st, canvas, styled, sky, edge_w, w_img, w_orig, color_lut, npix, aligned, out);
@@ -447,16 +381,16 @@ struct ApWorkspace {
     size_t weight, state, sky_bits, edge, mask, count, image, total;
 };
 static ApWorkspace ap_workspace(int N, int H, int W) {
-    const size_t px = (size_t)N * H * W, plane = ap_align(px);
+    const size_t px = (size_t)N * H * W, plane = align16(px);
     ApWorkspace w;
     w.weight = 0;
-    w.state = ap_align(px * sizeof(double));
+    w.state = align16(px * sizeof(double));
     w.sky_bits = w.state + plane;
     w.edge = w.sky_bits + plane;
     w.mask = w.edge + plane;
     w.count = w.mask + plane;
-    w.image = w.count + ap_align((size_t)N * sizeof(int));
-    w.total = w.image + ap_align(px * 3);
+    w.image = w.count + align16((size_t)N * sizeof(int));
+    w.total = w.image + align16(px * 3);
     return w;
 }
 
@@ -486,22 +420,22 @@ extern "C" int mstg_gaussian_kernel_f64(int ksize, double sigma, double* out) {
 
 extern "C" int mstg_app_sky_mask(const unsigned char* canvas, int N, int H, int W, unsigned char* mask, void* stream) {
     if (!canvas || !mask) return fail_arg(MSTG_E_BADARG, "app_sky_mask: null canvas or mask pointer");
-    const int rc = ap_shape("app_sky_mask", N, H, W);
+    const int rc = check_shape_16x64("app_sky_mask", N, H, W);
     if (rc != MSTG_OK) return rc;
     const size_t px = (size_t)N * H * W;
-    if (ap_overlap(mask, px, canvas, px * 3)) return fail_arg(MSTG_E_BADARG, "app_sky_mask: mask overlaps the canvas");
+    if (overlaps(mask, px, canvas, px * 3)) return fail_arg(MSTG_E_BADARG, "app_sky_mask: mask overlaps the canvas");
     return ap_sky_mask(canvas, N, H, W, mask, (hipStream_t)stream);
 }
 
 extern "C" int mstg_app_edge_weight(const unsigned char* edge, int N, int H, int W, const double* kernel_f64, double detail, double* weight,
                                     void* stream) {
     if (!edge || !kernel_f64 || !weight) return fail_arg(MSTG_E_BADARG, "app_edge_weight: null edge, kernel or weight pointer");
-    const int rc = ap_shape("app_edge_weight", N, H, W);
+    const int rc = check_shape_16x64("app_edge_weight", N, H, W);
     if (rc != MSTG_OK) return rc;
     if (((uintptr_t)weight & 7) || ((uintptr_t)kernel_f64 & 7))
         return fail_arg(MSTG_E_ALIGN, "app_edge_weight: weight or kernel not 8-byte aligned");
     const size_t px = (size_t)N * H * W;
-    if (ap_overlap(weight, px * 8, edge, px) || ap_overlap(weight, px * 8, kernel_f64, sizeof(double) * AE_TAPS))
+    if (overlaps(weight, px * 8, edge, px) || overlaps(weight, px * 8, kernel_f64, sizeof(double) * AE_TAPS))
         return fail_arg(MSTG_E_BADARG, "app_edge_weight: weight overlaps the edge mask or the kernel");
     return ap_edge_weight(edge, kernel_f64, detail, N, H, W, weight, (hipStream_t)stream);
 }
@@ -511,18 +445,18 @@ extern "C" int mstg_app_chain(const unsigned char* canvas, const unsigned char* 
                               unsigned char* out, void* stream) {
     const bool blend = sky_mask || edge_weight || use_strength;
     if (!styled || !out || (blend && !canvas)) return fail_arg(MSTG_E_BADARG, "app_chain: null styled, out or (with a blend) canvas pointer");
-    const int rc = ap_shape("app_chain", N, H, W);
+    const int rc = check_shape_16x64("app_chain", N, H, W);
     if (rc != MSTG_OK) return rc;
     if ((uintptr_t)edge_weight & 7) return fail_arg(MSTG_E_ALIGN, "app_chain: edge_weight not 8-byte aligned");
     const size_t px = (size_t)N * H * W, nb = px * 3;
-    if (ap_overlap(out, nb, styled, nb) || (blend && ap_overlap(out, nb, canvas, nb)) || (sky_mask && ap_overlap(out, nb, sky_mask, px)) ||
-        (edge_weight && ap_overlap(out, nb, edge_weight, px * 8)) || (color_lut && ap_overlap(out, nb, color_lut, 768)))
+    if (overlaps(out, nb, styled, nb) || (blend && overlaps(out, nb, canvas, nb)) || (sky_mask && overlaps(out, nb, sky_mask, px)) ||
+        (edge_weight && overlaps(out, nb, edge_weight, px * 8)) || (color_lut && overlaps(out, nb, color_lut, 768)))
         return fail_arg(MSTG_E_BADARG, "app_chain: out overlaps an input, a mask or the table");
     return ap_chain(canvas, styled, sky_mask, edge_weight, use_strength != 0, w_styled, w_canvas, color_lut, px, out, (hipStream_t)stream);
 }
 
 extern "C" size_t mstg_app_local_style_workspace_bytes(int N, int H, int W) {
-    if (ap_shape("app_local_style_workspace_bytes", N, H, W) != MSTG_OK) return 0;
+    if (check_shape_16x64("app_local_style_workspace_bytes", N, H, W) != MSTG_OK) return 0;
     return ap_workspace(N, H, W).total;
 }
 
@@ -531,8 +465,8 @@ extern "C" int mstg_app_local_style_finish(const unsigned char* canvas, const un
                                            const double* kernel_f64, const unsigned char* color_lut, const float* bilateral_table,
                                            unsigned char* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!canvas || !styled || !out) return fail_arg(MSTG_E_BADARG, "app_local_style_finish: null canvas, styled or out pointer");
-    int rc = ap_shape("app_local_style_finish", N, H, W);
-    if (rc == MSTG_OK && auto_select) rc = ap_fits_lds("app_local_style_finish", H, W);
+    int rc = check_shape_16x64("app_local_style_finish", N, H, W);
+    if (rc == MSTG_OK && auto_select) rc = fits_hysteresis_lds("app_local_style_finish", H, W, "with auto_select ");
     if (rc != MSTG_OK) return rc;
     if (auto_select && !kernel_f64) return fail_arg(MSTG_E_BADARG, "app_local_style_finish: auto_select needs the 21-tap kernel");
     if (smooth && !bilateral_table) return fail_arg(MSTG_E_BADARG, "app_local_style_finish: smooth needs the bilateral table");
@@ -541,9 +475,9 @@ extern "C" int mstg_app_local_style_finish(const unsigned char* canvas, const un
     if (((uintptr_t)workspace & 15) || ((uintptr_t)kernel_f64 & 7) || ((uintptr_t)bilateral_table & 3))
         return fail_arg(MSTG_E_ALIGN, "app_local_style_finish: workspace not 16-byte, kernel not 8-byte or bilateral table not 4-byte aligned");
     const size_t px = (size_t)N * H * W, nb = px * 3;
-    if (ap_overlap(out, nb, canvas, nb) || ap_overlap(out, nb, styled, nb) || ap_overlap(out, nb, workspace, ws.total) ||
-        (auto_select && ap_overlap(out, nb, kernel_f64, sizeof(double) * AE_TAPS)) || (color_lut && ap_overlap(out, nb, color_lut, 768)) ||
-        (smooth && ap_overlap(out, nb, bilateral_table, sizeof(float) * MSTG_BILATERAL_TABLE_FLOATS)))
+    if (overlaps(out, nb, canvas, nb) || overlaps(out, nb, styled, nb) || overlaps(out, nb, workspace, ws.total) ||
+        (auto_select && overlaps(out, nb, kernel_f64, sizeof(double) * AE_TAPS)) || (color_lut && overlaps(out, nb, color_lut, 768)) ||
+        (smooth && overlaps(out, nb, bilateral_table, sizeof(float) * MSTG_BILATERAL_TABLE_FLOATS)))
         return fail_arg(MSTG_E_BADARG, "app_local_style_finish: out overlaps an input, a table or the workspace");
     unsigned char* base = (unsigned char*)workspace;
     double* weight = (double*)(base + ws.weight);

@@ -20,9 +20,9 @@
 //    wave idles for 3 of the 2 * radius + 4 steps.  Within a row a lane slides along j = -jmax(i) .. jmax(i): one LDS read of a
 //    packed pixel serves four taps.  The row is stored de-interleaved (column e at (e & 3) * pitch + (e >> 2)) so that the lanes of
 //    a wave, which read columns 4 apart, hit consecutive banks.  i and j are the same for the whole wave: the space weight,
-//    indexed by i * i + j * j, is a scalar load and the loop does not diverge.  Per tap the arithmetic of standard_bilateral_kernel:
-//    v_sad_u8, one LDS gather of the colour weight, one rounded product, wsum, three __fmaf_rn; the tap order per pixel is the
-//    definition's (i, then j).
+//    indexed by i * i + j * j, is a scalar load and the loop does not diverge.  Per tap bilateral_tap (u8_image.h), as in
+//    standard_bilateral_kernel: v_sad_u8, one LDS gather of the colour weight, one rounded product, wsum, three __fmaf_rn; the tap
+//    order per pixel is the definition's (i, then j).
 // H  cb_blur_row_kernel    one thread per pixel: the float64 row pass of cv2.GaussianBlur on the three channels, left to right.
 // B  cb_detail_blend_kernel one thread per pixel: the column pass (centre, then the nearest pair first), detail = orig - blurred,
 //    ((img * w_img) + (orig * alpha)) + (detail * beta), clip, truncate.  Contraction off in both.
@@ -31,7 +31,7 @@
 // floating-point order everywhere, no atomics: bit-reproducible and independent of N.
 #include <cmath>
 
-#include "common.h"
+#include "u8_image.h"
 
 namespace mstg {
 
@@ -45,34 +45,6 @@ constexpr int BW_PITCH = (BW_ROW + 3) / 4;   // de-interleaved: four runs of thi
 constexpr int BW_COLOR = MSTG_BILATERAL_COLOR_WEIGHTS;
 static_assert(BW_TH * WAVE == CB_THREADS && 2 * CB_THREADS >= BW_ROW, "a wave per band row; two columns of the LDS row per thread");
 static_assert(MSTG_BILATERAL_WIDE_TABLE_FLOATS == BW_COLOR + BW_RMAX * BW_RMAX + 1, "colour weights, then space weights by i*i + j*j");
-
-// cv2.BORDER_REFLECT_101 (d c b | a b c d | c b a), for any distance from the array; n == 1 gives 0
-__device__ __forceinline__ int cb_reflect101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
-__device__ __forceinline__ unsigned cb_load_px(const unsigned char* p) { return (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16; }
-
-// four pixels (packed words, 24 bits each) -> the 12 bytes at p; n = how many of the four exist
-__device__ __forceinline__ void cb_store4(unsigned char* p, const unsigned* v, int n) {
-    if (n >= 4 && ((uintptr_t)p & 3) == 0) {
-        unsigned* q = reinterpret_cast<unsigned*>(p);
-        q[0] = v[0] | v[1] << 24;
-        q[1] = v[1] >> 8 | v[2] << 16;
-        q[2] = v[2] >> 16 | v[3] << 8;
-        return;
-    }
-    for (int k = 0; k < 4; ++k)
-        if (k < n) {
-            p[3 * k] = (unsigned char)(v[k] & 0xffu);
-            p[3 * k + 1] = (unsigned char)((v[k] >> 8) & 0xffu);
-            p[3 * k + 2] = (unsigned char)((v[k] >> 16) & 0xffu);
-        }
-}
 
 // ---- E: the block edges ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CB_THREADS) void cb_edge_kernel(const unsigned char* __restrict__ in, const unsigned short* __restrict__ tab,
@@ -93,8 +65,8 @@ __global__ __launch_bounds__(CB_THREADS) void cb_edge_kernel(const unsigned char
     int ys[3], xs[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        ys[k] = cb_reflect101(y + k - 1, H);
-        xs[k] = cb_reflect101(x + k - 1, W);
+        ys[k] = reflect101(y + k - 1, H);
+        xs[k] = reflect101(x + k - 1, W);
     }
     float a[3][3], b[3][3];
 #pragma unroll
@@ -205,9 +177,7 @@ __global__ __launch_bounds__(CB_THREADS) void cb_bilateral_wide_kernel(const uns
     __shared__ float color[BW_COLOR];
     const int tid = threadIdx.x;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & (WAVE - 1);
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * BW_TH, x0 = tx * BW_TW;
+    const auto [n, y0, x0] = tile_of<BW_TH, BW_TW>(tiles, tiles_x);
     const unsigned char* img = in + (size_t)n * H * W * 3;
     const int R = radius, rowlen = BW_TW + 2 * R;
     for (int e = tid; e < BW_COLOR; e += CB_THREADS) color[e] = table[e];
@@ -215,7 +185,7 @@ __global__ __launch_bounds__(CB_THREADS) void cb_bilateral_wide_kernel(const uns
     // the two columns of the LDS row this thread stages at every step: byte offsets of their mirrored source columns
     int soff[2];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) soff[k] = cb_reflect101(x0 - R + min(tid + k * CB_THREADS, rowlen - 1), W) * 3;
+    for (int k = 0; k < 2; ++k) soff[k] = reflect101(x0 - R + min(tid + k * CB_THREADS, rowlen - 1), W) * 3;
     const int d0 = bw_index(tid), d1 = bw_index(tid + CB_THREADS);
     const bool two = tid + CB_THREADS < rowlen;  // tid < rowlen always: rowlen >= 258
     const int py = y0 + wv, pxx = x0 + lane * BW_PX;
@@ -225,22 +195,22 @@ __global__ __launch_bounds__(CB_THREADS) void cb_bilateral_wide_kernel(const uns
 #pragma unroll
     for (int p = 0; p < BW_PX; ++p) {
         wsum[p] = s0[p] = s1[p] = s2[p] = 0.f;
-        ctr[p] = active ? cb_load_px(img + ((size_t)py * W + min(pxx + p, W - 1)) * 3) : 0u;
+        ctr[p] = active ? load_px(img + ((size_t)py * W + min(pxx + p, W - 1)) * 3) : 0u;
     }
     const int steps = 2 * R + min(BW_TH, H - y0);  // the last row of the band that exists needs input rows up to its own + R
     {
-        const unsigned char* src = img + (size_t)cb_reflect101(y0 - R, H) * W * 3;
-        rowbuf[0][d0] = cb_load_px(src + soff[0]);
-        if (two) rowbuf[0][d1] = cb_load_px(src + soff[1]);
+        const unsigned char* src = img + (size_t)reflect101(y0 - R, H) * W * 3;
+        rowbuf[0][d0] = load_px(src + soff[0]);
+        if (two) rowbuf[0][d1] = load_px(src + soff[1]);
     }
     __syncthreads();
     for (int s = 0; s < steps; ++s) {
         const bool more = s + 1 < steps;
         unsigned nxt0 = 0, nxt1 = 0;
         if (more) {  // the next input row: in flight while this one is used
-            const unsigned char* src = img + (size_t)cb_reflect101(y0 - R + s + 1, H) * W * 3;
-            nxt0 = cb_load_px(src + soff[0]);
-            nxt1 = cb_load_px(src + soff[1]);
+            const unsigned char* src = img + (size_t)reflect101(y0 - R + s + 1, H) * W * 3;
+            nxt0 = load_px(src + soff[0]);
+            nxt1 = load_px(src + soff[1]);
         }
         const int i = s - R - wv;  // the tap row of this wave: the same for all its lanes
         if (active && i >= -R && i <= R) {
@@ -256,14 +226,7 @@ __global__ __launch_bounds__(CB_THREADS) void cb_bilateral_wide_kernel(const uns
                 const float sp = space[i2 + j * j];
                 const unsigned q[BW_PX] = {q0, q1, q2, q3};
 #pragma unroll
-                for (int p = 0; p < BW_PX; ++p) {
-                    const unsigned t = __builtin_amdgcn_sad_u8(q[p], ctr[p], 0u);  // |b - b0| + |g - g0| + |r - r0| <= 765
-                    const float w = sp * color[t];
-                    wsum[p] += w;
-                    s0[p] = __fmaf_rn((float)(q[p] & 0xffu), w, s0[p]);
-                    s1[p] = __fmaf_rn((float)((q[p] >> 8) & 0xffu), w, s1[p]);
-                    s2[p] = __fmaf_rn((float)((q[p] >> 16) & 0xffu), w, s2[p]);
-                }
+                for (int p = 0; p < BW_PX; ++p) bilateral_tap(q[p], ctr[p], sp, color, wsum[p], s0[p], s1[p], s2[p]);
                 q0 = q1;
                 q1 = q2;
                 q2 = q3;
@@ -280,13 +243,11 @@ __global__ __launch_bounds__(CB_THREADS) void cb_bilateral_wide_kernel(const uns
     unsigned o[BW_PX];
 #pragma unroll
     for (int p = 0; p < BW_PX; ++p) {
-        const float inv = __fdiv_rn(1.0f, wsum[p]);  // wsum >= 1: the centre tap weighs 1
-        const unsigned b0 = (unsigned)fminf(fmaxf(__builtin_rintf(s0[p] * inv), 0.f), 255.f);
-        const unsigned b1 = (unsigned)fminf(fmaxf(__builtin_rintf(s1[p] * inv), 0.f), 255.f);
-        const unsigned b2 = (unsigned)fminf(fmaxf(__builtin_rintf(s2[p] * inv), 0.f), 255.f);
+        unsigned b0, b1, b2;
+        bilateral_bytes(wsum[p], s0[p], s1[p], s2[p], b0, b1, b2);
         o[p] = b0 | b1 << 8 | b2 << 16;
     }
-    cb_store4(out + (size_t)n * H * W * 3 + ((size_t)py * W + pxx) * 3, o, W - pxx);
+    store_px4(out + (size_t)n * H * W * 3 + ((size_t)py * W + pxx) * 3, o, W - pxx);
 }
 
 // ---- H, B: the detail blend -----------------------------------------------------------------------------------------------------
@@ -303,7 +264,7 @@ __global__ __launch_bounds__(CB_THREADS) void cb_blur_row_kernel(const unsigned 
     double t[3] = {0.0, 0.0, 0.0};
     for (int j = 0; j < ksize; ++j) {  // left to right
         int sx = x + j - r;
-        if ((unsigned)sx >= (unsigned)W) sx = cb_reflect101(sx, W);
+        if ((unsigned)sx >= (unsigned)W) sx = reflect101(sx, W);
         const unsigned char* p = line + (size_t)sx * 3;
         const double kj = taps[j];
 #pragma unroll
@@ -335,8 +296,8 @@ __global__ __launch_bounds__(CB_THREADS) void cb_detail_blend_kernel(const unsig
     double t[3] = {kc * c0[0], kc * c0[1], kc * c0[2]};
     for (int j = 1; j <= r; ++j) {  // the nearest pair first
         int ya = y + j, yb = y - j;
-        if (ya >= H) ya = cb_reflect101(ya, H);
-        if (yb < 0) yb = cb_reflect101(yb, H);
+        if (ya >= H) ya = reflect101(ya, H);
+        if (yb < 0) yb = reflect101(yb, H);
         const double* pa = plane + ((size_t)ya * W + x) * 3;
         const double* pb = plane + ((size_t)yb * W + x) * 3;
         const double kj = taps[r + j];
@@ -360,21 +321,10 @@ __global__ __launch_bounds__(CB_THREADS) void cb_detail_blend_kernel(const unsig
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 // 0 = fine, else the error code (message set)
 static int cb_shape(const char* who, int N, int H, int W) {
-    char msg[200];
-    if (N < 1 || H < 1 || W < 1) {
-        snprintf(msg, sizeof(msg), "%s: N = %d, H = %d, W = %d: need at least one image of at least one pixel", who, N, H, W);
-        return fail_arg(MSTG_E_BADARG, msg);
-    }
-    if ((long long)H * W * 3 >= (1ll << 31)) {
-        snprintf(msg, sizeof(msg), "%s: H * W * 3 = %lld does not fit 31 bits", who, (long long)H * W * 3);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    const long long blocks = ((long long)N * H * W + CB_THREADS - 1) / CB_THREADS;  // the finest grid: a thread per pixel
-    if (blocks >= (1ll << 31)) {
-        snprintf(msg, sizeof(msg), "%s: N * H * W = %lld, more than 2^31 - 1 workgroups in one launch", who, (long long)N * H * W);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    return MSTG_OK;
+    const int rc = check_extent(who, N, H, W);
+    if (rc != MSTG_OK) return rc;
+    const long long px = (long long)N * H * W;  // the finest grid: a thread per pixel
+    return check_grid(who, (px + CB_THREADS - 1) / CB_THREADS, 31, "N * H * W", px);
 }
 
 static int cb_kernel_size(const char* who, int k) {
@@ -412,12 +362,6 @@ static int cb_ksize(const char* who, int ksize) {
     return fail_arg(MSTG_E_UNSUPPORTED, msg);
 }
 
-static bool cb_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-static size_t cb_align(size_t b) { return (b + 15) & ~(size_t)15; }
 static dim3 cb_grid(size_t px) { return dim3((unsigned)cdivz(px, (size_t)CB_THREADS)); }
 
 static int cb_mask(const unsigned char* in, int N, int H, int W, const unsigned short* lab, float threshold, int k, unsigned char* edge,
@@ -473,11 +417,11 @@ static CbWorkspace cb_workspace(int N, int H, int W, bool with_orig) {
     const size_t px = (size_t)N * H * W;
     CbWorkspace w;
     w.edge = 0;
-    w.mask = cb_align(px);
-    w.sums = w.mask + cb_align(px);  // the window's row sums (12 bytes a pixel), then the blur's row pass (24 bytes a pixel)
-    w.corrected = w.sums + cb_align(px * 3 * (with_orig ? sizeof(double) : sizeof(unsigned)));
-    w.smoothed = w.corrected + cb_align(px * 3);
-    w.total = w.smoothed + (with_orig ? cb_align(px * 3) : 0);
+    w.mask = align16(px);
+    w.sums = w.mask + align16(px);  // the window's row sums (12 bytes a pixel), then the blur's row pass (24 bytes a pixel)
+    w.corrected = w.sums + align16(px * 3 * (with_orig ? sizeof(double) : sizeof(unsigned)));
+    w.smoothed = w.corrected + align16(px * 3);
+    w.total = w.smoothed + (with_orig ? align16(px * 3) : 0);
     return w;
 }
 
@@ -539,8 +483,8 @@ extern "C" int mstg_color_block_mask(const unsigned char* in, int N, int H, int 
     const size_t px = (size_t)N * H * W;
     if (!workspace || workspace_bytes < px) return fail_arg(MSTG_E_WORKSPACE, "color_block_mask: workspace too small (N * H * W bytes)");
     if ((uintptr_t)lab_table & 1) return fail_arg(MSTG_E_ALIGN, "color_block_mask: table not 2-byte aligned");
-    if (cb_overlap(mask, px, in, px * 3) || cb_overlap(mask, px, workspace, px) || cb_overlap(mask, px, lab_table, 2 * MSTG_LAB_TABLE_U16) ||
-        cb_overlap(workspace, px, in, px * 3) || cb_overlap(workspace, px, lab_table, 2 * MSTG_LAB_TABLE_U16))
+    if (overlaps(mask, px, in, px * 3) || overlaps(mask, px, workspace, px) || overlaps(mask, px, lab_table, 2 * MSTG_LAB_TABLE_U16) ||
+        overlaps(workspace, px, in, px * 3) || overlaps(workspace, px, lab_table, 2 * MSTG_LAB_TABLE_U16))
         return fail_arg(MSTG_E_BADARG, "color_block_mask: mask or workspace overlaps an input, the table or each other");
     return cb_mask(in, N, H, W, lab_table, threshold, kernel_size, (unsigned char*)workspace, mask, (hipStream_t)stream);
 }
@@ -554,8 +498,8 @@ extern "C" int mstg_color_correct_u8(const unsigned char* in, const unsigned cha
     const size_t px = (size_t)N * H * W, nb = px * 3, need = nb * sizeof(unsigned);
     if (!workspace || workspace_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "color_correct_u8: workspace too small (N * H * W * 12 bytes)");
     if ((uintptr_t)workspace & 3) return fail_arg(MSTG_E_ALIGN, "color_correct_u8: workspace not 4-byte aligned");
-    if (cb_overlap(out, nb, in, nb) || cb_overlap(out, nb, mask, px) || cb_overlap(out, nb, workspace, need) ||
-        cb_overlap(workspace, need, in, nb) || cb_overlap(workspace, need, mask, px))
+    if (overlaps(out, nb, in, nb) || overlaps(out, nb, mask, px) || overlaps(out, nb, workspace, need) ||
+        overlaps(workspace, need, in, nb) || overlaps(workspace, need, mask, px))
         return fail_arg(MSTG_E_BADARG, "color_correct_u8: out or workspace overlaps an input or each other");
     return cb_correct(in, mask, N, H, W, radius, (unsigned*)workspace, out, (hipStream_t)stream);
 }
@@ -570,7 +514,7 @@ extern "C" int mstg_bilateral_wide_u8(const unsigned char* in, int N, int H, int
     if (rc != MSTG_OK) return rc;
     if ((uintptr_t)table & 3) return fail_arg(MSTG_E_ALIGN, "bilateral_wide_u8: table not 4-byte aligned");
     const size_t nb = (size_t)N * H * W * 3;
-    if (cb_overlap(out, nb, in, nb) || cb_overlap(out, nb, table, sizeof(float) * MSTG_BILATERAL_WIDE_TABLE_FLOATS))
+    if (overlaps(out, nb, in, nb) || overlaps(out, nb, table, sizeof(float) * MSTG_BILATERAL_WIDE_TABLE_FLOATS))
         return fail_arg(MSTG_E_BADARG, "bilateral_wide_u8: out overlaps the input or the table (the filter reads neighbours of every pixel)");
     return cb_wide(in, N, H, W, radius, table, out, (hipStream_t)stream);
 }
@@ -587,9 +531,9 @@ extern "C" int mstg_detail_blend_u8(const unsigned char* img, const unsigned cha
     if (!workspace || workspace_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "detail_blend_u8: workspace too small (N * H * W * 24 bytes)");
     if (((uintptr_t)workspace & 7) || ((uintptr_t)kernel_f64 & 7))
         return fail_arg(MSTG_E_ALIGN, "detail_blend_u8: workspace or kernel not 8-byte aligned");
-    if (cb_overlap(out, nb, img, nb) || cb_overlap(out, nb, orig, nb) || cb_overlap(out, nb, workspace, need) ||
-        cb_overlap(out, nb, kernel_f64, sizeof(double) * ksize) || cb_overlap(workspace, need, img, nb) || cb_overlap(workspace, need, orig, nb) ||
-        cb_overlap(workspace, need, kernel_f64, sizeof(double) * ksize))
+    if (overlaps(out, nb, img, nb) || overlaps(out, nb, orig, nb) || overlaps(out, nb, workspace, need) ||
+        overlaps(out, nb, kernel_f64, sizeof(double) * ksize) || overlaps(workspace, need, img, nb) || overlaps(workspace, need, orig, nb) ||
+        overlaps(workspace, need, kernel_f64, sizeof(double) * ksize))
         return fail_arg(MSTG_E_BADARG, "detail_blend_u8: out or workspace overlaps an input, the kernel or each other");
     return cb_blend(img, orig, N, H, W, kernel_f64, ksize, w_img, alpha, beta, (double*)workspace, out, (hipStream_t)stream);
 }
@@ -618,11 +562,11 @@ extern "C" int mstg_color_block_fix(const unsigned char* in, const unsigned char
     if (((uintptr_t)workspace & 15) || ((uintptr_t)bilateral_table & 3) || ((uintptr_t)kernel_f64 & 7) || ((uintptr_t)lab_table & 1))
         return fail_arg(MSTG_E_ALIGN, "color_block_fix: workspace not 16-byte, bilateral table not 4-byte, kernel not 8-byte or Lab table not 2-byte aligned");
     const size_t nb = (size_t)N * H * W * 3;
-    if (cb_overlap(out, nb, in, nb) || (orig && cb_overlap(out, nb, orig, nb)) || cb_overlap(out, nb, workspace, ws.total) ||
-        cb_overlap(out, nb, lab_table, 2 * MSTG_LAB_TABLE_U16) ||
-        cb_overlap(out, nb, bilateral_table, sizeof(float) * MSTG_BILATERAL_WIDE_TABLE_FLOATS) ||
-        (orig && cb_overlap(out, nb, kernel_f64, sizeof(double) * ksize)) || cb_overlap(workspace, ws.total, in, nb) ||
-        (orig && cb_overlap(workspace, ws.total, orig, nb)))
+    if (overlaps(out, nb, in, nb) || (orig && overlaps(out, nb, orig, nb)) || overlaps(out, nb, workspace, ws.total) ||
+        overlaps(out, nb, lab_table, 2 * MSTG_LAB_TABLE_U16) ||
+        overlaps(out, nb, bilateral_table, sizeof(float) * MSTG_BILATERAL_WIDE_TABLE_FLOATS) ||
+        (orig && overlaps(out, nb, kernel_f64, sizeof(double) * ksize)) || overlaps(workspace, ws.total, in, nb) ||
+        (orig && overlaps(workspace, ws.total, orig, nb)))
         return fail_arg(MSTG_E_BADARG, "color_block_fix: out or the workspace overlaps an input or a table");
     unsigned char* base = (unsigned char*)workspace;
     unsigned char* mask = base + ws.mask;

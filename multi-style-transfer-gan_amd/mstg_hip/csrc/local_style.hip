@@ -28,7 +28,7 @@
 // Everything before the Gaussian is integer, nothing uses floating-point atomics, so the three outputs are bit-reproducible.
 //
 // D  local_style_finish_kernel   the blend with that map and the two finishing steps of the mode (:342-352), one workgroup of 256
-//    threads per 32 x 64 tile: x = orig * (1 - w) + styled * w as blend_u8_kernel forms it (float64, every product and the sum
+//    threads per 32 x 64 tile: x = orig * (1 - w) + styled * w as blend_byte (u8_image.h) forms it (float64, products and sum
 //    rounded); enhance_colors = cv2.convertScaleAbs(x, alpha=1.1, beta=5) restated as narrow to float32, ONE fused multiply-add,
 //    |.|, round half to even, saturate; smooth = smooth_transitions(radius=3): boundary = dilate != erode of the detail mask over
 //    the 9 x 9 window clipped to the image (two iterations of a 5 x 5 box), the 8-bit GaussianBlur 7 x 7 (sigma 0) in OpenCV's
@@ -37,7 +37,7 @@
 //    is neutral) and the 16-bit horizontally filtered rows in LDS; without smooth the kernel is the per-pixel blend and uses no
 //    LDS.  Integer after the colour step, no atomics: bit-reproducible.  Restated from the definitions (include/mstg_hip.h),
 //    not compared with an OpenCV binary.
-#include "common.h"
+#include "u8_image.h"
 
 namespace mstg {
 
@@ -73,6 +73,7 @@ __global__ __launch_bounds__(LA_THREADS) void local_style_prepare_kernel(const u
     __shared__ unsigned short mag[LA_MH * LA_MW];
     __shared__ int wave_cnt[LA_THREADS / WAVE];
     const int tid = threadIdx.x;
+    // tile_of (u8_image.h) written out: with the call the compiler schedules this kernel's third loop differently
     const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
     const int y0 = ty * LA_TH, x0 = tx * LA_TW;
@@ -258,9 +259,7 @@ __global__ __launch_bounds__(LC_THREADS) void local_style_weights_kernel(const u
     __shared__ unsigned char ed[LC_EH * LC_EW];
     __shared__ double col[LC_TH * LC_EW];
     const int tid = threadIdx.x;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * LC_TH, x0 = tx * LC_TW;
+    const auto [n, y0, x0] = tile_of<LC_TH, LC_TW>(tiles, tiles_x);
     const size_t plane = (size_t)n * H * W;
     const unsigned char* e_img = edge + plane;
     for (int e = tid; e < LC_EH * LC_EW; e += LC_THREADS) {
@@ -304,34 +303,16 @@ constexpr int LD_EH = LD_TH + 2 * LD_RB, LD_EW = LD_TW + 2 * LD_RB;  // enhanced
 constexpr int LD_EWP = LD_TW + 8;  // its row pitch in LDS: the item of the last four columns reads three whole dwords
 constexpr int LD_DH = LD_TH + 2 * LD_RM, LD_DW = LD_TW + 2 * LD_RM;  // detail patch
 static_assert(LD_EWP >= LD_EW && LD_EWP % 4 == 0 && LD_DW == LD_TW + 8 && LD_TW % 4 == 0, "dword passes of the finish kernel");
-// OpenCV's table for getGaussianKernel(7, sigma <= 0), {0.03125, 0.109375, 0.21875, 0.28125, ...}, in 8.8 fixed point; sum 256
-__device__ __forceinline__ int ld_tap(int k) {
-    constexpr int t[7] = {8, 28, 56, 72, 56, 28, 8};
-    return t[k];
-}
 
-// cv2.BORDER_REFLECT_101 (d c b | a b c d | c b a), for any distance from the array; n == 1 gives 0
-__device__ __forceinline__ int reflect101_index(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
-// One channel of one pixel: the blend in float64 as blend_u8_kernel forms it, then either its clip and truncation or the
-// convertScaleAbs restatement.
+// One channel of one pixel: the blend in float64, then either its clip and truncation (blend_byte, u8_image.h) or the
+// convertScaleAbs restatement on the unclipped sum.
 template <bool ENHANCE>
 __device__ __forceinline__ unsigned char finish_channel(unsigned char o, unsigned char s, double w0, double w1) {
 #pragma clang fp contract(off)  // numpy rounds each product and the sum
+    if (!ENHANCE) return (unsigned char)blend_byte(o, s, w0, w1);
     const double a = (double)o * w0;
     const double b = (double)s * w1;
-    double r = a + b;
-    if (!ENHANCE) {
-        r = r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r);
-        if (!(r == r)) r = 0.0;  // a NaN weight: keep the byte defined, as blend_u8_kernel does
-        return (unsigned char)r;
-    }
+    const double r = a + b;
     float t = fabsf(__builtin_fmaf((float)r, 1.1f, 5.0f));  // the one fused multiply-add of the definition
     if (!(t == t)) t = 0.f;                                 // a NaN weight: keep the byte defined here too
     t = fminf(__builtin_rintf(t), 255.f);                   // round half to even, saturate (t >= 0)
@@ -346,9 +327,7 @@ __global__ __launch_bounds__(LD_THREADS) void local_style_finish_kernel(const un
                                                                         int tiles, unsigned char* __restrict__ out) {
 #pragma clang fp contract(off)
     const int tid = threadIdx.x;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * LD_TH, x0 = tx * LD_TW;
+    const auto [n, y0, x0] = tile_of<LD_TH, LD_TW>(tiles, tiles_x);
     const size_t plane = (size_t)n * H * W;
     const unsigned char* c_img = canvas + plane * 3;
     const unsigned char* s_img = styled + plane * 3;
@@ -375,8 +354,8 @@ __global__ __launch_bounds__(LD_THREADS) void local_style_finish_kernel(const un
     for (int e = tid; e < LD_EH * LD_EW; e += LD_THREADS) {
         const int r = e / LD_EW, c = e - r * LD_EW;
         int sy = y0 - LD_RB + r, sx = x0 - LD_RB + c;
-        if ((unsigned)sy >= (unsigned)H) sy = reflect101_index(sy, H);
-        if ((unsigned)sx >= (unsigned)W) sx = reflect101_index(sx, W);
+        if ((unsigned)sy >= (unsigned)H) sy = reflect101(sy, H);
+        if ((unsigned)sx >= (unsigned)W) sx = reflect101(sx, W);
         const size_t i = (size_t)sy * W + sx;
         const double w1 = w_img[i], w0 = 1.0 - w1;
 #pragma unroll
@@ -414,7 +393,7 @@ __global__ __launch_bounds__(LD_THREADS) void local_style_finish_kernel(const un
         for (int j = 0; j < 4; ++j) {
             int sum = 0;
 #pragma unroll
-            for (int k = 0; k < 7; ++k) sum += ld_tap(k) * px[j + k];
+            for (int k = 0; k <= 2 * LD_RB; ++k) sum += gauss_q8_tap<2 * LD_RB + 1>(k) * px[j + k];
             o[j] = (unsigned short)sum;
         }
         *reinterpret_cast<uint2*>(&hz[row * LD_TW + c]) = make_uint2((unsigned)o[0] | (unsigned)o[1] << 16, (unsigned)o[2] | (unsigned)o[3] << 16);
@@ -436,7 +415,7 @@ __global__ __launch_bounds__(LD_THREADS) void local_style_finish_kernel(const un
                 const unsigned short* hp = &hz[(ch * LD_EH + r) * LD_TW + c];
                 int sum = 0;
 #pragma unroll
-                for (int k = 0; k < 7; ++k) sum += ld_tap(k) * (int)hp[k * LD_TW];
+                for (int k = 0; k <= 2 * LD_RB; ++k) sum += gauss_q8_tap<2 * LD_RB + 1>(k) * (int)hp[k * LD_TW];
                 o = (o + ((sum + 32768) >> 16)) >> 1;
             }
             o_img[i + ch] = (unsigned char)o;
@@ -444,36 +423,8 @@ __global__ __launch_bounds__(LD_THREADS) void local_style_finish_kernel(const un
     }
 }
 
-// 0 = fine, else the error code (message set)
-static int ls_shape(const char* who, int N, int H, int W) {
-    char msg[200];
-    if (N < 1 || H < 1 || W < 1) {
-        snprintf(msg, sizeof(msg), "%s: N = %d, H = %d, W = %d: need at least one image of at least one pixel", who, N, H, W);
-        return fail_arg(MSTG_E_BADARG, msg);
-    }
-    if ((long long)H * W * 3 >= (1ll << 31)) {
-        snprintf(msg, sizeof(msg), "%s: H * W * 3 = %lld does not fit 31 bits", who, (long long)H * W * 3);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    const long long blocks = (long long)N * cdiv(H, LC_TH) * cdiv(W, LC_TW);  // the finer of the two tilings
-    if (blocks >= (1ll << 24)) {
-        snprintf(msg, sizeof(msg), "%s: N * tiles = %lld, more than 2^24 - 1 workgroups in one launch", who, blocks);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    return MSTG_OK;
-}
-
-static int ls_fits_lds(const char* who, int H, int W) {
-    if ((long long)H * W > LS_MAX_PIXELS) {
-        char msg[200];
-        snprintf(msg, sizeof(msg), "%s: a %d x %d image has %lld pixels; the hysteresis keeps one byte per pixel in LDS and takes at most %d",
-                 who, H, W, (long long)H * W, LS_MAX_PIXELS);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    return MSTG_OK;
-}
-
-static size_t ls_align(size_t b) { return (b + 15) & ~(size_t)15; }
+// ---- host side: every check returns 0 = fine, else the error code (message set) -----------------------------------------------
+static_assert(LC_TH == 16 && LC_TW == 64, "check_shape_16x64 counts the tiles of the weights kernel, the finer of the two tilings");
 
 static int ls_prepare(const unsigned char* canvas, int N, int H, int W, unsigned char* state, unsigned char* sky, int* sky_count,
                       unsigned char* gray, hipStream_t st) {
@@ -536,9 +487,27 @@ static int ls_flags(const char* who, int enhance, int smooth) {
     return MSTG_OK;
 }
 
-static bool ls_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
+// the layout of the workspace of mstg_local_style_weight_map and, with the weight map and the detail mask, mstg_local_style_enhanced
+struct LsWorkspace {
+    size_t weight, state, sky, edge, detail, count, total;
+};
+static LsWorkspace ls_workspace(int N, int H, int W, bool enhanced) {
+    const size_t px = (size_t)N * H * W, plane = align16(px);
+    LsWorkspace w;
+    w.weight = 0;
+    w.state = enhanced ? align16(px * sizeof(double)) : 0;
+    w.sky = w.state + plane;
+    w.edge = w.sky + plane;
+    w.detail = w.edge + plane;
+    w.count = w.detail + (enhanced ? plane : 0);
+    w.total = w.count + align16((size_t)N * sizeof(int));
+    return w;
+}
+
+// shape and hysteresis limit of an entry that runs, or sizes the workspace of, the whole chain
+static int ls_chain_shape(const char* who, int N, int H, int W) {
+    const int rc = check_shape_16x64(who, N, H, W);
+    return rc != MSTG_OK ? rc : fits_hysteresis_lds(who, H, W, "");
 }
 
 }  // namespace mstg
@@ -546,14 +515,14 @@ static bool ls_overlap(const void* a, size_t na, const void* b, size_t nb) {
 using namespace mstg;
 
 extern "C" size_t mstg_local_style_workspace_bytes(int N, int H, int W) {
-    if (ls_shape("local_style_workspace_bytes", N, H, W) != MSTG_OK || ls_fits_lds("local_style_workspace_bytes", H, W) != MSTG_OK) return 0;
-    return 3 * ls_align((size_t)N * H * W) + ls_align((size_t)N * sizeof(int));
+    if (ls_chain_shape("local_style_workspace_bytes", N, H, W) != MSTG_OK) return 0;
+    return ls_workspace(N, H, W, false).total;
 }
 
 extern "C" int mstg_local_style_prepare(const unsigned char* canvas, int N, int H, int W, unsigned char* state, unsigned char* sky,
                                         int* sky_count, unsigned char* gray, void* stream) {
     if (!canvas || !state || !sky || !sky_count) return fail_arg(MSTG_E_BADARG, "local_style_prepare: null canvas, state, sky or count pointer");
-    const int rc = ls_shape("local_style_prepare", N, H, W);
+    const int rc = check_shape_16x64("local_style_prepare", N, H, W);
     if (rc != MSTG_OK) return rc;
     if ((uintptr_t)sky_count & 3) return fail_arg(MSTG_E_ALIGN, "local_style_prepare: sky_count not 4-byte aligned");
     return ls_prepare(canvas, N, H, W, state, sky, sky_count, gray, (hipStream_t)stream);
@@ -561,8 +530,7 @@ extern "C" int mstg_local_style_prepare(const unsigned char* canvas, int N, int 
 
 extern "C" int mstg_local_style_hysteresis(const unsigned char* state, int N, int H, int W, unsigned char* edge, void* stream) {
     if (!state || !edge) return fail_arg(MSTG_E_BADARG, "local_style_hysteresis: null state or edge pointer");
-    int rc = ls_shape("local_style_hysteresis", N, H, W);
-    if (rc == MSTG_OK) rc = ls_fits_lds("local_style_hysteresis", H, W);
+    const int rc = ls_chain_shape("local_style_hysteresis", N, H, W);
     if (rc != MSTG_OK) return rc;
     return ls_hysteresis(state, N, H, W, edge, (hipStream_t)stream);
 }
@@ -571,7 +539,7 @@ extern "C" int mstg_local_style_weights(const unsigned char* edge, const unsigne
                                         double w_base, double w_sky, double w_detail, double* weight_map, unsigned char* detail,
                                         void* stream) {
     if (!edge || !sky || !sky_count || !weight_map) return fail_arg(MSTG_E_BADARG, "local_style_weights: null edge, sky, count or map pointer");
-    const int rc = ls_shape("local_style_weights", N, H, W);
+    const int rc = check_shape_16x64("local_style_weights", N, H, W);
     if (rc != MSTG_OK) return rc;
     if (((uintptr_t)weight_map & 7) || ((uintptr_t)sky_count & 3))
         return fail_arg(MSTG_E_ALIGN, "local_style_weights: weight_map not 8-byte or sky_count not 4-byte aligned");
@@ -581,18 +549,15 @@ extern "C" int mstg_local_style_weights(const unsigned char* edge, const unsigne
 extern "C" int mstg_local_style_weight_map(const unsigned char* canvas, int N, int H, int W, double w_base, double w_sky, double w_detail,
                                            double* weight_map, void* workspace, size_t workspace_bytes, void* stream) {
     if (!canvas || !weight_map) return fail_arg(MSTG_E_BADARG, "local_style_weight_map: null canvas or map pointer");
-    int rc = ls_shape("local_style_weight_map", N, H, W);
-    if (rc == MSTG_OK) rc = ls_fits_lds("local_style_weight_map", H, W);
+    int rc = ls_chain_shape("local_style_weight_map", N, H, W);
     if (rc != MSTG_OK) return rc;
-    const size_t plane = ls_align((size_t)N * H * W);
-    if (!workspace || workspace_bytes < 3 * plane + ls_align((size_t)N * sizeof(int)))
-        return fail_arg(MSTG_E_WORKSPACE, "local_style_weight_map: workspace too small");
+    const LsWorkspace ws = ls_workspace(N, H, W, false);
+    if (!workspace || workspace_bytes < ws.total) return fail_arg(MSTG_E_WORKSPACE, "local_style_weight_map: workspace too small");
     if (((uintptr_t)workspace & 15) || ((uintptr_t)weight_map & 7))
         return fail_arg(MSTG_E_ALIGN, "local_style_weight_map: workspace not 16-byte or weight_map not 8-byte aligned");
-    unsigned char* state = (unsigned char*)workspace;
-    unsigned char* sky = state + plane;
-    unsigned char* edge = sky + plane;
-    int* count = (int*)(edge + plane);
+    unsigned char* base = (unsigned char*)workspace;
+    unsigned char *state = base + ws.state, *sky = base + ws.sky, *edge = base + ws.edge;
+    int* count = (int*)(base + ws.count);
     hipStream_t st = (hipStream_t)stream;
     rc = ls_prepare(canvas, N, H, W, state, sky, count, nullptr, st);
     if (rc == MSTG_OK) rc = ls_hysteresis(state, N, H, W, edge, st);
@@ -604,46 +569,40 @@ extern "C" int mstg_local_style_finish(const unsigned char* canvas, const unsign
                                        const unsigned char* detail, int N, int H, int W, int enhance_colors, int smooth, unsigned char* out,
                                        void* stream) {
     if (!canvas || !styled || !weight_map || !out) return fail_arg(MSTG_E_BADARG, "local_style_finish: null canvas, styled, map or out pointer");
-    int rc = ls_shape("local_style_finish", N, H, W);
+    int rc = check_shape_16x64("local_style_finish", N, H, W);
     if (rc == MSTG_OK) rc = ls_flags("local_style_finish", enhance_colors, smooth);
     if (rc != MSTG_OK) return rc;
     if (smooth && !detail) return fail_arg(MSTG_E_BADARG, "local_style_finish: smooth needs the detail mask");
     if ((uintptr_t)weight_map & 7) return fail_arg(MSTG_E_ALIGN, "local_style_finish: weight_map not 8-byte aligned");
     const size_t px = (size_t)N * H * W;
-    if (ls_overlap(out, px * 3, canvas, px * 3) || ls_overlap(out, px * 3, styled, px * 3) || ls_overlap(out, px * 3, weight_map, px * 8) ||
-        (smooth && ls_overlap(out, px * 3, detail, px)))
+    if (overlaps(out, px * 3, canvas, px * 3) || overlaps(out, px * 3, styled, px * 3) || overlaps(out, px * 3, weight_map, px * 8) ||
+        (smooth && overlaps(out, px * 3, detail, px)))
         return fail_arg(MSTG_E_BADARG, "local_style_finish: out overlaps an input (the smoothing reads neighbours of every pixel)");
     return ls_finish(canvas, styled, weight_map, detail, N, H, W, enhance_colors, smooth, out, (hipStream_t)stream);
 }
 
 extern "C" size_t mstg_local_style_enhanced_workspace_bytes(int N, int H, int W) {
-    if (ls_shape("local_style_enhanced_workspace_bytes", N, H, W) != MSTG_OK ||
-        ls_fits_lds("local_style_enhanced_workspace_bytes", H, W) != MSTG_OK)
-        return 0;
-    const size_t px = (size_t)N * H * W;
-    return ls_align(px * sizeof(double)) + 4 * ls_align(px) + ls_align((size_t)N * sizeof(int));
+    if (ls_chain_shape("local_style_enhanced_workspace_bytes", N, H, W) != MSTG_OK) return 0;
+    return ls_workspace(N, H, W, true).total;
 }
 
 extern "C" int mstg_local_style_enhanced(const unsigned char* canvas, const unsigned char* styled, int N, int H, int W, double w_base,
                                          double w_sky, double w_detail, int enhance_colors, int smooth, unsigned char* out, void* workspace,
                                          size_t workspace_bytes, void* stream) {
     if (!canvas || !styled || !out) return fail_arg(MSTG_E_BADARG, "local_style_enhanced: null canvas, styled or out pointer");
-    int rc = ls_shape("local_style_enhanced", N, H, W);
-    if (rc == MSTG_OK) rc = ls_fits_lds("local_style_enhanced", H, W);
+    int rc = ls_chain_shape("local_style_enhanced", N, H, W);
     if (rc == MSTG_OK) rc = ls_flags("local_style_enhanced", enhance_colors, smooth);
     if (rc != MSTG_OK) return rc;
-    const size_t px = (size_t)N * H * W, plane = ls_align(px), mapb = ls_align(px * sizeof(double));
-    const size_t need = mapb + 4 * plane + ls_align((size_t)N * sizeof(int));
-    if (!workspace || workspace_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "local_style_enhanced: workspace too small");
+    const LsWorkspace ws = ls_workspace(N, H, W, true);
+    if (!workspace || workspace_bytes < ws.total) return fail_arg(MSTG_E_WORKSPACE, "local_style_enhanced: workspace too small");
     if ((uintptr_t)workspace & 15) return fail_arg(MSTG_E_ALIGN, "local_style_enhanced: workspace not 16-byte aligned");
-    if (ls_overlap(out, px * 3, canvas, px * 3) || ls_overlap(out, px * 3, styled, px * 3) || ls_overlap(out, px * 3, workspace, need))
+    const size_t px = (size_t)N * H * W;
+    if (overlaps(out, px * 3, canvas, px * 3) || overlaps(out, px * 3, styled, px * 3) || overlaps(out, px * 3, workspace, ws.total))
         return fail_arg(MSTG_E_BADARG, "local_style_enhanced: out overlaps an input or the workspace");
-    double* wm = (double*)workspace;
-    unsigned char* state = (unsigned char*)workspace + mapb;
-    unsigned char* sky = state + plane;
-    unsigned char* edge = sky + plane;
-    unsigned char* det = edge + plane;
-    int* count = (int*)(det + plane);
+    unsigned char* base = (unsigned char*)workspace;
+    double* wm = (double*)(base + ws.weight);
+    unsigned char *state = base + ws.state, *sky = base + ws.sky, *edge = base + ws.edge, *det = base + ws.detail;
+    int* count = (int*)(base + ws.count);
     hipStream_t st = (hipStream_t)stream;
     rc = ls_prepare(canvas, N, H, W, state, sky, count, nullptr, st);
     if (rc == MSTG_OK) rc = ls_hysteresis(state, N, H, W, edge, st);

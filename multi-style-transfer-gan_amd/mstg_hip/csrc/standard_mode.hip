@@ -6,7 +6,7 @@
 //
 // M  standard_median3_kernel     one workgroup of 256 threads per 16 x 64 tile, four pixels of a row per thread.  The tile + 1 pixel
 //    of halo (BORDER_REPLICATE) goes to LDS as one packed word per pixel; with BLEND the word is formed from the styled image and
-//    the canvas as blend_u8_kernel forms it (float64, two rounded products, one rounded sum, clip, truncate), halo pixels from
+//    the canvas as blend_byte (u8_image.h) forms it (float64, two rounded products, one rounded sum, clip, truncate), halo pixels from
 //    their own replicated source coordinates.  Per channel the median of the 9 samples through a 19-exchange network: integers.
 // B  standard_bilateral_kernel   the hot one: same tiling, halo = radius (4 at d = 9) with BORDER_REFLECT_101 source coordinates,
 //    the 768 colour weights in LDS (a gather per tap), the space weights read at compile-time indices of the table (scalar loads).
@@ -21,7 +21,7 @@
 // No atomics, no floating-point reduction across threads: every output is a function of the inputs alone, bit-reproducible.
 #include <cmath>
 
-#include "common.h"
+#include "u8_image.h"
 
 namespace mstg {
 
@@ -31,48 +31,10 @@ constexpr int SG_TH = 32, SG_TW = 64;  // tile of the blur
 constexpr int SM_COLOR = MSTG_BILATERAL_COLOR_WEIGHTS, SM_TAPS = MSTG_BILATERAL_MAX_TAPS;
 static_assert(SM_TW == 64 && SM_TH * (SM_TW / 4) == SM_THREADS, "one item of four pixels per thread");
 
-// cv2.BORDER_REFLECT_101 (d c b | a b c d | c b a), for any distance from the array; n == 1 gives 0
-__device__ __forceinline__ int sm_reflect101(int i, int n) {
-    if (n == 1) return 0;
-    const int p = 2 * n - 2;
-    i %= p;
-    if (i < 0) i += p;
-    return i < n ? i : p - i;
-}
-
-__device__ __forceinline__ unsigned sm_load_px(const unsigned char* p) { return (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16; }
-
-// one byte of styled * (1 - r) + canvas * r as blend_u8_kernel forms it
-__device__ __forceinline__ unsigned sm_blend_byte(unsigned s, unsigned c, double w0, double w1) {
-#pragma clang fp contract(off)  // numpy rounds each product and the sum
-    const double a = (double)s * w0;
-    const double b = (double)c * w1;
-    double r = a + b;
-    r = r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r);
-    if (!(r == r)) r = 0.0;  // a NaN ratio: keep the byte defined, as blend_u8_kernel does
-    return (unsigned)(unsigned char)r;
-}
-
+// a packed pixel of styled * (1 - r) + canvas * r, every byte through blend_byte
 __device__ __forceinline__ unsigned sm_blend_px(unsigned s, unsigned c, double w0, double w1) {
-    return sm_blend_byte(s & 0xffu, c & 0xffu, w0, w1) | sm_blend_byte((s >> 8) & 0xffu, (c >> 8) & 0xffu, w0, w1) << 8 |
-           sm_blend_byte((s >> 16) & 0xffu, (c >> 16) & 0xffu, w0, w1) << 16;
-}
-
-// four pixels (packed words, 24 bits each) -> the 12 bytes at p; n = how many of the four exist
-__device__ __forceinline__ void sm_store4(unsigned char* p, const unsigned* v, int n) {
-    if (n >= 4 && ((uintptr_t)p & 3) == 0) {
-        unsigned* q = reinterpret_cast<unsigned*>(p);
-        q[0] = v[0] | v[1] << 24;
-        q[1] = v[1] >> 8 | v[2] << 16;
-        q[2] = v[2] >> 16 | v[3] << 8;
-        return;
-    }
-    for (int k = 0; k < 4; ++k)
-        if (k < n) {
-            p[3 * k] = (unsigned char)(v[k] & 0xffu);
-            p[3 * k + 1] = (unsigned char)((v[k] >> 8) & 0xffu);
-            p[3 * k + 2] = (unsigned char)((v[k] >> 16) & 0xffu);
-        }
+    return blend_byte(s & 0xffu, c & 0xffu, w0, w1) | blend_byte((s >> 8) & 0xffu, (c >> 8) & 0xffu, w0, w1) << 8 |
+           blend_byte((s >> 16) & 0xffu, (c >> 16) & 0xffu, w0, w1) << 16;
 }
 
 __device__ __forceinline__ void sm_sort2(int& a, int& b) {
@@ -100,16 +62,14 @@ __global__ __launch_bounds__(SM_THREADS) void standard_median3_kernel(const unsi
     constexpr int PH = SM_TH + 2, PW = SM_TW + 2;
     __shared__ unsigned px[PH * PW];
     const int tid = threadIdx.x;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * SM_TH, x0 = tx * SM_TW;
+    const auto [n, y0, x0] = tile_of<SM_TH, SM_TW>(tiles, tiles_x);
     const size_t base = (size_t)n * H * W * 3;
     for (int e = tid; e < PH * PW; e += SM_THREADS) {
         const int r = e / PW, c = e - r * PW;
         const int sy = min(max(y0 - 1 + r, 0), H - 1), sx = min(max(x0 - 1 + c, 0), W - 1);  // BORDER_REPLICATE
         const size_t i = base + ((size_t)sy * W + sx) * 3;
-        unsigned v = sm_load_px(in + i);
-        if (BLEND) v = sm_blend_px(v, sm_load_px(canvas + i), w0, w1);
+        unsigned v = load_px(in + i);
+        if (BLEND) v = sm_blend_px(v, load_px(canvas + i), w0, w1);
         px[e] = v;
     }
     __syncthreads();
@@ -132,7 +92,7 @@ __global__ __launch_bounds__(SM_THREADS) void standard_median3_kernel(const unsi
         }
         o[p] = v;
     }
-    sm_store4(out + base + ((size_t)py * W + pxx) * 3, o, W - pxx);
+    store_px4(out + base + ((size_t)py * W + pxx) * 3, o, W - pxx);
 }
 
 template <int R, bool LUT>
@@ -145,20 +105,18 @@ __global__ __launch_bounds__(SM_THREADS) void standard_bilateral_kernel(const un
     __shared__ float color[SM_COLOR];
     __shared__ unsigned char slut[LUT ? 768 : 4];
     const int tid = threadIdx.x;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * SM_TH, x0 = tx * SM_TW;
+    const auto [n, y0, x0] = tile_of<SM_TH, SM_TW>(tiles, tiles_x);
     const size_t base = (size_t)n * H * W * 3;
     for (int e = tid; e < SM_COLOR; e += SM_THREADS) {
         color[e] = table[e];
-        if (LUT) slut[e] = lut[e];
+        if (LUT) slut[e] = lut[e];  // the two tables have the same length: one loop stages both (stage_lut768 would be a second one)
     }
     for (int e = tid; e < PH * PW; e += SM_THREADS) {
         const int r = e / PW, c = e - r * PW;
         int sy = y0 - R + r, sx = x0 - R + c;
-        if ((unsigned)sy >= (unsigned)H) sy = sm_reflect101(sy, H);  // also for rows of the tile below the image: any valid pixel
-        if ((unsigned)sx >= (unsigned)W) sx = sm_reflect101(sx, W);
-        px[e] = sm_load_px(in + base + ((size_t)sy * W + sx) * 3);
+        if ((unsigned)sy >= (unsigned)H) sy = reflect101(sy, H);  // also for rows of the tile below the image: any valid pixel
+        if ((unsigned)sx >= (unsigned)W) sx = reflect101(sx, W);
+        px[e] = load_px(in + base + ((size_t)sy * W + sx) * 3);
     }
     __syncthreads();
     const int r = tid >> 4, c = (tid & 15) * 4;
@@ -183,24 +141,14 @@ __global__ __launch_bounds__(SM_THREADS) void standard_bilateral_kernel(const un
             const float sp = table[SM_COLOR + k];
             ++k;
 #pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                const unsigned q = row[p + R + j];
-                const unsigned t = __builtin_amdgcn_sad_u8(q, ctr[p], 0u);  // |b - b0| + |g - g0| + |r - r0| <= 765
-                const float w = sp * color[t];
-                wsum[p] += w;
-                s0[p] = __fmaf_rn((float)(q & 0xffu), w, s0[p]);
-                s1[p] = __fmaf_rn((float)((q >> 8) & 0xffu), w, s1[p]);
-                s2[p] = __fmaf_rn((float)((q >> 16) & 0xffu), w, s2[p]);
-            }
+            for (int p = 0; p < 4; ++p) bilateral_tap(row[p + R + j], ctr[p], sp, color, wsum[p], s0[p], s1[p], s2[p]);
         }
     }
     unsigned o[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const float inv = __fdiv_rn(1.0f, wsum[p]);  // wsum >= 1: the centre tap weighs 1
-        unsigned b0 = (unsigned)fminf(fmaxf(__builtin_rintf(s0[p] * inv), 0.f), 255.f);
-        unsigned b1 = (unsigned)fminf(fmaxf(__builtin_rintf(s1[p] * inv), 0.f), 255.f);
-        unsigned b2 = (unsigned)fminf(fmaxf(__builtin_rintf(s2[p] * inv), 0.f), 255.f);
+        unsigned b0, b1, b2;
+        bilateral_bytes(wsum[p], s0[p], s1[p], s2[p], b0, b1, b2);
         if (LUT) {
             b0 = slut[b0];
             b1 = slut[256 + b1];
@@ -208,7 +156,7 @@ __global__ __launch_bounds__(SM_THREADS) void standard_bilateral_kernel(const un
         }
         o[p] = b0 | b1 << 8 | b2 << 16;
     }
-    sm_store4(out + base + ((size_t)py * W + pxx) * 3, o, W - pxx);
+    store_px4(out + base + ((size_t)py * W + pxx) * 3, o, W - pxx);
 }
 
 // a and canvas: flat byte streams of nbytes (a multiple of 3: byte b belongs to channel b % 3); 12 bytes per thread
@@ -220,7 +168,7 @@ __global__ __launch_bounds__(SM_THREADS) void standard_pointwise_kernel(const un
     __shared__ unsigned char slut[LUT ? 768 : 4];
     const int tid = threadIdx.x;
     if (LUT) {
-        for (int e = tid; e < 768; e += SM_THREADS) slut[e] = lut[e];
+        stage_lut768<SM_THREADS>(lut, slut, tid);
         __syncthreads();
     }
     const size_t b0 = ((size_t)blockIdx.x * SM_THREADS + tid) * 12;
@@ -236,7 +184,7 @@ __global__ __launch_bounds__(SM_THREADS) void standard_pointwise_kernel(const un
 #pragma unroll
         for (int k = 0; k < 12; ++k) {
             unsigned v = (va[k >> 2] >> (8 * (k & 3))) & 0xffu;
-            if (BLEND) v = sm_blend_byte(v, (vc[k >> 2] >> (8 * (k & 3))) & 0xffu, w0, w1);
+            if (BLEND) v = blend_byte(v, (vc[k >> 2] >> (8 * (k & 3))) & 0xffu, w0, w1);
             if (LUT) v = slut[256 * (k % 3) + v];
             vo[k >> 2] |= v << (8 * (k & 3));
         }
@@ -247,17 +195,10 @@ __global__ __launch_bounds__(SM_THREADS) void standard_pointwise_kernel(const un
     const int cnt = (int)(nbytes - b0 < 12 ? nbytes - b0 : 12);
     for (int k = 0; k < cnt; ++k) {
         unsigned v = a[b0 + k];
-        if (BLEND) v = sm_blend_byte(v, canvas[b0 + k], w0, w1);
+        if (BLEND) v = blend_byte(v, canvas[b0 + k], w0, w1);
         if (LUT) v = slut[256 * (k % 3) + v];
         out[b0 + k] = (unsigned char)v;
     }
-}
-
-// OpenCV's table for getGaussianKernel(2 R + 1, sigma <= 0) in 8.8 fixed point; every row sums to 256
-template <int R>
-__device__ __forceinline__ int sg_tap(int k) {
-    constexpr int t[3][7] = {{64, 128, 64, 0, 0, 0, 0}, {16, 64, 96, 64, 16, 0, 0}, {8, 28, 56, 72, 56, 28, 8}};
-    return t[R - 1][k];
 }
 
 template <int R>
@@ -268,16 +209,14 @@ __global__ __launch_bounds__(SM_THREADS) void standard_gaussian_kernel(const uns
     __shared__ unsigned char en[3 * EH * EWP];
     __shared__ unsigned short hz[3 * EH * SG_TW];  // the horizontally filtered rows, exact (<= 65280)
     const int tid = threadIdx.x;
-    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * SG_TH, x0 = tx * SG_TW;
+    const auto [n, y0, x0] = tile_of<SG_TH, SG_TW>(tiles, tiles_x);
     const size_t base = (size_t)n * H * W * 3;
     for (int e = tid; e < EH * EW; e += SM_THREADS) {
         const int r = e / EW, c = e - r * EW;
         int sy = y0 - R + r, sx = x0 - R + c;
-        if ((unsigned)sy >= (unsigned)H) sy = sm_reflect101(sy, H);
-        if ((unsigned)sx >= (unsigned)W) sx = sm_reflect101(sx, W);
-        const unsigned v = sm_load_px(in + base + ((size_t)sy * W + sx) * 3);
+        if ((unsigned)sy >= (unsigned)H) sy = reflect101(sy, H);
+        if ((unsigned)sx >= (unsigned)W) sx = reflect101(sx, W);
+        const unsigned v = load_px(in + base + ((size_t)sy * W + sx) * 3);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) en[(ch * EH + r) * EWP + c] = (unsigned char)((v >> (8 * ch)) & 0xffu);
     }
@@ -287,7 +226,7 @@ __global__ __launch_bounds__(SM_THREADS) void standard_gaussian_kernel(const uns
         const unsigned char* p = &en[row * EWP + c];
         int sum = 0;
 #pragma unroll
-        for (int k = 0; k <= 2 * R; ++k) sum += sg_tap<R>(k) * (int)p[k];
+        for (int k = 0; k <= 2 * R; ++k) sum += gauss_q8_tap<2 * R + 1>(k) * (int)p[k];
         hz[e] = (unsigned short)sum;
     }
     __syncthreads();
@@ -304,35 +243,17 @@ __global__ __launch_bounds__(SM_THREADS) void standard_gaussian_kernel(const uns
                 const unsigned short* hp = &hz[(ch * EH + r) * SG_TW + c + p];
                 int sum = 0;
 #pragma unroll
-                for (int k = 0; k <= 2 * R; ++k) sum += sg_tap<R>(k) * (int)hp[k * SG_TW];
+                for (int k = 0; k <= 2 * R; ++k) sum += gauss_q8_tap<2 * R + 1>(k) * (int)hp[k * SG_TW];
                 v |= (unsigned)((sum + 32768) >> 16) << (8 * ch);
             }
             o[p] = v;
         }
-        sm_store4(out + base + ((size_t)py * W + pxx) * 3, o, W - pxx);
+        store_px4(out + base + ((size_t)py * W + pxx) * 3, o, W - pxx);
     }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-// 0 = fine, else the error code (message set)
-static int sm_shape(const char* who, int N, int H, int W) {
-    char msg[200];
-    if (N < 1 || H < 1 || W < 1) {
-        snprintf(msg, sizeof(msg), "%s: N = %d, H = %d, W = %d: need at least one image of at least one pixel", who, N, H, W);
-        return fail_arg(MSTG_E_BADARG, msg);
-    }
-    if ((long long)H * W * 3 >= (1ll << 31)) {
-        snprintf(msg, sizeof(msg), "%s: H * W * 3 = %lld does not fit 31 bits", who, (long long)H * W * 3);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    const long long blocks = (long long)N * cdiv(H, SM_TH) * cdiv(W, SM_TW);  // the finest tiling; the point-wise grid is coarser
-    if (blocks >= (1ll << 24)) {
-        snprintf(msg, sizeof(msg), "%s: N * tiles = %lld, more than 2^24 - 1 workgroups in one launch", who, blocks);
-        return fail_arg(MSTG_E_UNSUPPORTED, msg);
-    }
-    return MSTG_OK;
-}
-
+// every check returns 0 = fine, else the error code (message set); the shape check is check_shape_16x64 (SM_TH x SM_TW)
 static int sm_d(const char* who, int d) {
     if (d == 3 || d == 5 || d == 7 || d == 9) return MSTG_OK;
     char msg[240];
@@ -357,13 +278,6 @@ static int sm_level(const char* who, int level) {
              who, level, 2 * level + 1);
     return fail_arg(MSTG_E_UNSUPPORTED, msg);
 }
-
-static bool sm_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-static size_t sm_align(size_t b) { return (b + 15) & ~(size_t)15; }
 
 static int sm_median(const unsigned char* in, const unsigned char* canvas, double w0, double w1, int N, int H, int W, unsigned char* out,
                      hipStream_t st) {
@@ -400,13 +314,11 @@ static int sm_bilateral(const unsigned char* in, int d, const float* table, cons
     return MSTG_OK;
 }
 
-static bool sm_al4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
 // the blend (canvas != NULL) and / or the lookup (lut != NULL) on N * H * W * 3 bytes; neither = a copy
 static int sm_pointwise(const unsigned char* a, const unsigned char* canvas, double w0, double w1, const unsigned char* lut, size_t nbytes,
                         unsigned char* out, hipStream_t st) {
     const dim3 grid((unsigned)cdivz(nbytes, (size_t)SM_THREADS * 12)), block(SM_THREADS);
-    const int aligned = sm_al4(a) && sm_al4(out) && (!canvas || sm_al4(canvas));
+    const int aligned = aligned4(a) && aligned4(out) && (!canvas || aligned4(canvas));
     if (canvas && lut)
         MSTG_LAUNCH((standard_pointwise_kernel<true, true>), grid, block, 0, st, a, canvas, w0, w1, lut, nbytes, aligned, out);
     else if (canvas)
@@ -482,10 +394,10 @@ extern "C" int mstg_standard_color_lut(int model_type, unsigned char* lut) {
 
 extern "C" int mstg_median3_u8(const unsigned char* in, int N, int H, int W, unsigned char* out, void* stream) {
     if (!in || !out) return fail_arg(MSTG_E_BADARG, "median3_u8: null in or out pointer");
-    const int rc = sm_shape("median3_u8", N, H, W);
+    const int rc = check_shape_16x64("median3_u8", N, H, W);
     if (rc != MSTG_OK) return rc;
     const size_t nb = (size_t)N * H * W * 3;
-    if (sm_overlap(out, nb, in, nb)) return fail_arg(MSTG_E_BADARG, "median3_u8: out overlaps the input (the filter reads neighbours of every pixel)");
+    if (overlaps(out, nb, in, nb)) return fail_arg(MSTG_E_BADARG, "median3_u8: out overlaps the input (the filter reads neighbours of every pixel)");
     return sm_median(in, nullptr, 0.0, 0.0, N, H, W, out, (hipStream_t)stream);
 }
 
@@ -493,21 +405,21 @@ extern "C" int mstg_bilateral_u8(const unsigned char* in, int N, int H, int W, i
     int rc = sm_d("bilateral_u8", d);  // first: the refusal does not depend on the buffers
     if (rc != MSTG_OK) return rc;
     if (!in || !out || !table) return fail_arg(MSTG_E_BADARG, "bilateral_u8: null in, table or out pointer");
-    rc = sm_shape("bilateral_u8", N, H, W);
+    rc = check_shape_16x64("bilateral_u8", N, H, W);
     if (rc != MSTG_OK) return rc;
     if ((uintptr_t)table & 3) return fail_arg(MSTG_E_ALIGN, "bilateral_u8: table not 4-byte aligned");
     const size_t nb = (size_t)N * H * W * 3;
-    if (sm_overlap(out, nb, in, nb) || sm_overlap(out, nb, table, sizeof(float) * MSTG_BILATERAL_TABLE_FLOATS))
+    if (overlaps(out, nb, in, nb) || overlaps(out, nb, table, sizeof(float) * MSTG_BILATERAL_TABLE_FLOATS))
         return fail_arg(MSTG_E_BADARG, "bilateral_u8: out overlaps the input or the table (the filter reads neighbours of every pixel)");
     return sm_bilateral(in, d, table, nullptr, N, H, W, out, (hipStream_t)stream);
 }
 
 extern "C" int mstg_lut_u8(const unsigned char* in, int N, int H, int W, const unsigned char* lut, unsigned char* out, void* stream) {
     if (!in || !out || !lut) return fail_arg(MSTG_E_BADARG, "lut_u8: null in, lut or out pointer");
-    const int rc = sm_shape("lut_u8", N, H, W);
+    const int rc = check_shape_16x64("lut_u8", N, H, W);
     if (rc != MSTG_OK) return rc;
     const size_t nb = (size_t)N * H * W * 3;
-    if (sm_overlap(out, nb, lut, 768) || sm_overlap(out, nb, in, nb)) return fail_arg(MSTG_E_BADARG, "lut_u8: out overlaps the input or the table");
+    if (overlaps(out, nb, lut, 768) || overlaps(out, nb, in, nb)) return fail_arg(MSTG_E_BADARG, "lut_u8: out overlaps the input or the table");
     return sm_pointwise(in, nullptr, 0.0, 0.0, lut, nb, out, (hipStream_t)stream);
 }
 
@@ -520,16 +432,16 @@ extern "C" int mstg_gaussian_u8(const unsigned char* in, int N, int H, int W, in
     int rc = sm_level("gaussian_u8", ksize / 2);
     if (rc != MSTG_OK) return rc;
     if (!in || !out) return fail_arg(MSTG_E_BADARG, "gaussian_u8: null in or out pointer");
-    rc = sm_shape("gaussian_u8", N, H, W);
+    rc = check_shape_16x64("gaussian_u8", N, H, W);
     if (rc != MSTG_OK) return rc;
     const size_t nb = (size_t)N * H * W * 3;
-    if (sm_overlap(out, nb, in, nb)) return fail_arg(MSTG_E_BADARG, "gaussian_u8: out overlaps the input (the filter reads neighbours of every pixel)");
+    if (overlaps(out, nb, in, nb)) return fail_arg(MSTG_E_BADARG, "gaussian_u8: out overlaps the input (the filter reads neighbours of every pixel)");
     return sm_gaussian(in, N, H, W, ksize / 2, out, (hipStream_t)stream);
 }
 
 extern "C" size_t mstg_standard_finish_workspace_bytes(int N, int H, int W) {
-    if (sm_shape("standard_finish_workspace_bytes", N, H, W) != MSTG_OK) return 0;
-    return 2 * sm_align((size_t)N * H * W * 3);
+    if (check_shape_16x64("standard_finish_workspace_bytes", N, H, W) != MSTG_OK) return 0;
+    return 2 * align16((size_t)N * H * W * 3);
 }
 
 extern "C" int mstg_standard_finish(const unsigned char* canvas, const unsigned char* styled, int N, int H, int W, double one_minus_ratio,
@@ -541,15 +453,15 @@ extern "C" int mstg_standard_finish(const unsigned char* canvas, const unsigned 
     const bool blend = blend_ratio > 0;  // the reference skips the step otherwise (:820)
     if (!styled || !out || (blend && !canvas)) return fail_arg(MSTG_E_BADARG, "standard_finish: null styled, out or (with a blend) canvas pointer");
     if (fix_blocks && !bilateral_table) return fail_arg(MSTG_E_BADARG, "standard_finish: fix_blocks needs the bilateral table");
-    rc = sm_shape("standard_finish", N, H, W);
+    rc = check_shape_16x64("standard_finish", N, H, W);
     if (rc != MSTG_OK) return rc;
-    const size_t nb = (size_t)N * H * W * 3, plane = sm_align(nb);
+    const size_t nb = (size_t)N * H * W * 3, plane = align16(nb);
     if (!workspace || workspace_bytes < 2 * plane) return fail_arg(MSTG_E_WORKSPACE, "standard_finish: workspace too small");
     if (((uintptr_t)workspace & 15) || ((uintptr_t)bilateral_table & 3))
         return fail_arg(MSTG_E_ALIGN, "standard_finish: workspace not 16-byte or bilateral table not 4-byte aligned");
-    if (sm_overlap(out, nb, styled, nb) || (blend && sm_overlap(out, nb, canvas, nb)) || sm_overlap(out, nb, workspace, 2 * plane) ||
-        (fix_blocks && sm_overlap(out, nb, bilateral_table, sizeof(float) * MSTG_BILATERAL_TABLE_FLOATS)) ||
-        (color_lut && sm_overlap(out, nb, color_lut, 768)))
+    if (overlaps(out, nb, styled, nb) || (blend && overlaps(out, nb, canvas, nb)) || overlaps(out, nb, workspace, 2 * plane) ||
+        (fix_blocks && overlaps(out, nb, bilateral_table, sizeof(float) * MSTG_BILATERAL_TABLE_FLOATS)) ||
+        (color_lut && overlaps(out, nb, color_lut, 768)))
         return fail_arg(MSTG_E_BADARG, "standard_finish: out overlaps an input, a table or the workspace");
     unsigned char* wa = (unsigned char*)workspace;
     unsigned char* wb = wa + plane;

@@ -1,0 +1,152 @@
+// Device and host helpers shared by the 8-bit image filters (local_style.hip, standard_mode.hip, app_local_style.hip,
+// color_blocks.hip).  Every device helper is a bit-exact restatement of an OpenCV / numpy definition; a primitive that more than one
+// of those files uses is defined HERE, once, so that a fix reaches every user ("Shared 8-bit image helpers").  All
+// __forceinline__: a kernel compiles to the code it had with the body written out in place.
+#pragma once
+#include "common.h"
+
+namespace mstg {
+
+// ---- device side ----------------------------------------------------------------------------------------------------------------
+// cv2.BORDER_REFLECT_101 (d c b | a b c d | c b a), for any distance from the array; n == 1 gives 0
+__device__ __forceinline__ int reflect101(int i, int n) {
+    if (n == 1) return 0;
+    const int p = 2 * n - 2;
+    i %= p;
+    if (i < 0) i += p;
+    return i < n ? i : p - i;
+}
+
+// one pixel of an interleaved 3-channel image as a packed word: channel ch in bits 8 ch .. 8 ch + 7
+__device__ __forceinline__ unsigned load_px(const unsigned char* p) { return (unsigned)p[0] | (unsigned)p[1] << 8 | (unsigned)p[2] << 16; }
+
+// four pixels (packed words, 24 bits each) -> the 12 bytes at p; n = how many of the four exist
+__device__ __forceinline__ void store_px4(unsigned char* p, const unsigned* v, int n) {
+    if (n >= 4 && ((uintptr_t)p & 3) == 0) {
+        unsigned* q = reinterpret_cast<unsigned*>(p);
+        q[0] = v[0] | v[1] << 24;
+        q[1] = v[1] >> 8 | v[2] << 16;
+        q[2] = v[2] >> 16 | v[3] << 8;
+        return;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (k < n) {
+            p[3 * k] = (unsigned char)(v[k] & 0xffu);
+            p[3 * k + 1] = (unsigned char)((v[k] >> 8) & 0xffu);
+            p[3 * k + 2] = (unsigned char)((v[k] >> 16) & 0xffu);
+        }
+}
+
+// One byte of a * wa + b * wb as numpy forms it on float64 arrays and as blend_u8_kernel (image.hip) restates it: two rounded
+// products, one rounded sum, clip to [0, 255], truncate (astype(uint8)).
+__device__ __forceinline__ unsigned blend_byte(unsigned a, unsigned b, double wa, double wb) {
+#pragma clang fp contract(off)  // numpy rounds each product and the sum (the pragma is lexical: it does not follow an inlined call)
+    const double x = (double)a * wa;
+    const double y = (double)b * wb;
+    double r = x + y;
+    r = r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r);
+    if (!(r == r)) r = 0.0;  // a NaN weight: keep the byte defined, as blend_u8_kernel does
+    return (unsigned)(unsigned char)r;
+}
+
+// One tap of cv2.bilateralFilter on 8-bit, 3-channel pixels (packed words): q = the neighbour, ctr = the centre, sp = the space
+// weight of the tap, color = the colour weights in LDS.  float32; the definition rounds the weight product, the three channel
+// sums go through __fmaf_rn (the only fused operations).
+__device__ __forceinline__ void bilateral_tap(unsigned q, unsigned ctr, float sp, const float* color, float& wsum, float& s0, float& s1,
+                                              float& s2) {
+#pragma clang fp contract(off)
+    const unsigned t = __builtin_amdgcn_sad_u8(q, ctr, 0u);  // |b - b0| + |g - g0| + |r - r0| <= 765
+    const float w = sp * color[t];
+    wsum += w;
+    s0 = __fmaf_rn((float)(q & 0xffu), w, s0);
+    s1 = __fmaf_rn((float)((q >> 8) & 0xffu), w, s1);
+    s2 = __fmaf_rn((float)((q >> 16) & 0xffu), w, s2);
+}
+
+// The tail of cv2.bilateralFilter: one IEEE division 1 / wsum, the three products, round half to even, saturate.
+__device__ __forceinline__ void bilateral_bytes(float wsum, float s0, float s1, float s2, unsigned& b0, unsigned& b1, unsigned& b2) {
+#pragma clang fp contract(off)
+    const float inv = __fdiv_rn(1.0f, wsum);  // wsum >= 1: the centre tap weighs 1
+    b0 = (unsigned)fminf(fmaxf(__builtin_rintf(s0 * inv), 0.f), 255.f);
+    b1 = (unsigned)fminf(fmaxf(__builtin_rintf(s1 * inv), 0.f), 255.f);
+    b2 = (unsigned)fminf(fmaxf(__builtin_rintf(s2 * inv), 0.f), 255.f);
+}
+
+// OpenCV's table for getGaussianKernel(KSIZE, sigma <= 0) in 8.8 fixed point, as its bit-exact 8-bit GaussianBlur uses it; every
+// row sums to 256.  Sizes 3, 5, 7 ({0.25, 0.5, 0.25}, {0.0625, 0.25, 0.375, ...}, {0.03125, 0.109375, 0.21875, 0.28125, ...}) are
+// exact; 15 comes from OpenCV's softfloat generator with error diffusion (include/mstg_hip.h).  The row pass (exact 16-bit sums) and
+// the column pass ((sum + 32768) >> 16) that loop over these taps stay in their kernels: a loop inside a shared function is
+// unrolled before the function is inlined, and the kernels then compile to other code than with the loop in place.
+template <int KSIZE>
+__device__ __forceinline__ int gauss_q8_tap(int k) {
+    static_assert(KSIZE == 3 || KSIZE == 5 || KSIZE == 7 || KSIZE == 15, "the sizes whose 8.8 taps are restated");
+    constexpr int t[4][15] = {{64, 128, 64}, {16, 64, 96, 64, 16}, {8, 28, 56, 72, 56, 28, 8},
+                              {1, 3, 6, 12, 20, 30, 36, 40, 36, 30, 20, 12, 6, 3, 1}};
+    return t[KSIZE == 15 ? 3 : KSIZE / 2 - 1][k];
+}
+
+// Workgroup -> (image, first row, first column of its TH x TW tile); the grid is N * tiles workgroups, tiles_x of them per tile row.
+struct TileOrigin {
+    int n, y0, x0;
+};
+template <int TH, int TW>
+__device__ __forceinline__ TileOrigin tile_of(int tiles, int tiles_x) {
+    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    return {n, ty * TH, tx * TW};
+}
+
+// The colour step's table (three runs of 256 bytes, one per channel) into LDS; the caller places the barrier.
+template <int THREADS>
+__device__ __forceinline__ void stage_lut768(const unsigned char* __restrict__ lut, unsigned char* slut, int tid) {
+    for (int e = tid; e < 768; e += THREADS) slut[e] = lut[e];
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
+// (N, H, W) of a batch of 8-bit images and the launch limit; 0 = fine, else the error code (message set).  blocks = workgroups of
+// the finest grid that any kernel of the entry launches; it must stay below 2^limit_bits.  grid_what / grid_count = how the
+// message names that grid.  The caller forms blocks only after check_extent passed (H * W * 3 < 2^31: no overflow in it).
+inline int check_extent(const char* who, int N, int H, int W) {
+    char msg[200];
+    if (N < 1 || H < 1 || W < 1) {
+        snprintf(msg, sizeof(msg), "%s: N = %d, H = %d, W = %d: need at least one image of at least one pixel", who, N, H, W);
+        return fail_arg(MSTG_E_BADARG, msg);
+    }
+    if ((long long)H * W * 3 >= (1ll << 31)) {
+        snprintf(msg, sizeof(msg), "%s: H * W * 3 = %lld does not fit 31 bits", who, (long long)H * W * 3);
+        return fail_arg(MSTG_E_UNSUPPORTED, msg);
+    }
+    return MSTG_OK;
+}
+inline int check_grid(const char* who, long long blocks, int limit_bits, const char* grid_what, long long grid_count) {
+    if (blocks < (1ll << limit_bits)) return MSTG_OK;
+    char msg[200];
+    snprintf(msg, sizeof(msg), "%s: %s = %lld, more than 2^%d - 1 workgroups in one launch", who, grid_what, grid_count, limit_bits);
+    return fail_arg(MSTG_E_UNSUPPORTED, msg);
+}
+// the shape check of the files whose finest tiling is 16 x 64 pixels a workgroup (a point-wise grid is coarser)
+inline int check_shape_16x64(const char* who, int N, int H, int W) {
+    const int rc = check_extent(who, N, H, W);
+    if (rc != MSTG_OK) return rc;
+    const long long blocks = (long long)N * cdiv(H, 16) * cdiv(W, 64);
+    return check_grid(who, blocks, 24, "N * tiles", blocks);
+}
+
+// cv2.Canny's hysteresis (local_style_hysteresis_kernel) keeps one byte per pixel of an image in LDS; extra = words for the
+// message between "pixels; " and "the hysteresis" (with their trailing blank), or "".
+inline int fits_hysteresis_lds(const char* who, int H, int W, const char* extra) {
+    if ((long long)H * W <= MSTG_LOCAL_STYLE_MAX_PIXELS) return MSTG_OK;
+    char msg[220];
+    snprintf(msg, sizeof(msg), "%s: a %d x %d image has %lld pixels; %sthe hysteresis keeps one byte per pixel in LDS and takes at most %d", who,
+             H, W, (long long)H * W, extra, MSTG_LOCAL_STYLE_MAX_PIXELS);
+    return fail_arg(MSTG_E_UNSUPPORTED, msg);
+}
+
+}  // namespace mstg

@@ -247,16 +247,34 @@ def _local_style_enhanced(canvas, styled, strength, detail, detail_coeff, enhanc
 _std_tables = {}
 
 
+def _device_table(key, device, build):
+    """what ``build()`` returns, with its numpy table on ``device``: built on the host and uploaded once per ``key`` and device.
+    ``build`` returns the table, or (value, table) where a value goes with it."""
+    key = key + (str(device),)
+    if key not in _std_tables:
+        built = build()
+        if isinstance(built, tuple):
+            _std_tables[key] = (built[0], torch.from_numpy(built[1]).to(device))
+        else:
+            _std_tables[key] = torch.from_numpy(built).to(device)
+    return _std_tables[key]
+
+
+def _host_fill(entry, size, dtype, *args, counts=False):
+    """(return value, table): ``size`` zeros of ``dtype`` filled by the host-only C entry ``entry(*args, pointer)``.  An error code
+    raises; with ``counts`` the entry returns a positive count, and 0 is an error as well."""
+    table = np.zeros(size, dtype=dtype)
+    rc = getattr(_lib.load(), entry)(*args, table.ctypes.data)
+    if rc <= 0 or not counts:
+        _lib.check((rc or -1) if counts else rc, entry)
+    return rc, table
+
+
 def _bilateral_table(d, sigma_color, sigma_space, device):
     """the host-built weight tables of ``mstg_bilateral_tables`` on ``device`` (built and uploaded once per parameter set)"""
-    key = ("bilateral", int(d), float(sigma_color), float(sigma_space), str(device))
-    if key not in _std_tables:
-        table = np.zeros(_lib.BILATERAL_COLOR_WEIGHTS + _lib.BILATERAL_MAX_TAPS, dtype=np.float32)
-        taps = _lib.load().mstg_bilateral_tables(int(d), float(sigma_color), float(sigma_space), table.ctypes.data)
-        if taps <= 0:
-            _lib.check(taps or -1, "mstg_bilateral_tables")
-        _std_tables[key] = torch.from_numpy(table).to(device)
-    return _std_tables[key]
+    args, size = (int(d), float(sigma_color), float(sigma_space)), _lib.BILATERAL_COLOR_WEIGHTS + _lib.BILATERAL_MAX_TAPS
+    return _device_table(("bilateral",) + args, device,
+                         lambda: _host_fill("mstg_bilateral_tables", size, np.float32, *args, counts=True)[1])
 
 
 def _standard_model_type(model_type):
@@ -267,12 +285,8 @@ def _standard_model_type(model_type):
 
 def _color_lut(model_type, device):
     """the colour step's three 256-entry tables of ``mstg_standard_color_lut`` on ``device``"""
-    key = ("lut", _standard_model_type(model_type), str(device))
-    if key not in _std_tables:
-        lut = np.zeros(768, dtype=np.uint8)
-        _lib.check(_lib.load().mstg_standard_color_lut(key[1], lut.ctypes.data), "mstg_standard_color_lut")
-        _std_tables[key] = torch.from_numpy(lut).to(device)
-    return _std_tables[key]
+    mt = _standard_model_type(model_type)
+    return _device_table(("lut", mt), device, lambda: _host_fill("mstg_standard_color_lut", 768, np.uint8, mt)[1])
 
 
 def _stage_u8(img, what):
@@ -842,12 +856,8 @@ APP_MODES = ("simple", "enhanced", "advanced")  # the tab's three modes in its o
 
 def _edge_kernel(device):
     """the 21 float64 taps of ``mstg_gaussian_kernel_f64(21, 0)`` on ``device`` (built on the host and uploaded once)"""
-    key = ("edge_kernel", str(device))
-    if key not in _std_tables:
-        k = np.zeros(_lib.APP_EDGE_KSIZE, dtype=np.float64)
-        _lib.check(_lib.load().mstg_gaussian_kernel_f64(_lib.APP_EDGE_KSIZE, 0.0, k.ctypes.data), "mstg_gaussian_kernel_f64")
-        _std_tables[key] = torch.from_numpy(k).to(device)
-    return _std_tables[key]
+    n = _lib.APP_EDGE_KSIZE
+    return _device_table(("edge_kernel",), device, lambda: _host_fill("mstg_gaussian_kernel_f64", n, np.float64, n, 0.0)[1])
 
 
 def app_sky_mask(canvas_u8: torch.Tensor) -> torch.Tensor:
@@ -1047,25 +1057,16 @@ def process_compare(enhanced_model, cyclegan_model, img_u8: torch.Tensor, model_
 # ---- the colour-block repair of improved_smooth.py (csrc/color_blocks.hip) --------------------------------------------------
 def _lab_table(device):
     """the 16-bit gamma, cube-root and coefficient tables of ``mstg_lab_tables`` on ``device`` (built on the host, uploaded once)"""
-    key = ("lab", str(device))
-    if key not in _std_tables:
-        t = np.zeros(_lib.LAB_TABLE_U16, dtype=np.uint16)
-        _lib.check(_lib.load().mstg_lab_tables(t.ctypes.data), "mstg_lab_tables")
-        _std_tables[key] = torch.from_numpy(t.view(np.int16)).to(device)  # the same bits: torch has no uint16 on every build
-    return _std_tables[key]
+    # uploaded as int16, the same bits: torch has no uint16 on every build
+    return _device_table(("lab",), device, lambda: _host_fill("mstg_lab_tables", _lib.LAB_TABLE_U16, np.uint16)[1].view(np.int16))
 
 
 def _bilateral_wide_table(d, sigma_color, sigma_space, device):
     """(radius, table): the host-built weight tables of ``mstg_bilateral_wide_tables`` on ``device`` (once per parameter set); a
     radius above 90 raises, naming it"""
-    key = ("bilateral_wide", int(d), float(sigma_color), float(sigma_space), str(device))
-    if key not in _std_tables:
-        table = np.zeros(_lib.BILATERAL_WIDE_TABLE_FLOATS, dtype=np.float32)
-        radius = _lib.load().mstg_bilateral_wide_tables(int(d), float(sigma_color), float(sigma_space), table.ctypes.data)
-        if radius <= 0:
-            _lib.check(radius or -1, "mstg_bilateral_wide_tables")
-        _std_tables[key] = (radius, torch.from_numpy(table).to(device))
-    return _std_tables[key]
+    args, size = (int(d), float(sigma_color), float(sigma_space)), _lib.BILATERAL_WIDE_TABLE_FLOATS
+    return _device_table(("bilateral_wide",) + args, device,
+                         lambda: _host_fill("mstg_bilateral_wide_tables", size, np.float32, *args, counts=True))
 
 
 def _detail_ksize(sigma):
@@ -1075,12 +1076,8 @@ def _detail_ksize(sigma):
 
 def _detail_kernel(ksize, sigma, device):
     """the float64 taps of ``mstg_gaussian_kernel_f64(ksize, sigma)`` on ``device`` (built on the host and uploaded once)"""
-    key = ("detail_kernel", int(ksize), float(sigma), str(device))
-    if key not in _std_tables:
-        k = np.zeros(int(ksize), dtype=np.float64)
-        _lib.check(_lib.load().mstg_gaussian_kernel_f64(int(ksize), float(sigma), k.ctypes.data), "mstg_gaussian_kernel_f64")
-        _std_tables[key] = torch.from_numpy(k).to(device)
-    return _std_tables[key]
+    args = (int(ksize), float(sigma))
+    return _device_table(("detail_kernel",) + args, device, lambda: _host_fill("mstg_gaussian_kernel_f64", args[0], np.float64, *args)[1])
 
 
 def detect_color_blocks(img: torch.Tensor, threshold=30, kernel_size=11) -> torch.Tensor:
