@@ -875,6 +875,107 @@ int mstg_color_block_fix(const unsigned char* in, const unsigned char* orig /*nu
                          double alpha, double beta, unsigned char* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The SEGMENTATION-DRIVEN LOCAL STYLE of the reference (enhanced_local_style.py:76-292) between the forward pass and the crop, on
+ * the device for N images (N, H, W, 3) uint8 RGB, N images per launch, 64-bit offsets; the segmentation itself (:68) on the host.
+ * The OpenCV, scipy and scikit-image steps are restated from the definitions below, as recalled
+ * (tests/enhanced_local_style_ref.py is the same restatement in numpy); NONE OF THEM HAS BEEN COMPARED WITH AN OPENCV OR
+ * SCIKIT-IMAGE BINARY; the Gaussian of step 2 is compared with scipy itself, bit for bit (tests/test_enhanced_local_style_cpu.py).
+ * No floating-point atomics: the statistics are integer sums (64-bit integer atomics, any order gives the same bits), everything
+ * else has a fixed order: bit-reproducible and independent of N.  A parameter outside what is built is refused with
+ * MSTG_E_UNSUPPORTED / MSTG_E_BADARG and a message naming it, never approximated.  `out` and a workspace must not overlap an input.
+ *
+ *   1. segment statistics and blend ratios (:76-171 analyze_segments, determine_blend_ratios).  labels (N, H, W) int32 and
+ *        num_segments S: a pixel whose label lies outside [0, S) belongs to no segment, contributes to nothing and gets map 0;
+ *        labels need be neither contiguous nor connected; a label with no pixel is skipped (ratio 0, sums 0).  2 <= H, W and
+ *        H * W <= MSTG_SEGMENT_MAX_PIXELS (the edge sum fits 64 bits while H * W * 1443 < 2^31), else refused by name.
+ *        Per image and label s, MSTG_SEGMENT_SUMS exact 64-bit integers, in this order: n; sum R, G, B; sum R^2, G^2, B^2; sum S
+ *        (the saturation of the 8-bit COLOR_RGB2HSV as defined above: sdiv, (diff * sdiv[v] + 2048) >> 12); sum y; sum x; E.
+ *        E: g_s = the 8-bit grey (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14 where the label is s, 0 elsewhere (cvtColor of the
+ *          zeroed copy); gx, gy = the 3 x 3 Sobel of g_s, BORDER_REFLECT_101 (labels and greys mirrored alike); m = sqrt of the
+ *          integer gx^2 + gy^2, correctly rounded in float64; E = the sum over ALL pixels of the image of rint(m * 2^32) (round
+ *          half to even) as unsigned 64-bit integers.  Only a pixel with an s in its reflected 3 x 3 neighbourhood contributes (at
+ *          most nine labels per pixel).  The fixed point is what makes the sum independent of its order.
+ *        ratio, float64, every operation rounded, no fused multiply-add, in this order: std_c = sqrt((double)(n * sum c^2 -
+ *          (sum c)^2)) / n with the integer formed exactly; mstd = ((std_R + std_G) + std_B) / 3.0; ed = (double)E / 2^32 /
+ *          (double)(H * W); py = (double)sum y / n, px likewise; cy = H / 2, cx = W / 2 (integers); md = sqrt((double)(cx^2 + cy^2));
+ *          dist = sqrt((py - cy)^2 + (px - cx)^2); sm = (double)sum S / n; adj = (((0.3 * (ed / 30) + 0.2 * (mstd / 50)) - 0.1 *
+ *          (dist / md)) + (-0.1 * (n / (H * W / 100.0)))) + 0.2 * (sm / 255); ratio = max(0.3, min(0.9, 0.7 + adj)) rounded to
+ *          float32.  This is not numpy's literal evaluation (np.std sums squared deviations in mask order, np.mean of the
+ *          magnitudes is a pairwise float64 sum); tests/test_enhanced_local_style_cpu.py compares the float32 ratios of the two.
+ *        map[p] = ratio[label[p]], float32 (N, H, W).
+ *   2. smoothed map (:174): scipy.ndimage.gaussian_filter(map, sigma=3) on float32: radius 12, the float64 weights of
+ *        _gaussian_kernel1d(3, 0, 12) to the bit (constants), mode 'reflect' (d c b a | a b c d | d c b a) for any extent, axis 0
+ *        then axis 1, per line t = in[i] * w[0]; t += (in[i - k] + in[i + k]) * w[k] for k = 12 .. 1 in float64, every operation
+ *        rounded; the result of each axis pass is stored as float32.
+ *   3. blend (:232-240), float32 as numpy forms it from uint8 and float32 arrays: x = fl(fl(styled * m) + fl(canvas * fl(1 - m))),
+ *        clipped to [0, 255] and truncated (a NaN gives 0).  The clip is this build's: it matters only for a map outside [0, 1].
+ *        NOT mstg_blend_u8, which is float64.
+ *   4. colour and contrast (:243-257).  (a) h, s, v of the 8-bit COLOR_RGB2HSV as defined above.  (b) s' = min(rint(s * 1.2), 255):
+ *        the fractions are multiples of 0.2, never near a tie, so float32 (used here) and float64 give the same byte for all 256
+ *        values (asserted in the CPU test).  (c) v' = CLAHE(clipLimit 2.0, tiles 8 x 8) of the v plane, OpenCV's clahe.cpp as
+ *        recalled: tile = (W / 8, H / 8); H and W must be multiples of 8 (OpenCV pads otherwise: refused by name); per tile a
+ *        256-bin histogram; clip = max((int)(2.0 * area / 256), 1); the excess above clip is summed and every bin capped; batch =
+ *        excess / 256 goes to every bin; residual = excess - batch * 256; if nonzero, step = max(256 / residual, 1) and
+ *        for (i = 0; i < 256 && residual > 0; i += step, --residual) ++hist[i]; lut[i] = sat_u8(rint((float)cumsum_i * lutScale)),
+ *        lutScale = 255.0f / area.  Per pixel txf = x * (1.0f / tw) - 0.5f; tx1 = floor(txf); xa = txf - tx1; xa1 = 1.0f - xa;
+ *        tx1 clamped to >= 0; tx2 = tx1 + 1 (formed before the clamp) clamped to <= 7; the same in y; res = (L11 * xa1 + L12 * xa) *
+ *        ya1 + (L21 * xa1 + L22 * xa) * ya in float32, every operation rounded; v' = sat_u8(rint(res)).  For tile sides that are
+ *        powers of two up to 64 every product and sum is exact.  (d) the 8-bit COLOR_HSV2RGB of (h, s', v'), OpenCV's float path
+ *        as recalled: hf = h, sf = s' * (1.f / 255.f), vf = v' * (1.f / 255.f); sf == 0: r = g = b = vf; else hf *= 6.f / 180.f,
+ *        sector = floor(hf), hf -= sector, a sector outside 0 .. 5 becomes sector 0 with hf = 0; tab = {vf, vf * (1 - sf),
+ *        vf * (1 - sf * hf), vf * (1 - sf * (1 - hf))}; (b, g, r) = tab indexed by {{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}}
+ *        [sector]; every operation rounded in float32, no fused multiply-add; each byte sat_u8(rint(c * 255.f)).  Over all
+ *        180 * 256 * 256 (h, s, v) a fused evaluation (1 - sf * hf and 1 - sf * (1 - hf) as one fused operation each)
+ *        changes 0.001 % of the bytes and a float64 evaluation 0.020 %, never by more than one level
+ *        (tests/test_enhanced_local_style_cpu.py measures both shares).
+ *   5. sharpen and denoise (:260-264): cv2.filter2D with [[-1,-1,-1],[-1,9,-1],[-1,-1,-1]] per channel = 9 * centre - the eight
+ *        neighbours, BORDER_REFLECT_101, exact integers, saturated; then cv2.bilateralFilter(5, 50, 50) = mstg_bilateral_u8.
+ *   segmentation (:68), HOST: skimage.segmentation.felzenszwalb(img, scale, sigma=0.5, min_size) as recalled: the image as float64
+ *        divided by 255, scale / 255; scipy's Gaussian per channel (sigma 0.5, radius 2, 'reflect', the weights of
+ *        _gaussian_kernel1d(0.5, 0, 2) to the bit, axis 0 then axis 1, the accumulation order of step 2; another sigma is refused
+ *        by name); the four 8-neighbour edge sets in the order right, down, down-right, up-right, each in row-major order of its
+ *        first pixel; cost = the rounded sqrt of ((d0^2 + d1^2) + d2^2); a STABLE sort by cost; union-find with the merge rule
+ *        cost < min(int_0 + scale / size_0, int_1 + scale / size_1), the merged internal cost = the edge's cost; a second pass in
+ *        the same edge order that merges any two components of which one is smaller than min_size; labels numbered in ascending
+ *        order of the root's pixel index, where the root of a component is its smallest pixel index.  scikit-image orders equal
+ *        costs however numpy's unstable sort leaves them: the stable order is THIS BUILD'S definition.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_SEGMENT_SUMS 11
+#define MSTG_SEGMENT_MAX_PIXELS 1048576
+#define MSTG_SEGMENT_TILE_SLOTS 128 /* distinct labels a 16 x 64 tile combines in LDS; more go straight to the global sums */
+#define MSTG_CLAHE_TILES 8
+/* bytes mstg_segment_blend_map needs; 0 for an invalid shape (mstg_last_error says which) */
+size_t mstg_segment_blend_map_workspace_bytes(int N, int H, int W, int num_segments, int smooth);
+/* step 1, and step 2 when smooth != 0: map float32 (N, H, W); sums (N, S, MSTG_SEGMENT_SUMS) unsigned 64-bit and ratio float32
+ * (N, S): the per-segment record; workspace 16-byte aligned (read with smooth only).  Four launches, six with smooth, whatever N
+ * and S */
+int mstg_segment_blend_map(const unsigned char* canvas, const int* labels, int N, int H, int W, int num_segments, int smooth, float* map,
+                           unsigned long long* sums, float* ratio, void* workspace, size_t workspace_bytes, void* stream);
+/* step 2 alone on any float32 (N, H, W), any H, W >= 1; workspace: N * H * W * 4 bytes; two launches */
+int mstg_gaussian_reflect_f32(const float* in, int N, int H, int W, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* step 3; one launch */
+int mstg_blend_map_f32_u8(const unsigned char* canvas, const unsigned char* styled, const float* map, int N, int H, int W, unsigned char* out,
+                          void* stream);
+/* bytes of the CLAHE tables for N images (mstg_clahe_u8, mstg_hsv_enhance_u8); 0 for an invalid shape */
+size_t mstg_clahe_workspace_bytes(int N, int H, int W);
+/* step 4c on a plane (N, H, W): the tables, then the application; two launches */
+int mstg_clahe_u8(const unsigned char* in, int N, int H, int W, unsigned char* out, void* workspace, size_t workspace_bytes, void* stream);
+/* steps 4a-d on an RGB batch; two launches */
+int mstg_hsv_enhance_u8(const unsigned char* in, int N, int H, int W, unsigned char* out, void* workspace, size_t workspace_bytes, void* stream);
+/* the filter of step 5; one launch */
+int mstg_sharpen3_u8(const unsigned char* in, int N, int H, int W, unsigned char* out, void* stream);
+/* bytes mstg_enhanced_style_finish needs for (N, H, W); 0 for an invalid shape (mstg_last_error says which) */
+size_t mstg_enhanced_style_finish_workspace_bytes(int N, int H, int W);
+/* Steps 3, 4 and 5 from canvas, styled and map on the caller's workspace (16-byte aligned), byte for byte the composition of
+ * mstg_blend_map_f32_u8, mstg_hsv_enhance_u8, mstg_sharpen3_u8 and mstg_bilateral_u8(d = 5), in FIVE launches whatever N.
+ * bilateral_table: the MSTG_BILATERAL_TABLE_FLOATS floats of mstg_bilateral_tables(5, 50, 50) on the device. */
+int mstg_enhanced_style_finish(const unsigned char* canvas, const unsigned char* styled, const float* map, int N, int H, int W,
+                               const float* bilateral_table, unsigned char* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Host only (host pointers, no stream): the segmentation above of one (H, W, 3) image into labels (H, W) int32.  Returns the number
+ * of segments (>= 1) or a negative code. */
+int mstg_felzenszwalb_u8(const unsigned char* img, int H, int W, double scale, double sigma, int min_size, int* labels);
+
+/* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain
  * (enhanced_generator.py:4; call shape :115, :218-225) -- parity unpinned; definition in structural_transformer.py.
  * The block's Linear layers go through mstg_conv2d_* (a Linear over tokens (N, L, dim) is a 1x1 convolution on NHWC).

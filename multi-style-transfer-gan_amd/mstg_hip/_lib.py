@@ -217,6 +217,17 @@ SIGNATURES = {
     "mstg_color_block_fix_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "mstg_color_block_fix": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _i, _i, _i, _vp, _vp, _i, C.c_double, C.c_double, C.c_double, _vp, _vp,
                                   _sz, _vp]),
+    "mstg_segment_blend_map_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "mstg_segment_blend_map": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_gaussian_reflect_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mstg_blend_map_f32_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mstg_clahe_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_clahe_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mstg_hsv_enhance_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mstg_sharpen3_u8": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "mstg_enhanced_style_finish_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_enhanced_style_finish": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_felzenszwalb_u8": (_i, [_vp, _i, _i, C.c_double, C.c_double, _i, _vp]),
 }
 
 APP_EDGE_KSIZE = 21  # MSTG_APP_EDGE_KSIZE
@@ -225,6 +236,8 @@ BILATERAL_COLOR_WEIGHTS, BILATERAL_MAX_TAPS = 768, 49  # MSTG_BILATERAL_COLOR_WE
 LAB_TABLE_U16 = 3340  # MSTG_LAB_TABLE_U16
 BILATERAL_WIDE_MAX_RADIUS = 90  # MSTG_BILATERAL_WIDE_MAX_RADIUS
 BILATERAL_WIDE_TABLE_FLOATS = 768 + 90 * 90 + 1  # MSTG_BILATERAL_WIDE_TABLE_FLOATS
+SEGMENT_SUMS, SEGMENT_MAX_PIXELS, SEGMENT_TILE_SLOTS = 11, 1 << 20, 128  # MSTG_SEGMENT_SUMS, _MAX_PIXELS, _TILE_SLOTS
+CLAHE_TILES = 8  # MSTG_CLAHE_TILES
 STANDARD_MODEL_TYPES = {"photo_to_monet": 0, "monet_to_photo": 1}  # MSTG_STANDARD_PHOTO_TO_MONET, MSTG_STANDARD_MONET_TO_PHOTO
 
 _lib = None

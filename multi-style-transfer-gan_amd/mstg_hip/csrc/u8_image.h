@@ -1,5 +1,5 @@
 // Device and host helpers shared by the 8-bit image filters (local_style.hip, standard_mode.hip, app_local_style.hip,
-// color_blocks.hip).  Every device helper is a bit-exact restatement of an OpenCV / numpy definition; a primitive that more than one
+// color_blocks.hip, segment_style.hip).  Every device helper is a bit-exact restatement of an OpenCV / numpy definition; a primitive that more than one
 // of those files uses is defined HERE, once, so that a fix reaches every user ("Shared 8-bit image helpers").  All
 // __forceinline__: a kernel compiles to the code it had with the body written out in place.
 #pragma once
@@ -100,6 +100,41 @@ __device__ __forceinline__ TileOrigin tile_of(int tiles, int tiles_x) {
 template <int THREADS>
 __device__ __forceinline__ void stage_lut768(const unsigned char* __restrict__ lut, unsigned char* slut, int tid) {
     for (int e = tid; e < 768; e += THREADS) slut[e] = lut[e];
+}
+
+// ---- shared by the kernels of segment_style.hip ------------------------------------------------------------------------------------
+// round-half-even(num / i) in integers, 0 for i == 0: OpenCV's cvRound of the divisor tables (sdiv: num = 255 << 12, hdiv: 122880)
+__device__ __forceinline__ int div_rhe(int num, int i) {
+    if (i == 0) return 0;
+    const int q = num / i, r = num - q * i;
+    return q + ((2 * r > i || (2 * r == i && (q & 1))) ? 1 : 0);
+}
+
+// the 8-bit COLOR_RGB2GRAY of a packed pixel
+__device__ __forceinline__ int gray_px(unsigned q) {
+    return (int)((q & 0xffu) * 4899u + ((q >> 8) & 0xffu) * 9617u + (q >> 16) * 1868u + 8192u) >> 14;
+}
+
+// the 8-bit COLOR_RGB2HSV of a packed pixel (include/mstg_hip.h); sdiv, hdiv = the two divisor tables (hdiv may be null: h = 0)
+__device__ __forceinline__ void hsv_px(unsigned q, const int* sdiv, const int* hdiv, int& h, int& s, int& v) {
+    const int R = q & 0xff, G = (q >> 8) & 0xff, B = q >> 16;
+    v = max(R, max(G, B));
+    const int diff = v - min(R, min(G, B));
+    s = (diff * sdiv[v] + 2048) >> 12;
+    h = 0;
+    if (hdiv) {
+        const int h0 = v == R ? G - B : (v == G ? B - R + 2 * diff : R - G + 4 * diff);
+        h = (h0 * hdiv[diff] + 2048) >> 12;  // arithmetic shift of the signed product
+        if (h < 0) h += 180;
+    }
+}
+
+// scipy.ndimage 'reflect' (d c b a | a b c d | d c b a), for any distance from the array
+__device__ __forceinline__ int reflect_sym(int i, int n) {
+    const int p = 2 * n;
+    i %= p;
+    if (i < 0) i += p;
+    return i < n ? i : p - 1 - i;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------

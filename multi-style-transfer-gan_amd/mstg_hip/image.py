@@ -1191,3 +1191,196 @@ def fix_color_blocks(img: torch.Tensor, original=None) -> torch.Tensor:
     _lib.check(lib.mstg_color_block_fix(_p(x), _p(o), N, H, W, _p(_lab_table(dev)), 30.0, 11, 50, radius, _p(table), _p(kern), ksize,
                                         1 - alpha, alpha, beta, _p(out), _p(ws), need, _stream()), "mstg_color_block_fix")
     return out[0] if single else out
+
+
+# ---- the segmentation-driven local style of enhanced_local_style.py (csrc/segment_style.hip) -------------------------------
+def felzenszwalb_labels(img, scale=100, sigma=0.5, min_size=50) -> np.ndarray:
+    """``skimage.segmentation.felzenszwalb(img, scale, sigma, min_size)`` of an (H, W, 3) uint8 image (numpy, or a tensor that is
+    copied to the host) on the HOST, as include/mstg_hip.h defines it -> int32 numpy (H, W), labels 0 .. count - 1.  Equal edge
+    costs keep their order (a stable sort): this build's definition, where scikit-image leaves them as numpy's unstable sort does.
+    Only ``sigma=0.5`` is built; another value raises, naming it.  Not compared with scikit-image."""
+    a = img.detach().cpu().numpy() if isinstance(img, torch.Tensor) else np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise RuntimeError(f"mstg_hip segmentation: expected an (H, W, 3) uint8 image, got {a.dtype} {tuple(a.shape)}")
+    a = np.ascontiguousarray(a)
+    H, W = a.shape[:2]
+    labels = np.zeros((H, W), dtype=np.int32)
+    rc = _lib.load().mstg_felzenszwalb_u8(a.ctypes.data, H, W, float(scale), float(sigma), int(min_size), labels.ctypes.data)
+    if rc <= 0:
+        _lib.check(rc or -1, "mstg_felzenszwalb_u8")
+    return labels
+
+
+def _req_labels(labels, shape, device):
+    lab = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
+    lab = lab.to(device=device, dtype=torch.int32).contiguous()
+    if lab.dim() == 2:
+        lab = lab.unsqueeze(0)
+    if tuple(lab.shape) != tuple(shape):
+        raise RuntimeError(f"mstg_hip segment style: expected labels of shape {tuple(shape)}, got {tuple(lab.shape)}")
+    return lab
+
+
+def segment_blend_map(canvas_u8, labels, num_segments=None, smooth=True, return_stats=False):
+    """``determine_blend_ratios(analyze_segments(canvas, labels), labels, shape)`` of the reference (enhanced_local_style.py:76-176)
+    for an (H, W, 3) or (N, H, W, 3) uint8 canvas on the GPU and integer labels (H, W) / (N, H, W) (numpy or tensor) -> float32
+    (H, W) / (N, H, W): the per-segment sums in one pass over the image (a segmented reduction keyed by label), the ratio of every
+    label, the map, and with ``smooth`` ``scipy.ndimage.gaussian_filter(map, sigma=3)``.  ``num_segments`` None: the largest label
+    + 1 (one host synchronisation); a label outside ``[0, num_segments)`` belongs to no segment and gets 0.  With ``return_stats``
+    also (sums int64 (N, S, 11): n, sum R, G, B, R^2, G^2, B^2, S, y, x and the 2^32 fixed-point edge sum; ratio float32 (N, S)).
+    Four launches, six with ``smooth``, whatever N and the number of segments; bit-reproducible."""
+    single, c = _stage_u8(canvas_u8, "canvas")
+    N, H, W = c.shape[:3]
+    lab = _req_labels(labels, (N, H, W), c.device)
+    S = int(lab.max().item()) + 1 if num_segments is None else int(num_segments)
+    lib = _lib.load()
+    out = torch.empty((N, H, W), dtype=torch.float32, device=c.device)
+    sums = torch.empty((N, max(S, 1), _lib.SEGMENT_SUMS), dtype=torch.int64, device=c.device)
+    ratio = torch.empty((N, max(S, 1)), dtype=torch.float32, device=c.device)
+    need = lib.mstg_segment_blend_map_workspace_bytes(N, H, W, S, int(bool(smooth)))  # 0: the call below names what is wrong
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=c.device)
+    _lib.check(lib.mstg_segment_blend_map(_p(c), _p(lab), N, H, W, S, int(bool(smooth)), _p(out), _p(sums), _p(ratio), _p(ws), need, _stream()),
+               "mstg_segment_blend_map")
+    if single:
+        out, sums, ratio = out[0], sums[0], ratio[0]
+    return (out, sums, ratio) if return_stats else out
+
+
+def gaussian_reflect_f32(plane: torch.Tensor) -> torch.Tensor:
+    """``scipy.ndimage.gaussian_filter(plane, sigma=3)`` of a float32 (H, W) or (N, H, W) tensor on the GPU, bit for bit (radius 12,
+    float64 weights and accumulation, mode 'reflect', float32 between the two passes); two launches."""
+    single = plane.dim() == 2
+    x = (plane.unsqueeze(0) if single else plane).contiguous()
+    if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 3:
+        raise RuntimeError(f"mstg_hip segment style: expected a float32 (H, W) or (N, H, W) tensor on the GPU, got {x.dtype} {tuple(x.shape)}")
+    N, H, W = x.shape
+    out, ws = torch.empty_like(x), torch.empty_like(x)
+    _lib.check(_lib.load().mstg_gaussian_reflect_f32(_p(x), N, H, W, _p(out), _p(ws), ws.numel() * 4, _stream()), "mstg_gaussian_reflect_f32")
+    return out[0] if single else out
+
+
+def _clahe_ws(lib, N, H, W, device):
+    need = lib.mstg_clahe_workspace_bytes(N, H, W)  # 0: the call names what is wrong with the shape
+    return need, torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+
+
+def clahe_u8(plane: torch.Tensor) -> torch.Tensor:
+    """``cv2.createCLAHE(clipLimit=2.0, tileGridSize=(8, 8)).apply(plane)`` of a uint8 (H, W) or (N, H, W) plane on the GPU as
+    include/mstg_hip.h defines it; H and W must be multiples of 8 (OpenCV pads other sizes: raises, naming them).  Two launches.
+    Not compared with an OpenCV binary."""
+    single = plane.dim() == 2
+    x = (plane.unsqueeze(0) if single else plane).contiguous()
+    if not x.is_cuda or x.dtype != torch.uint8 or x.dim() != 3:
+        raise RuntimeError(f"mstg_hip segment style: expected a uint8 (H, W) or (N, H, W) plane on the GPU, got {x.dtype} {tuple(x.shape)}")
+    N, H, W = x.shape
+    lib = _lib.load()
+    need, ws = _clahe_ws(lib, N, H, W, x.device)
+    out = torch.empty_like(x)
+    _lib.check(lib.mstg_clahe_u8(_p(x), N, H, W, _p(out), _p(ws), need, _stream()), "mstg_clahe_u8")
+    return out[0] if single else out
+
+
+def hsv_enhance_u8(img: torch.Tensor) -> torch.Tensor:
+    """The colour step of the reference (enhanced_local_style.py:243-257) for an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU:
+    8-bit ``COLOR_RGB2HSV``, s * 1.2 saturated, CLAHE(2.0, 8 x 8) of v, ``COLOR_HSV2RGB``; H and W multiples of 8.  Two launches.
+    Not compared with an OpenCV binary."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    lib = _lib.load()
+    need, ws = _clahe_ws(lib, N, H, W, x.device)
+    out = torch.empty_like(x)
+    _lib.check(lib.mstg_hsv_enhance_u8(_p(x), N, H, W, _p(out), _p(ws), need, _stream()), "mstg_hsv_enhance_u8")
+    return out[0] if single else out
+
+
+def sharpen3_u8(img: torch.Tensor) -> torch.Tensor:
+    """``cv2.filter2D(img, -1, [[-1,-1,-1],[-1,9,-1],[-1,-1,-1]])`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU
+    (enhanced_local_style.py:260-261): exact integers, BORDER_REFLECT_101, saturated; one launch."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_sharpen3_u8(_p(x), N, H, W, _p(out), _stream()), "mstg_sharpen3_u8")
+    return out[0] if single else out
+
+
+def _req_map(blend_map, shape, device):
+    m = torch.from_numpy(np.ascontiguousarray(blend_map)) if isinstance(blend_map, np.ndarray) else blend_map
+    m = m.to(device=device, dtype=torch.float32).contiguous()
+    if m.dim() == 2:
+        m = m.unsqueeze(0)
+    if tuple(m.shape) != tuple(shape):
+        raise RuntimeError(f"mstg_hip segment style: expected a blend map of shape {tuple(shape)}, got {tuple(m.shape)}")
+    return m
+
+
+def blend_map_u8(canvas_u8, styled_u8, blend_map) -> torch.Tensor:
+    """``styled * map + canvas * (1 - map)`` in float32 as numpy forms it from uint8 and float32 arrays, clipped and truncated
+    (enhanced_local_style.py:232-240); not ``blend_u8``, which is float64.  One launch."""
+    single, st = _stage_u8(styled_u8, "styled image")
+    _, c = _stage_u8(canvas_u8, "canvas")
+    if c.shape != st.shape:
+        raise RuntimeError(f"mstg_hip segment style: shapes differ {tuple(c.shape)} vs {tuple(st.shape)}")
+    N, H, W = st.shape[:3]
+    m = _req_map(blend_map, (N, H, W), st.device)
+    out = torch.empty_like(st)
+    _lib.check(_lib.load().mstg_blend_map_f32_u8(_p(c), _p(st), _p(m), N, H, W, _p(out), _stream()), "mstg_blend_map_f32_u8")
+    return out[0] if single else out
+
+
+def enhanced_style_finish(canvas_u8, styled_u8, blend_map) -> torch.Tensor:
+    """Everything ``enhanced_local_style_transfer`` of the reference does between the blend map and the crop
+    (enhanced_local_style.py:232-264) for (H, W, 3) or (N, H, W, 3) uint8 images and a float32 map on the GPU: the float32 blend,
+    the colour step (``hsv_enhance_u8``), ``sharpen3_u8`` and ``cv2.bilateralFilter(5, 50, 50)``; H and W multiples of 8.  Five
+    launches on one workspace whatever N, byte for byte the composition of ``blend_map_u8``, ``hsv_enhance_u8``, ``sharpen3_u8``
+    and ``bilateral_u8(d=5, 50, 50)``.  Not compared with an OpenCV binary."""
+    single, st = _stage_u8(styled_u8, "styled image")
+    _, c = _stage_u8(canvas_u8, "canvas")
+    if c.shape != st.shape:
+        raise RuntimeError(f"mstg_hip segment style: shapes differ {tuple(c.shape)} vs {tuple(st.shape)}")
+    N, H, W = st.shape[:3]
+    m = _req_map(blend_map, (N, H, W), st.device)
+    lib = _lib.load()
+    table = _bilateral_table(5, 50, 50, st.device)
+    out = torch.empty_like(st)
+    need = lib.mstg_enhanced_style_finish_workspace_bytes(N, H, W)  # 0: the call below names what is wrong with the shape
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=st.device)
+    _lib.check(lib.mstg_enhanced_style_finish(_p(c), _p(st), _p(m), N, H, W, _p(table), _p(out), _p(ws), need, _stream()),
+               "mstg_enhanced_style_finish")
+    return out[0] if single else out
+
+
+def letterbox_black(img_u8: torch.Tensor, target=256):
+    """enhanced_local_style.py:184-203: ``letterbox`` on a BLACK canvas -> (canvas, (width, height))"""
+    height, width = img_u8.shape[:2]
+    if width > height:
+        new_width, new_height = target, int(height * (target / width))
+    else:
+        new_height, new_width = target, int(width * (target / height))
+    resized = resize_u8(img_u8, (new_width, new_height), LANCZOS)
+    off_x, off_y = (target - new_width) // 2, (target - new_height) // 2
+    return paste_u8(resized, (0, 0, new_height, new_width), (target, target), (off_y, off_x), fill=0), (width, height)
+
+
+def process_enhanced_local_style(model, img_u8: torch.Tensor, segments=None, target=256) -> torch.Tensor:
+    """``enhanced_local_style_transfer`` of the reference (enhanced_local_style.py:178-292) without the file I/O and the chart:
+    decoded uint8 image in, uint8 image out.  The letterbox on black, the forward pass, ``segment_blend_map`` of the canvas with
+    ``segments`` (integer labels (target, target); None: ``felzenszwalb_labels(canvas)``, the one host step), ``enhanced_style_finish``,
+    the crop of :270-277 exactly as written (its ``min(target, int(...))`` sizes leave an image larger than the canvas in both
+    directions uncropped) and the LANCZOS resize back under the condition of :280."""
+    canvas, (width, height) = letterbox_black(img_u8, target)
+    x = to_tensor(canvas).unsqueeze(0)
+    with torch.no_grad():
+        y = model(x)
+    styled = to_u8(y[0])
+    if segments is None:
+        segments = felzenszwalb_labels(canvas)
+    blend_map = segment_blend_map(canvas, segments)
+    out = enhanced_style_finish(canvas, styled, blend_map)
+    if width != height:
+        new_width = min(target, int(height * (width / height)))
+        new_height = min(target, int(width * (height / width)))
+        left, top = (target - new_width) // 2, (target - new_height) // 2
+        out = crop_u8(out, left, top, left + new_width, top + new_height)
+    if (width > target or height > target) and width * height <= 1024 * 1024:
+        out = resize_u8(out, (width, height), LANCZOS)
+    return out
