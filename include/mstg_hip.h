@@ -976,7 +976,136 @@ int mstg_enhanced_style_finish(const unsigned char* canvas, const unsigned char*
 int mstg_felzenszwalb_u8(const unsigned char* img, int H, int W, double scale, double sigma, int min_size, int* labels);
 
 /* ------------------------------------------------------------------------------------------------
- * BUILD-DEFINED StructuralTransformerBlock pieces.  The reference imports the class from a file its snapshot does not contain
+ * The FIVE SETTINGS of the reference's advanced_transform.py (:129-311: standard, contrast, multi-scale fusion, detail, K-means
+ * regions) between the forward pass and the encoder, on the device for N images (N, H, W, 3) uint8 RGB, any H, W >= 1 unless
+ * stated, N images per launch, 64-bit offsets.  The OpenCV steps are restated from the definitions below, as recalled, not
+ * compared with an OpenCV binary (tests/advanced_transform_ref.py is the same restatement in numpy); where OpenCV's path could not be
+ * recalled or cannot be pinned the step is THIS BUILD'S and says so.  No floating-point atomics, every summation order fixed:
+ * bit-reproducible and independent of N.  `out` and a workspace must not overlap an input (MSTG_E_BADARG).  A parameter outside
+ * what is built is refused with MSTG_E_UNSUPPORTED and a message naming it, never approximated.  The device evaluates no exp, pow
+ * or cbrt: the tables come from host-only entries.
+ *
+ *   1. Lab (:145, :234), the 8-bit COLOR_RGB2LAB, bytes (L, a, b) in the place of (R, G, B).  fX, fY, fZ, a and b exactly as step 1
+ *        of the colour-block repair above defines them (mstg_lab_tables: gamma, cbrt, C), completed with OpenCV's L as recalled:
+ *        L = sat_u8((296 fY - 1336934 + 16384) >> 15), 296 = (116 * 255 + 50) / 100 and 1336934 = (16 * 255 * 32768 + 50) / 100 in
+ *        integer division, arithmetic shift.  Black gives L 0, white 255, (255, 0, 0) 136, (0, 255, 0) 224, (0, 0, 255) 82.
+ *   2. Lab -> RGB (:156, :246), the 8-bit COLOR_LAB2RGB.  The STRUCTURE is OpenCV's integer path as recalled (a table from L to fY,
+ *        fX and fZ by adding scaled a and b, a table back from f to the linear value, an integer matrix, an inverse-gamma table);
+ *        its table sizes, scales and rounding could not be recalled, so the CONSTANTS AND THE ROUNDING ARE THIS BUILD'S.  Tables,
+ *        built on the host in double (mstg_lab_inverse_tables), 16-bit entries:
+ *          fy[L]   = round(32768 * f), L* = L * 100 / 255, f = L* <= 8 ? 7.787 (L* / 903.3) + 16 / 116 : (L* + 16) / 116;
+ *          da[a]   = round(32768 * (a - 128) / 500), db[b] = round(32768 * (b - 128) / 200) (signed);
+ *          cube[i] = round(8192 * max(g(8 i / 32768), 0)), i = 0 .. MSTG_LAB_INV_CUBE - 1, g(t) = t > 6 / 29 ? t^3 : (t - 16 / 116) / 7.787
+ *          (at most 36160);
+ *          D[r][k] = round(4096 * Minv[r][k] * white[k]) (signed), Minv = {3.240479, -1.53715, -0.498535; -0.969256, 1.875991,
+ *          0.041556; 0.055648, -0.204043, 1.057311}, white as above;
+ *          enc[i]  = round(255 * e(i / 8192)), i = 0 .. 8192, e(x) = x <= 0.0031308 ? 12.92 x : 1.055 x^(1 / 2.4) - 0.055.
+ *        Per pixel: fY = fy[L], fX = fY + da[a], fZ = fY - db[b]; for q = X, Y, Z: f = clamp(f_q, 0, 8 * (MSTG_LAB_INV_CUBE - 1) - 1),
+ *        i = f >> 3, G_q = cube[i] + (((cube[i + 1] - cube[i]) * (f & 7) + 4) >> 3) (linear interpolation between two entries; a
+ *        negative f gives 0); lin_c = (D[c][0] G_X + D[c][1] G_Y + D[c][2] G_Z + 2048) >> 12 (arithmetic shift; fits 32 bits),
+ *        byte_c = enc[clamp(lin_c, 0, 8192)].  Defined for every byte triple, out-of-gamut ones included (they clamp).
+ *        Measured over all 2^24 colours (tests/test_advanced_transform_cpu.py): the inverse lies within 2.07 levels of a float64
+ *        CIE inverse (the same constants, clipped to [0, 255], unrounded) of the same Lab bytes; RGB -> Lab -> RGB is off by at
+ *        most 27 levels in a channel, 0.702 on average, and by more than one level in 9.8 % of the channels.  That is the 8-bit
+ *        Lab's own quantisation (dark and saturated blues): the float64 inverse, rounded, is off by at most 27 and by 0.699 on
+ *        average as well.  The smallest distance of an unrounded table entry from a rounding tie is 3.1e-5 (asserted above 1e-9).
+ *   3. Gaussian (:230): cv2.GaussianBlur(plane, (0, 0), sigma) on 8 bits: ksize = cvRound(sigma * 6 + 1) | 1 (round half to even; 19
+ *        at sigma 3); the bit-exact 8.8 fixed-point path defined for the application's 15 x 15 blur above, with the generator as
+ *        recalled there run for this sigma (mstg_gaussian_sigma_taps, host): t_i = exp(-0.5 x_i^2 / sigma^2) normalised by the
+ *        left-to-right sum, for the first ksize / 2 taps a = t_i * 256 + err, q = round half to even(a), err = a - q, the
+ *        centre = 256 - 2 * their sum.  Sigma 3: {0, 1, 3, 4, 9, 14, 20, 28, 32, 34, 32, ...} (sum 256); the smallest distance of
+ *        any a from a tie is returned (0.0935 at sigma 3, asserted above 0.09 in the CPU test).  Along x, then along y; BORDER_REFLECT_101
+ *        repeated for sides shorter than the radius; the row sums are exact in 16 bits; out = (sum + 32768) >> 16.  ksize above
+ *        MSTG_GAUSSIAN_SIGMA_MAX_KSIZE is refused (the message names ksize).
+ *   4. HSV gains (:159-164, :249-256, :304-309): h, s, v of the 8-bit COLOR_RGB2HSV as defined above; s' = min(rint(s * s_gain),
+ *        255) and v' = min(rint(v * v_gain), 255) in float32 with the gain rounded to float32, round half to even (cv2.multiply
+ *        as step 4b of the segmentation-driven local style defines it: OpenCV, as recalled, narrows a double scalar to float32
+ *        for 8-bit sources).  At 1.2 float64 gives the same byte for all 256 values; at 1.1 it gives the next byte for the six
+ *        values 55, 95, 115, 175, 195, 215 (x.5 in float32, just above it in float64; both asserted in the CPU test).  Then the
+ *        8-bit COLOR_HSV2RGB of step 4d there.  With v_gain = 1 and CLAHE put on v it is
+ *        mstg_hsv_enhance_u8.
+ *   5. K-means (:271-276).  cv2.kmeans(..., KMEANS_RANDOM_CENTERS) draws from OpenCV's generator and cannot be pinned: THIS BUILD'S
+ *        definition.  A problem is one attempt of one image; K in 1 .. MSTG_KMEANS_MAX_K, attempts in 1 .. MSTG_KMEANS_MAX_ATTEMPTS,
+ *        iters in 1 .. MSTG_KMEANS_MAX_ITERS, else refused by name.
+ *          initial centres: c[a][k][ch] = lo[ch] + u[a][k][ch] * (hi[ch] - lo[ch]) in float32, every operation rounded; lo, hi = the
+ *          image's per-channel minimum and maximum, found on the device; u = attempts * K * 3 float32 uniforms from the caller (the
+ *          Python side draws them from numpy.random.RandomState(seed)), the same for every image.  centers0 (N, K, 3) replaces
+ *          them for attempts = 1.
+ *          assignment: d_k = ((dx * dx + dy * dy) + dz * dz) in float32, every operation rounded, dx = (float)R - c[k][0] and so
+ *          on; the label is the k of the smallest d, the lowest k wins a tie.
+ *          update: per cluster the exact integers n, sum c and sum c^2 per channel (64-bit); the new centre is (float)((double)sum /
+ *          (double)n); an empty cluster keeps its centre.  shift = max over k of ((e0 * e0 + e1 * e1) + e2 * e2) in float64 with
+ *          e = (double)new - (double)old.  A problem whose shift <= eps * eps is frozen (a flag on the device) and skipped from
+ *          then on.  At most `iters` rounds of assignment and update.
+ *          result: one more assignment of every problem under its final centres gives its sums; compactness = the sum over k
+ *          ascending, then ch ascending, of (((double)sum c^2 - (2.0 * c) * (double)sum c) + ((double)n * c) * c) with c the
+ *          float32 centre as double, every operation rounded; the attempt of the smallest compactness wins, the lowest attempt
+ *          wins a tie.  labels (N, H, W) int32 are the winner's assignment, in the order of its initial centres (no
+ *          renumbering); centers (N, K, 3) float32; compactness (N) float64; best (N) int32 = the winning attempt.
+ *        6 + 2 * iters launches whatever N and attempts, no host synchronisation.
+ *   6. region blend (:281-301): r = ratios[min(label, count - 1)] (the reference: 0.8, 0.4, then 0.6); per byte styled * r + orig *
+ *        (1 - r) in float64, two rounded products, one rounded sum, 1 - r a double subtraction; clip, truncate.  A negative label
+ *        belongs to no region and gives 0, as the reference's sum over the regions does.
+ *   7. fusion of scales (:206-215), float32, every operation rounded: x_s = (float)byte / 255.0f; f = 0; f = f + x_s * w_s in the
+ *        order given; f = f * gain; clip to [0, 1]; byte = (u8)(f * 255.0f) truncated.  1 .. MSTG_FUSE_MAX_SCALES scales.
+ *   chains, each byte for byte the composition of its stages:
+ *        contrast (:137-166): Lab, CLAHE(2.0, 8 x 8) of L (step 4c of the segmentation-driven local style; H and W multiples of 8,
+ *        else refused by name), Lab -> RGB, the gains: TWO launches (the histograms and tables of L; one point-wise kernel).
+ *        detail (:218-258): g = the 8-bit grey of orig; blurred = step 3 of g; d = (g - blurred) mod 256 (uint8 arithmetic wraps);
+ *        L' = (u8)clip((float)L + (float)d * 0.5f, 0, 255) truncated; Lab -> RGB of (L', a, b); the gains: TWO launches (the row
+ *        pass of the grey; the column pass with everything else).
+ *        regions (:261-311): K-means of orig, then the region blend and the gains in ONE launch (mstg_region_blend_gain_u8).
+ *   Still not built: a comparison with an OpenCV binary; OpenCV's own random K-means centres; the random ColorJitter of the
+ *   contrast setting's input; the matplotlib chart.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_LAB_INV_CUBE 6720
+#define MSTG_LAB_INV_TABLE_U16 15696 /* fy[256], da[256], db[256], cube[6720], D[9] row by row, enc[8193], 6 entries of padding */
+#define MSTG_GAUSSIAN_SIGMA_MAX_KSIZE 31
+#define MSTG_KMEANS_MAX_K 16
+#define MSTG_KMEANS_MAX_ATTEMPTS 16
+#define MSTG_KMEANS_MAX_ITERS 100
+#define MSTG_FUSE_MAX_SCALES 8
+/* Host only: the tables of step 2 */
+int mstg_lab_inverse_tables(unsigned short* table /* [MSTG_LAB_INV_TABLE_U16] */);
+/* Host only: the taps of step 3 (entries past ksize 0) and, where margin != NULL, the smallest distance from a rounding tie.
+ * Returns ksize or a negative code. */
+int mstg_gaussian_sigma_taps(double sigma, int* taps /* [MSTG_GAUSSIAN_SIGMA_MAX_KSIZE] */, double* margin /*nullable*/);
+/* step 1: lab_table = the entries of mstg_lab_tables on the device; one launch */
+int mstg_lab_u8(const unsigned char* in, int N, int H, int W, const unsigned short* lab_table, unsigned char* out, void* stream);
+/* step 2: inv_table = the entries of mstg_lab_inverse_tables on the device; one launch */
+int mstg_lab2rgb_u8(const unsigned char* in, int N, int H, int W, const unsigned short* inv_table, unsigned char* out, void* stream);
+/* step 3 on a plane (N, H, W): taps on the HOST (non-negative, sum 256); workspace N * H * W * 2 bytes; two launches */
+int mstg_gaussian_sigma_u8(const unsigned char* in, int N, int H, int W, const int* taps, int ksize, unsigned char* out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* step 4; one launch */
+int mstg_hsv_gain_u8(const unsigned char* in, int N, int H, int W, float s_gain, float v_gain, unsigned char* out, void* stream);
+/* bytes mstg_kmeans_u8 needs; 0 for a parameter outside what is built (mstg_last_error says which) */
+size_t mstg_kmeans_workspace_bytes(int N, int K, int attempts);
+/* step 5: exactly one of uniforms (attempts * K * 3) and centers0 (N * K * 3, attempts = 1), on the device; workspace 16-byte aligned */
+int mstg_kmeans_u8(const unsigned char* img, int N, int H, int W, int K, int attempts, int iters, double eps, const float* uniforms,
+                   const float* centers0, int* labels, float* centers, double* compactness, int* best, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* step 6: ratios on the HOST, count in 1 .. MSTG_KMEANS_MAX_K; one launch */
+int mstg_region_blend_u8(const unsigned char* styled, const unsigned char* orig, const int* labels, int N, int H, int W, const double* ratios,
+                         int count, unsigned char* out, void* stream);
+/* steps 6 and 4 in one launch */
+int mstg_region_blend_gain_u8(const unsigned char* styled, const unsigned char* orig, const int* labels, int N, int H, int W,
+                              const double* ratios, int count, float s_gain, float v_gain, unsigned char* out, void* stream);
+/* step 7: outputs (S, N, H, W, 3), weights (S floats) on the HOST; one launch */
+int mstg_fuse_scales_u8(const unsigned char* outputs, int S, int N, int H, int W, const float* weights, float gain, unsigned char* out,
+                        void* stream);
+/* bytes of the CLAHE tables mstg_contrast_enhanced_finish needs; 0 for an invalid shape (mstg_last_error says which) */
+size_t mstg_contrast_enhanced_finish_workspace_bytes(int N, int H, int W);
+int mstg_contrast_enhanced_finish(const unsigned char* styled, int N, int H, int W, const unsigned short* lab_table,
+                                  const unsigned short* inv_table, float s_gain, float v_gain, unsigned char* out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* workspace: N * H * W * 2 bytes, 2-byte aligned (the row pass) */
+int mstg_detail_enhanced_finish(const unsigned char* styled, const unsigned char* orig, int N, int H, int W, const unsigned short* lab_table,
+                                const unsigned short* inv_table, const int* taps, int ksize, float s_gain, float v_gain, unsigned char* out,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * BUILD-DEFINED StructuralTransformerBlock pieces. The reference imports the class from a file its snapshot does not contain
  * (enhanced_generator.py:4; call shape :115, :218-225) -- parity unpinned; definition in structural_transformer.py.
  * The block's Linear layers go through mstg_conv2d_* (a Linear over tokens (N, L, dim) is a 1x1 convolution on NHWC).
  * ---------------------------------------------------------------------------------------------- */

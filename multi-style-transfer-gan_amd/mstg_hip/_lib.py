@@ -228,6 +228,20 @@ SIGNATURES = {
     "mstg_enhanced_style_finish_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_enhanced_style_finish": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mstg_felzenszwalb_u8": (_i, [_vp, _i, _i, C.c_double, C.c_double, _i, _vp]),
+    "mstg_lab_inverse_tables": (_i, [_vp]),
+    "mstg_gaussian_sigma_taps": (_i, [C.c_double, _vp, _vp]),
+    "mstg_lab_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "mstg_lab2rgb_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "mstg_gaussian_sigma_u8": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "mstg_hsv_gain_u8": (_i, [_vp, _i, _i, _i, _f, _f, _vp, _vp]),
+    "mstg_kmeans_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_kmeans_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_region_blend_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "mstg_region_blend_gain_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _f, _f, _vp, _vp]),
+    "mstg_fuse_scales_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _f, _vp, _vp]),
+    "mstg_contrast_enhanced_finish_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_contrast_enhanced_finish": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _sz, _vp]),
+    "mstg_detail_enhanced_finish": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _sz, _vp]),
 }
 
 APP_EDGE_KSIZE = 21  # MSTG_APP_EDGE_KSIZE
@@ -238,6 +252,8 @@ BILATERAL_WIDE_MAX_RADIUS = 90  # MSTG_BILATERAL_WIDE_MAX_RADIUS
 BILATERAL_WIDE_TABLE_FLOATS = 768 + 90 * 90 + 1  # MSTG_BILATERAL_WIDE_TABLE_FLOATS
 SEGMENT_SUMS, SEGMENT_MAX_PIXELS, SEGMENT_TILE_SLOTS = 11, 1 << 20, 128  # MSTG_SEGMENT_SUMS, _MAX_PIXELS, _TILE_SLOTS
 CLAHE_TILES = 8  # MSTG_CLAHE_TILES
+LAB_INV_TABLE_U16, GAUSSIAN_SIGMA_MAX_KSIZE = 15696, 31  # MSTG_LAB_INV_TABLE_U16, MSTG_GAUSSIAN_SIGMA_MAX_KSIZE
+KMEANS_MAX_K, KMEANS_MAX_ATTEMPTS, KMEANS_MAX_ITERS, FUSE_MAX_SCALES = 16, 16, 100, 8  # MSTG_KMEANS_MAX_*, MSTG_FUSE_MAX_SCALES
 STANDARD_MODEL_TYPES = {"photo_to_monet": 0, "monet_to_photo": 1}  # MSTG_STANDARD_PHOTO_TO_MONET, MSTG_STANDARD_MONET_TO_PHOTO
 
 _lib = None

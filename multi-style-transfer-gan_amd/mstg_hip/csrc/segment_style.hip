@@ -23,7 +23,8 @@
 // G  seg_gauss_kernel<AXIS> one thread per pixel: scipy's correlate1d on a float32 plane, float64 weights (SS_K), mode 'reflect',
 //    the symmetric accumulation order (outermost pair first), the result stored as float32.
 // B  es_blend_kernel        point-wise float32 blend with a map.
-// L  es_clahe_lut_kernel    one workgroup per CLAHE tile: histogram in LDS (integer atomics), clip, redistribution, prefix sum, table.
+// L  es_clahe_lut_kernel    one workgroup per CLAHE tile: histogram in LDS (integer atomics), clip, redistribution, prefix sum, table
+//    (the tail, the interpolation and the HSV -> RGB conversion are in u8_image.h: advanced_transform.hip uses them too).
 // A  es_clahe_apply_kernel  / es_hsv_apply_kernel: per pixel the bilinear interpolation of the four tables; the RGB form also converts
 //    to HSV, scales s and converts back.
 // F  es_sharpen_kernel      one thread per pixel: 9 * centre - the eight neighbours, BORDER_REFLECT_101, saturated.
@@ -337,58 +338,7 @@ __global__ __launch_bounds__(SS_THREADS) void es_clahe_lut_kernel(const unsigned
         atomicAdd(&hist[v], 1);
     }
     __syncthreads();
-    const int clip = max((int)(2.0 * (double)area / 256.0), 1);
-    int h = hist[tid];
-    if (h > clip) {
-        atomicAdd(&excess, h - clip);
-        h = clip;
-    }
-    __syncthreads();
-    const int ex = excess, batch = ex / 256;
-    int residual = ex - batch * 256;
-    h += batch;
-    if (residual != 0) {
-        const int step = max(256 / residual, 1);
-        if (tid % step == 0 && tid / step < residual) ++h;
-    }
-    scan[tid] = h;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {  // inclusive prefix sum
-        const int add = tid >= o ? scan[tid - o] : 0;
-        __syncthreads();
-        scan[tid] += add;
-        __syncthreads();
-    }
-    const float scale = __fdiv_rn(255.0f, (float)area);
-    const float f = __builtin_rintf((float)scan[tid] * scale);
-    luts[(size_t)blockIdx.x * 256 + tid] = (unsigned char)fminf(fmaxf(f, 0.f), 255.f);
-}
-
-// one axis of the interpolation: the two tiles and the two float32 weights
-__device__ __forceinline__ void clahe_axis(int p, float inv, int& t1, int& t2, float& a, float& a1) {
-#pragma clang fp contract(off)
-    const float tf = (float)p * inv - 0.5f;
-    const float fl = floorf(tf);
-    t1 = (int)fl;
-    t2 = t1 + 1;
-    a = tf - fl;
-    a1 = 1.0f - a;
-    t1 = max(t1, 0);
-    t2 = min(t2, ES_TILES - 1);
-}
-
-__device__ __forceinline__ int clahe_px(const unsigned char* luts_img, int v, int y, int x, float inv_th, float inv_tw) {
-#pragma clang fp contract(off)
-    int tx1, tx2, ty1, ty2;
-    float xa, xa1, ya, ya1;
-    clahe_axis(x, inv_tw, tx1, tx2, xa, xa1);
-    clahe_axis(y, inv_th, ty1, ty2, ya, ya1);
-    const float l11 = (float)luts_img[(ty1 * ES_TILES + tx1) * 256 + v], l12 = (float)luts_img[(ty1 * ES_TILES + tx2) * 256 + v];
-    const float l21 = (float)luts_img[(ty2 * ES_TILES + tx1) * 256 + v], l22 = (float)luts_img[(ty2 * ES_TILES + tx2) * 256 + v];
-    const float p0 = l11 * xa1, p1 = l12 * xa, p2 = l21 * xa1, p3 = l22 * xa;
-    const float top = (p0 + p1) * ya1, bot = (p2 + p3) * ya;
-    const float res = top + bot;
-    return (int)fminf(fmaxf(__builtin_rintf(res), 0.f), 255.f);
+    clahe_tile_lut(tid, area, hist, scan, &excess, luts + (size_t)blockIdx.x * 256);  // u8_image.h
 }
 
 __global__ __launch_bounds__(SS_THREADS) void es_clahe_apply_kernel(const unsigned char* __restrict__ in, const unsigned char* __restrict__ luts,
@@ -400,43 +350,6 @@ __global__ __launch_bounds__(SS_THREADS) void es_clahe_apply_kernel(const unsign
     const int rem = (int)(idx - n * hw), y = rem / W, x = rem - y * W;
     const float inv_th = __fdiv_rn(1.0f, (float)(H / ES_TILES)), inv_tw = __fdiv_rn(1.0f, (float)(W / ES_TILES));
     out[idx] = (unsigned char)clahe_px(luts + n * ES_TILES * ES_TILES * 256, in[idx], y, x, inv_th, inv_tw);
-}
-
-// 8-bit COLOR_HSV2RGB, OpenCV's float path: float32, every operation rounded
-__device__ __forceinline__ unsigned hsv2rgb_px(int h, int s, int v) {
-#pragma clang fp contract(off)
-    constexpr float k255 = 1.f / 255.f, hscale = 6.f / 180.f;
-    float hf = (float)h;
-    const float sf = (float)s * k255, vf = (float)v * k255;
-    float b, g, r;
-    if (sf == 0.f) {
-        b = g = r = vf;
-    } else {
-        hf = hf * hscale;
-        const float fl = floorf(hf);
-        int sector = (int)fl;
-        hf = hf - fl;
-        if ((unsigned)sector >= 6u) {
-            sector = 0;
-            hf = 0.f;
-        }
-        float tab[4];
-        tab[0] = vf;
-        tab[1] = vf * (1.f - sf);
-        const float sh = sf * hf;
-        tab[2] = vf * (1.f - sh);
-        const float sh1 = sf * (1.f - hf);
-        tab[3] = vf * (1.f - sh1);
-        // (b, g, r) = tab[idx[sector]] with idx = {{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}}, packed two bits each
-        const unsigned bi = (0x835u >> (2 * sector)) & 3u, gi = (0x583u >> (2 * sector)) & 3u, ri = (0x358u >> (2 * sector)) & 3u;
-        b = tab[bi];
-        g = tab[gi];
-        r = tab[ri];
-    }
-    const unsigned rb = (unsigned)fminf(fmaxf(__builtin_rintf(r * 255.f), 0.f), 255.f);
-    const unsigned gb = (unsigned)fminf(fmaxf(__builtin_rintf(g * 255.f), 0.f), 255.f);
-    const unsigned bb = (unsigned)fminf(fmaxf(__builtin_rintf(b * 255.f), 0.f), 255.f);
-    return rb | gb << 8 | bb << 16;
 }
 
 __global__ __launch_bounds__(SS_THREADS) void es_hsv_apply_kernel(const unsigned char* __restrict__ in, const unsigned char* __restrict__ luts, int H,

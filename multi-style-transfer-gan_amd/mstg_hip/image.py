@@ -1384,3 +1384,235 @@ def process_enhanced_local_style(model, img_u8: torch.Tensor, segments=None, tar
     if (width > target or height > target) and width * height <= 1024 * 1024:
         out = resize_u8(out, (width, height), LANCZOS)
     return out
+
+
+# ---- the five settings of advanced_transform.py (csrc/advanced_transform.hip) ------------------------------------------------
+ADVANCED_SETTINGS = ("standard", "contrast", "multi_scale", "detail", "regions")
+
+
+def _lab_inverse_table(device):
+    """the 16-bit tables of ``mstg_lab_inverse_tables`` on ``device`` (built on the host, uploaded once; int16 holds the same bits)"""
+    return _device_table(("lab_inverse",), device,
+                         lambda: _host_fill("mstg_lab_inverse_tables", _lib.LAB_INV_TABLE_U16, np.uint16)[1].view(np.int16))
+
+
+@lru_cache(maxsize=32)
+def gaussian_sigma_taps(sigma: float):
+    """(ksize, taps, margin) of ``cv2.GaussianBlur(u8, (0, 0), sigma)``: ``ksize = cvRound(sigma * 6 + 1) | 1``, the 8.8 fixed-point
+    taps (int32 numpy, ``ksize`` of them) and the smallest distance of a rounded quantity from a tie, from the host entry
+    ``mstg_gaussian_sigma_taps``; a size above 31 (sigma above 5) raises, naming ksize."""
+    taps, margin = np.zeros(_lib.GAUSSIAN_SIGMA_MAX_KSIZE, dtype=np.int32), np.zeros(1, dtype=np.float64)
+    ksize = _lib.load().mstg_gaussian_sigma_taps(float(sigma), taps.ctypes.data, margin.ctypes.data)
+    if ksize <= 0:
+        _lib.check(ksize or -1, "mstg_gaussian_sigma_taps")
+    return ksize, taps, float(margin[0])
+
+
+def lab_u8(img: torch.Tensor) -> torch.Tensor:
+    """``cv2.cvtColor(img, cv2.COLOR_RGB2LAB)`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU -> (L, a, b) bytes of the same
+    shape: OpenCV's integer path as include/mstg_hip.h defines it (a and b are those of ``detect_color_blocks``); one launch.  Not
+    compared with an OpenCV binary."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_lab_u8(_p(x), N, H, W, _p(_lab_table(x.device)), _p(out), _stream()), "mstg_lab_u8")
+    return out[0] if single else out
+
+
+def lab2rgb_u8(lab: torch.Tensor) -> torch.Tensor:
+    """``cv2.cvtColor(lab, cv2.COLOR_LAB2RGB)`` of (L, a, b) bytes, (H, W, 3) or (N, H, W, 3), on the GPU: an integer path from
+    host-built tables whose structure is OpenCV's and whose constants are this build's (include/mstg_hip.h states the measured
+    distance from a float64 CIE inverse); every byte triple has a result, out-of-gamut ones clamp.  One launch."""
+    single, x = _stage_u8(lab, "Lab image")
+    N, H, W = x.shape[:3]
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_lab2rgb_u8(_p(x), N, H, W, _p(_lab_inverse_table(x.device)), _p(out), _stream()), "mstg_lab2rgb_u8")
+    return out[0] if single else out
+
+
+def _req_plane(plane, what):
+    single = plane.dim() == 2
+    x = (plane.unsqueeze(0) if single else plane).contiguous()
+    if not x.is_cuda or x.dtype != torch.uint8 or x.dim() != 3:
+        raise RuntimeError(f"mstg_hip advanced transform: expected a uint8 (H, W) or (N, H, W) {what} on the GPU, got {x.dtype} {tuple(x.shape)}")
+    return single, x
+
+
+def gaussian_sigma_u8(plane: torch.Tensor, sigma=3.0) -> torch.Tensor:
+    """``cv2.GaussianBlur(plane, (0, 0), sigma)`` of a uint8 (H, W) or (N, H, W) plane on the GPU: OpenCV's bit-exact 8.8
+    fixed-point path with the taps of ``gaussian_sigma_taps`` (19 at sigma 3), BORDER_REFLECT_101 for any side; two launches.  Not
+    compared with an OpenCV binary."""
+    single, x = _req_plane(plane, "plane")
+    N, H, W = x.shape
+    ksize, taps, _ = gaussian_sigma_taps(float(sigma))
+    out = torch.empty_like(x)
+    ws = torch.empty(N * H * W, dtype=torch.int16, device=x.device)
+    _lib.check(_lib.load().mstg_gaussian_sigma_u8(_p(x), N, H, W, taps.ctypes.data, ksize, _p(out), _p(ws), ws.numel() * 2, _stream()),
+               "mstg_gaussian_sigma_u8")
+    return out[0] if single else out
+
+
+def hsv_gain_u8(img: torch.Tensor, s_gain=1.2, v_gain=1.0) -> torch.Tensor:
+    """8-bit ``COLOR_RGB2HSV``, ``cv2.multiply(s, s_gain)`` and ``cv2.multiply(v, v_gain)`` (float32, rounded half to even,
+    saturated), ``COLOR_HSV2RGB`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU: the colour step of ``hsv_enhance_u8``
+    without its CLAHE; one launch."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    out = torch.empty_like(x)
+    _lib.check(_lib.load().mstg_hsv_gain_u8(_p(x), N, H, W, float(s_gain), float(v_gain), _p(out), _stream()), "mstg_hsv_gain_u8")
+    return out[0] if single else out
+
+
+def kmeans_u8(img: torch.Tensor, K=5, attempts=10, iters=10, eps=1.0, seed=0, centers0=None, return_attempt=False):
+    """This build's deterministic stand-in for ``cv2.kmeans(pixels, K, None, (EPS + MAX_ITER, iters, eps), attempts,
+    KMEANS_RANDOM_CENTERS)`` on the pixels of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU (OpenCV draws its centres from its
+    own generator, which cannot be pinned): initial centres ``lo + u * (hi - lo)`` per channel with ``u`` drawn from
+    ``numpy.random.RandomState(seed)`` (the same table for every image) or ``centers0`` ((K, 3) / (N, K, 3), ``attempts = 1``),
+    float32 distances with the lowest index winning a tie, exact integer sums, a freeze flag per attempt on the device, and the
+    attempt of the smallest float64 compactness (include/mstg_hip.h).  All attempts of all images run as parallel problems in
+    ``6 + 2 * iters`` launches, without a host synchronisation.  Returns (labels int32 (H, W) / (N, H, W) in the order of the
+    initial centres, centres float32 (K, 3) / (N, K, 3), compactness float64 () / (N,)), and with ``return_attempt`` the winning
+    attempt.  K and attempts outside 1 .. 16 raise, naming the parameter."""
+    single, x = _stage_u8(img, "image")
+    N, H, W = x.shape[:3]
+    K, attempts, iters = int(K), int(attempts), int(iters)
+    lib, dev = _lib.load(), x.device
+    need = lib.mstg_kmeans_workspace_bytes(N, K, attempts)
+    if need == 0:  # the refusal names the parameter
+        _lib.check(lib.mstg_kmeans_u8(None, N, H, W, K, attempts, iters, float(eps), None, None, None, None, None, None, None, 0, None) or -1,
+                   "mstg_kmeans_u8")
+    u = c0 = None
+    if centers0 is not None:
+        c0 = torch.as_tensor(centers0).to(device=dev, dtype=torch.float32)
+        c0 = (c0.unsqueeze(0) if c0.dim() == 2 else c0).contiguous()
+        if tuple(c0.shape) != (N, K, 3):
+            raise RuntimeError(f"mstg_hip kmeans: expected centers0 of shape {(N, K, 3)}, got {tuple(c0.shape)}")
+    else:
+        table = np.random.RandomState(int(seed)).random_sample(attempts * K * 3).astype(np.float32)
+        u = torch.from_numpy(table).to(dev)
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=dev)
+    centers = torch.empty((N, K, 3), dtype=torch.float32, device=dev)
+    comp = torch.empty(N, dtype=torch.float64, device=dev)
+    best = torch.empty(N, dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mstg_kmeans_u8(_p(x), N, H, W, K, attempts, iters, float(eps), _p(u), _p(c0), _p(labels), _p(centers), _p(comp), _p(best),
+                                  _p(ws), need, _stream()), "mstg_kmeans_u8")
+    out = (labels, centers, comp, best) if return_attempt else (labels, centers, comp)
+    return tuple(t[0] for t in out) if single else out
+
+
+def _region_args(styled_u8, orig_u8, labels, ratios):
+    single, st = _stage_u8(styled_u8, "styled image")
+    o = _same_size(orig_u8, st)
+    N, H, W = st.shape[:3]
+    lab = _req_labels(labels, (N, H, W), st.device)
+    r = np.ascontiguousarray(np.asarray(ratios, dtype=np.float64).reshape(-1))
+    return single, st, o, lab, r
+
+
+def region_blend_u8(styled_u8, orig_u8, labels, ratios=(0.8, 0.4, 0.6)) -> torch.Tensor:
+    """The region loop of ``local_style_transfer`` (advanced_transform.py:281-301) for (H, W, 3) or (N, H, W, 3) uint8 images and
+    integer labels on the GPU: ``styled * r + orig * (1 - r)`` in float64 with ``r = ratios[min(label, len(ratios) - 1)]`` (the
+    reference: 0.8, 0.4, then 0.6), clipped and truncated; a negative label gives 0.  One launch."""
+    single, st, o, lab, r = _region_args(styled_u8, orig_u8, labels, ratios)
+    N, H, W = st.shape[:3]
+    out = torch.empty_like(st)
+    _lib.check(_lib.load().mstg_region_blend_u8(_p(st), _p(o), _p(lab), N, H, W, r.ctypes.data, len(r), _p(out), _stream()), "mstg_region_blend_u8")
+    return out[0] if single else out
+
+
+def fuse_scales_u8(outputs: torch.Tensor, weights=(0.2, 0.3, 0.5), gain=1.1) -> torch.Tensor:
+    """The fusion of ``multi_scale_fusion`` (advanced_transform.py:206-215) for uint8 ``outputs`` (S, H, W, 3) or (S, N, H, W, 3)
+    on the GPU, in float32 as numpy forms it: ``x / 255``, the weighted sum in the order given, ``* gain``, clip, ``* 255``,
+    truncate; up to 8 scales.  One launch."""
+    single = outputs.dim() == 4
+    x = outputs.unsqueeze(1) if single else outputs
+    if not x.is_cuda or x.dtype != torch.uint8 or x.dim() != 5 or x.shape[4] != 3 or x.shape[1] < 1:
+        raise RuntimeError("mstg_hip advanced transform: expected uint8 (S, H, W, 3) or (S, N, H, W, 3) outputs on the GPU")
+    x = x.contiguous()
+    S, N, H, W = x.shape[:4]
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+    if len(w) != S:
+        raise RuntimeError(f"mstg_hip advanced transform: {S} scales but {len(w)} weights")
+    out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().mstg_fuse_scales_u8(_p(x), S, N, H, W, w.ctypes.data, float(gain), _p(out), _stream()), "mstg_fuse_scales_u8")
+    return out[0] if single else out
+
+
+def contrast_enhanced_finish(styled_u8: torch.Tensor, s_gain=1.2) -> torch.Tensor:
+    """``contrast_enhanced_postprocess`` of the reference (advanced_transform.py:137-166) after the plain post-process, for an
+    (H, W, 3) or (N, H, W, 3) uint8 image on the GPU: Lab, CLAHE(2.0, 8 x 8) of L, Lab -> RGB, saturation * 1.2; byte for byte
+    ``hsv_gain_u8(lab2rgb_u8(lab with clahe_u8(L))))`` in TWO launches whatever N; H and W multiples of 8."""
+    single, x = _stage_u8(styled_u8, "styled image")
+    N, H, W = x.shape[:3]
+    lib, dev = _lib.load(), x.device
+    need = lib.mstg_contrast_enhanced_finish_workspace_bytes(N, H, W)  # 0: the call below names what is wrong with the shape
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out = torch.empty_like(x)
+    _lib.check(lib.mstg_contrast_enhanced_finish(_p(x), N, H, W, _p(_lab_table(dev)), _p(_lab_inverse_table(dev)), float(s_gain), 1.0, _p(out),
+                                                 _p(ws), need, _stream()), "mstg_contrast_enhanced_finish")
+    return out[0] if single else out
+
+
+def detail_enhanced_finish(styled_u8, orig_u8, sigma=3.0, s_gain=1.2, v_gain=1.1) -> torch.Tensor:
+    """``detail_enhanced_postprocess`` of the reference (advanced_transform.py:218-258) after the plain post-process, for (H, W, 3)
+    or (N, H, W, 3) uint8 images on the GPU (an original of another size is resized first, Lanczos): the 8-bit grey of the
+    original minus its ``GaussianBlur((0, 0), 3)`` in wrapping uint8 arithmetic, half of it added to L in float32, Lab -> RGB,
+    saturation * 1.2 and value * 1.1; byte for byte the composition of the stage functions in TWO launches whatever N."""
+    single, x = _stage_u8(styled_u8, "styled image")
+    o = _same_size(orig_u8, x)
+    N, H, W = x.shape[:3]
+    lib, dev = _lib.load(), x.device
+    ksize, taps, _ = gaussian_sigma_taps(float(sigma))
+    ws = torch.empty(N * H * W, dtype=torch.int16, device=dev)
+    out = torch.empty_like(x)
+    _lib.check(lib.mstg_detail_enhanced_finish(_p(x), _p(o), N, H, W, _p(_lab_table(dev)), _p(_lab_inverse_table(dev)), taps.ctypes.data, ksize,
+                                               float(s_gain), float(v_gain), _p(out), _p(ws), ws.numel() * 2, _stream()),
+               "mstg_detail_enhanced_finish")
+    return out[0] if single else out
+
+
+def local_regions_finish(styled_u8, orig_u8, seed=0, ratios=(0.8, 0.4, 0.6), s_gain=1.2) -> torch.Tensor:
+    """``local_style_transfer`` of the reference (advanced_transform.py:261-311) after the plain post-process, for (H, W, 3) or
+    (N, H, W, 3) uint8 images on the GPU: ``kmeans_u8(orig)`` with the reference's K = 5, 10 attempts, 10 iterations and eps 1.0
+    (this build's deterministic centres from ``seed``, not OpenCV's), then the region blend and saturation * 1.2 in one launch:
+    27 launches whatever N, byte for byte ``hsv_gain_u8(region_blend_u8(styled, orig, labels))``."""
+    single, st = _stage_u8(styled_u8, "styled image")
+    o = _same_size(orig_u8, st)
+    lab = kmeans_u8(o, seed=seed)[0]
+    r = np.ascontiguousarray(np.asarray(ratios, dtype=np.float64).reshape(-1))
+    N, H, W = st.shape[:3]
+    out = torch.empty_like(st)
+    _lib.check(_lib.load().mstg_region_blend_gain_u8(_p(st), _p(o), _p(lab), N, H, W, r.ctypes.data, len(r), float(s_gain), 1.0, _p(out),
+                                                     _stream()), "mstg_region_blend_gain_u8")
+    return out[0] if single else out
+
+
+def process_advanced(model, img_u8: torch.Tensor, setting, seed=0) -> torch.Tensor:
+    """``generate_with_different_settings`` of the reference (advanced_transform.py:38-107) for ONE setting without the file I/O:
+    decoded uint8 (H, W, 3) image in, (256, 256, 3) uint8 image out.  ``setting``: 'standard' (the plain post-process), 'contrast'
+    (``contrast_enhanced_finish``), 'multi_scale' (the original at 0.5, 0.75 and 1.0 of its size by LANCZOS, each resized to
+    256 x 256, three forward passes of one image each, ``fuse_scales_u8``; a batch of three does not give the bytes of three single
+    passes (measured in tests/test_gpu_advanced_transform.py), so the three run singly as in the reference), 'detail' (``detail_enhanced_finish`` with the original
+    resized by LANCZOS) and 'regions' (``local_regions_finish``, ``seed`` for the K-means).  ``Resize((256, 256))`` is
+    ``resize_u8(..., BILINEAR)``.  Not built: the random ``ColorJitter(brightness=0.1, contrast=0.2)`` on the input of the
+    'contrast' setting (a caller passes a jittered image if it wants one) and the matplotlib comparison chart."""
+    if setting not in ADVANCED_SETTINGS:
+        raise ValueError(f"mstg_hip advanced transform: setting {setting!r} is none of {ADVANCED_SETTINGS}")
+    img = _req_u8(img_u8)
+    height, width = img.shape[:2]
+    if setting == "multi_scale":
+        inputs = [resize_u8(resize_u8(img, (int(width * s), int(height * s)), LANCZOS), (256, 256), BILINEAR) for s in (0.5, 0.75, 1.0)]
+    else:
+        inputs = [resize_u8(img, (256, 256), BILINEAR)]
+    with torch.no_grad():
+        outs = [to_u8(model(to_tensor(i).unsqueeze(0))[0]) for i in inputs]
+    if setting == "multi_scale":
+        return fuse_scales_u8(torch.stack(outs))
+    styled = outs[0]
+    if setting == "standard":
+        return styled
+    if setting == "contrast":
+        return contrast_enhanced_finish(styled)
+    orig = resize_u8(img, (256, 256), LANCZOS)
+    return detail_enhanced_finish(styled, orig) if setting == "detail" else local_regions_finish(styled, orig, seed)
