@@ -976,6 +976,69 @@ int mstg_enhanced_style_finish(const unsigned char* canvas, const unsigned char*
 int mstg_felzenszwalb_u8(const unsigned char* img, int H, int W, double scale, double sigma, int min_size, int* labels);
 
 /* ------------------------------------------------------------------------------------------------
+ * SLIC SUPERPIXELS, the DEVICE segmentation for the local style above: the `slic` method that the reference's get_segmentation_mask
+ * names (enhanced_local_style.py:65-66: skimage.segmentation.slic(img, n_segments=100, compactness=10)), per image for N images
+ * (N, H, W, 3) uint8 RGB, N images per launch, 64-bit offsets, no host step and no host synchronisation.  The algorithm is restated
+ * from its definition as recalled (tests/slic_ref.py is the same restatement in numpy); every place where the definition is THIS
+ * BUILD'S OWN says so; IT HAS NOT BEEN COMPARED WITH A SCIKIT-IMAGE BINARY.  No floating-point atomics: the updates are exact integer
+ * sums, everything else has a fixed order: bit-reproducible and independent of N.  A parameter outside what is built is refused with
+ * MSTG_E_UNSUPPORTED and a message naming it, never approximated.  An output or the workspace must not overlap an input.
+ *
+ *   1. features.  Per pixel the integers (y, x, L, a, b); L, a, b are the bytes of the 8-bit Lab of step 1 of the advanced settings
+ *        below (mstg_lab_u8; lab_table = the entries of mstg_lab_tables on the device).  THIS BUILD'S OWN: scikit-image converts
+ *        with a float64 rgb2lab.  The 8-bit form keeps every sum an exact integer, evaluates no cbrt or pow on the device and makes
+ *        the result bit-reproducible.
+ *   2. grid.  s = sqrt((double)(H * W) / n_segments); step = rint(s) (ties to even); start = floor(s / 2).  The centres are the pixels
+ *        (start + i * step, start + j * step) for all i, j >= 0 inside the image, row-major: K = ny * nx.  The initial centre is
+ *        (y, x, L, a, b) of its pixel as float32.  Refused by name: n_segments < 1; H * W <= n_segments; a side smaller than step
+ *        (scikit-image re-grids there; not built); K above MSTG_SLIC_MAX_CENTRES; H * W above MSTG_SEGMENT_MAX_PIXELS;
+ *        compactness <= 0 (or one whose square is not a finite float32).
+ *   3. ten rounds of assignment and update (max_num_iter = 10, ALWAYS ten: a round that changes nothing is a fixed point, so
+ *        scikit-image's early exit gives the same labels).  Every label starts as 0.
+ *        candidates: centre k is a candidate for pixel (y, x) iff |y - (int)cy_k| <= 2 * step and |x - (int)cx_k| <= 2 * step.
+ *        distance, float32, every operation rounded, no fused multiply-add, in exactly this order:
+ *          d = ((dy * dy + dx * dx) * ws) + ((((dL * kL) * (dL * kL) + da * da) + db * db) * wc),
+ *          ws = 1.f / (float)(step * step), wc = 1.f / (m * m) with m = (float)compactness, kL = 100.f / 255.f (the 8-bit L back on
+ *          the scale of a and b); every difference is (float)feature - centre.
+ *        choice: the pixel takes the candidate of the smallest d, among equal d the lowest k; a pixel with no candidate keeps its
+ *          label (in round 1 every pixel has one: the nearest grid row and column are at most step away).
+ *        update: per centre the exact integers n and the sums of y, x, L, a, b over its pixels; centre = (float)((double)sum /
+ *          (double)n) per feature; a centre without pixels keeps its values.
+ *        The labels are those of the tenth assignment, 0 .. K - 1; the centres (N, K, 5) float32 those of the tenth update.
+ *   4. connectivity.  THIS BUILD'S OWN: scikit-image's pass is a raster-order flood fill whose merge target and whose max_size split
+ *        depend on the visiting order; here every decision is a function of the labels alone.
+ *        Components are the 4-connected sets of equal label; a component's root is its smallest raster index r, its size n.
+ *        min_size = (int)(0.5 * ((double)(H * W) / K)) (mstg_connect_labels takes it from the caller).
+ *        A component with n < min_size and r > 0 is SMALL.  Its parent is the component of pixel r - 1, or of pixel r - W when
+ *        r % W == 0: that pixel is a 4-neighbour of r with a smaller index, so it belongs to another component with a smaller
+ *        root, and the links cannot cycle.  The owner of a component is the first component along its parent links that is not
+ *        small (the component of pixel 0 never is); sizes are not updated by merging.  The owners are numbered 1, 2, ... in
+ *        ascending order of their roots (scikit-image's start_label = 1) and every pixel gets its owner's number; count = the
+ *        number of owners <= H * W / max(min_size, 1) + 1 (integer division; every owner but that of pixel 0 has min_size pixels),
+ *        a bound the host can compute, so a caller sizes its per-segment buffers without reading count back.
+ *        Components above max_size are NOT split: not built.
+ *   Still not built: `quickshift`; the max_size split; a comparison with a scikit-image binary.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_SLIC_MAX_CENTRES 4096
+#define MSTG_SLIC_SUMS 6 /* per centre: n, sum y, x, L, a, b */
+/* Host only: step, ny and nx of step 2 (K = ny * nx); a refused shape returns its code (mstg_last_error names the value) */
+int mstg_slic_grid(int H, int W, int n_segments, int* step, int* ny, int* nx);
+/* bytes mstg_slic_u8 needs (mstg_slic_assign_u8 needs no more); 0 for a refused shape (mstg_last_error says which) */
+size_t mstg_slic_workspace_bytes(int N, int H, int W, int n_segments);
+/* steps 1 to 4: labels (N, H, W) int32 in 1 .. count, count (N) int32, both on the device; workspace 16-byte aligned.
+ * 22 launches for steps 1 to 3 and 9 + max(ceil(log16(H * W)), 1) for step 4 (13 at 256 x 256), whatever N and the image */
+int mstg_slic_u8(const unsigned char* img, int N, int H, int W, int n_segments, double compactness, const unsigned short* lab_table,
+                 int* labels, int* count, void* workspace, size_t workspace_bytes, void* stream);
+/* steps 1 to 3 only: the raw labels (N, H, W) int32 in 0 .. K - 1 and the final centres (N, K, 5) float32: y, x, L, a, b */
+int mstg_slic_assign_u8(const unsigned char* img, int N, int H, int W, int n_segments, double compactness, const unsigned short* lab_table,
+                        int* labels, float* centres, void* workspace, size_t workspace_bytes, void* stream);
+/* bytes mstg_connect_labels needs; 0 for a refused shape */
+size_t mstg_connect_labels_workspace_bytes(int N, int H, int W);
+/* step 4 on any int32 labels (N, H, W), any H, W >= 1 with H * W <= MSTG_SEGMENT_MAX_PIXELS; min_size <= 1: nothing is small */
+int mstg_connect_labels(const int* labels_in, int N, int H, int W, int min_size, int* labels_out, int* count, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The FIVE SETTINGS of the reference's advanced_transform.py (:129-311: standard, contrast, multi-scale fusion, detail, K-means
  * regions) between the forward pass and the encoder, on the device for N images (N, H, W, 3) uint8 RGB, any H, W >= 1 unless
  * stated, N images per launch, 64-bit offsets.  The OpenCV steps are restated from the definitions below, as recalled, not

@@ -7,7 +7,10 @@ Differences from the reference, on purpose: ``get_segmentation_mask`` builds 'fe
 NotImplementedError by name); equal edge costs of the segmentation keep their order (a stable sort; scikit-image leaves them as
 numpy's unstable sort does), so labels can differ from scikit-image's where costs tie; ``analyze_segments`` reports the hue and
 value means of ``avg_color_hsv`` as NaN (the device record holds the saturation sum, the only one the ratio reads); and no
-comparison chart is written (the reference's ``create_comparison`` needs matplotlib).  The OpenCV and scikit-image steps are
+comparison chart is written (the reference's ``create_comparison`` needs matplotlib); ``enhanced_local_style_transfer`` and the
+command line take ``segmentation`` / ``--segmentation``: 'felzenszwalb' (the reference's choice, the default) or 'slic', the
+device segmentation ``mstg_hip.image.slic_labels`` (8-bit Lab features and a connectivity step of this build's own), with which the
+whole call stays on the GPU.  The OpenCV and scikit-image steps are
 restated from their definitions (include/mstg_hip.h) and have not been compared with an OpenCV or scikit-image binary.
 """
 from __future__ import annotations
@@ -111,10 +114,11 @@ def determine_blend_ratios(segment_stats, segments, img_shape):
     return dimg.gaussian_reflect_f32(torch.from_numpy(blend_map).to("cuda")).cpu().numpy()
 
 
-def enhanced_local_style_transfer(model, img_path, output_path, device):
-    """:178-292 without the comparison chart: decode, ``mstg_hip.image.process_enhanced_local_style``, encode -> PIL image"""
+def enhanced_local_style_transfer(model, img_path, output_path, device, segmentation="felzenszwalb"):
+    """:178-292 without the comparison chart: decode, ``mstg_hip.image.process_enhanced_local_style``, encode -> PIL image.
+    ``segmentation``: 'felzenszwalb' (on the host) or 'slic' (on the device)."""
     original = Image.open(img_path).convert("RGB")
-    out = dimg.process_enhanced_local_style(model, _u8(original, device))
+    out = dimg.process_enhanced_local_style(model, _u8(original, device), segmentation=segmentation)
     final_img = Image.fromarray(out.cpu().numpy())
     if os.path.dirname(output_path):
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
@@ -123,20 +127,26 @@ def enhanced_local_style_transfer(model, img_path, output_path, device):
     return final_img
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser(description="segmentation-driven local style transfer")
     parser.add_argument("--image", type=str, required=True, help="input image")
     parser.add_argument("--model", type=str, required=True, help="checkpoint file")
     parser.add_argument("--output", type=str, default="output/enhanced_local_style.jpg", help="output image")
     parser.add_argument("--channels", type=int, default=16, help="model channels")
     parser.add_argument("--blocks", type=int, default=1, help="transformer blocks")
-    args = parser.parse_args(argv)
+    parser.add_argument("--segmentation", choices=dimg.SEGMENTATIONS, default="felzenszwalb",
+                        help="felzenszwalb: the reference's, on the host; slic: on the device")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("enhanced_local_style: no GPU; this build has no CPU path")
     device = torch.device("cuda")
     print(f"device: {device}")
     model, _ = load_model(args.model, device, args.channels, args.blocks)
-    enhanced_local_style_transfer(model, args.image, args.output, device)
+    enhanced_local_style_transfer(model, args.image, args.output, device, args.segmentation)
 
 
 if __name__ == "__main__":

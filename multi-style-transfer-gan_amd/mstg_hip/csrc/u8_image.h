@@ -1,5 +1,5 @@
 // Device and host helpers shared by the 8-bit image filters (local_style.hip, standard_mode.hip, app_local_style.hip,
-// color_blocks.hip, segment_style.hip, advanced_transform.hip).  Every device helper is a bit-exact restatement of an OpenCV / numpy
+// color_blocks.hip, segment_style.hip, advanced_transform.hip, slic.hip).  Every device helper is a bit-exact restatement of an OpenCV / numpy
 // definition; a primitive that more than one of those files uses is defined HERE, once, so that a fix reaches every user (DESIGN.md,
 // "Shared 8-bit image helpers").  All __forceinline__: a kernel compiles to the code it had with the body written out in place.
 #pragma once

@@ -1211,6 +1211,90 @@ def felzenszwalb_labels(img, scale=100, sigma=0.5, min_size=50) -> np.ndarray:
     return labels
 
 
+SEGMENTATIONS = ("felzenszwalb", "slic")
+
+
+def slic_grid(H, W, n_segments=100):
+    """(step, ny, nx) of the SLIC grid of an (H, W) image as include/mstg_hip.h defines it (K = ny * nx centres), from the host
+    entry ``mstg_slic_grid``; a shape that is not built raises, naming the value."""
+    out = np.zeros(3, dtype=np.int32)
+    at = out.ctypes.data
+    _lib.check(_lib.load().mstg_slic_grid(int(H), int(W), int(n_segments), at, at + 4, at + 8), "mstg_slic_grid")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def slic_min_size(H, W, n_segments=100):
+    """the connectivity step's ``min_size`` for the SLIC grid of (H, W): ``int(0.5 * (H * W / K))``"""
+    _, ny, nx = slic_grid(H, W, n_segments)
+    return int(0.5 * (float(H * W) / float(ny * nx)))
+
+
+def slic_segment_bound(H, W, n_segments=100):
+    """The most segments ``slic_labels`` can return for an (H, W) image: ``H * W // max(min_size, 1) + 1`` (every segment but the
+    first pixel's has at least ``min_size`` pixels).  Computed on the host, so a caller sizes per-segment buffers without reading
+    the count back; the labels are 1 .. count, so ``segment_blend_map`` takes ``num_segments = bound + 1``."""
+    return int(H) * int(W) // max(slic_min_size(H, W, n_segments), 1) + 1
+
+
+def _slic_call(entry, img_u8, n_segments, compactness, extra):
+    single, x = _stage_u8(img_u8, "image")
+    N, H, W = x.shape[:3]
+    lib = _lib.load()
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=x.device)
+    need = lib.mstg_slic_workspace_bytes(N, H, W, int(n_segments))  # 0: the call below names what is wrong
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    out = extra(N, H, W, x.device)
+    _lib.check(getattr(lib, entry)(_p(x), N, H, W, int(n_segments), float(compactness), _p(_lab_table(x.device)), _p(labels), _p(out), _p(ws),
+                                   need, _stream()), entry)
+    return single, labels, out
+
+
+def slic_labels(img_u8, n_segments=100, compactness=10.0, return_count=False):
+    """``skimage.segmentation.slic(img, n_segments, compactness)`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU as
+    include/mstg_hip.h defines it -> int32 (H, W) / (N, H, W) on the device, labels 1 .. count; with ``return_count`` also the
+    count, an int32 tensor () / (N,) on the device.  The features are this build's 8-bit Lab and the connectivity step is this
+    build's own (see the header); ten rounds, no host step and no host synchronisation; bit-reproducible.  A shape that is not
+    built raises, naming the value.  Not compared with scikit-image."""
+    single, labels, count = _slic_call("mstg_slic_u8", img_u8, n_segments, compactness,
+                                       lambda N, H, W, dev: torch.empty((N,), dtype=torch.int32, device=dev))
+    if single:
+        labels, count = labels[0], count[0]
+    return (labels, count) if return_count else labels
+
+
+def slic_assign(img_u8, n_segments=100, compactness=10.0):
+    """The ten rounds of assignment and update alone (steps 1 to 3 of the header) -> (raw labels int32 (H, W) / (N, H, W) in
+    0 .. K - 1, centres float32 (K, 5) / (N, K, 5): y, x, L, a, b after the last update), on the device."""
+    def centres_of(N, H, W, dev):
+        _, ny, nx = slic_grid(H, W, n_segments)
+        return torch.empty((N, ny * nx, 5), dtype=torch.float32, device=dev)
+
+    single, labels, centres = _slic_call("mstg_slic_assign_u8", img_u8, n_segments, compactness, centres_of)
+    return (labels[0], centres[0]) if single else (labels, centres)
+
+
+def connect_labels(labels, min_size, return_count=False):
+    """The connectivity step alone (step 4 of the header) on any integer labels (H, W) / (N, H, W) (numpy or tensor) on ``cuda`` ->
+    int32 labels 1 .. count of the same shape on the device: 4-connected components, every component smaller than ``min_size``
+    joined to the component of the pixel before its first pixel, the rest numbered in raster order of their first pixels."""
+    lab = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
+    lab = lab.to(device=lab.device if lab.is_cuda else "cuda", dtype=torch.int32).contiguous()
+    single = lab.dim() == 2
+    if single:
+        lab = lab.unsqueeze(0)
+    if lab.dim() != 3:
+        raise RuntimeError(f"mstg_hip segmentation: expected labels of shape (H, W) or (N, H, W), got {tuple(lab.shape)}")
+    N, H, W = lab.shape
+    lib = _lib.load()
+    out, count = torch.empty_like(lab), torch.empty((N,), dtype=torch.int32, device=lab.device)
+    need = lib.mstg_connect_labels_workspace_bytes(N, H, W)  # 0: the call below names what is wrong
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=lab.device)
+    _lib.check(lib.mstg_connect_labels(_p(lab), N, H, W, int(min_size), _p(out), _p(count), _p(ws), need, _stream()), "mstg_connect_labels")
+    if single:
+        out, count = out[0], count[0]
+    return (out, count) if return_count else out
+
+
 def _req_labels(labels, shape, device):
     lab = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
     lab = lab.to(device=device, dtype=torch.int32).contiguous()
@@ -1361,20 +1445,27 @@ def letterbox_black(img_u8: torch.Tensor, target=256):
     return paste_u8(resized, (0, 0, new_height, new_width), (target, target), (off_y, off_x), fill=0), (width, height)
 
 
-def process_enhanced_local_style(model, img_u8: torch.Tensor, segments=None, target=256) -> torch.Tensor:
+def process_enhanced_local_style(model, img_u8: torch.Tensor, segments=None, target=256, segmentation="felzenszwalb") -> torch.Tensor:
     """``enhanced_local_style_transfer`` of the reference (enhanced_local_style.py:178-292) without the file I/O and the chart:
     decoded uint8 image in, uint8 image out.  The letterbox on black, the forward pass, ``segment_blend_map`` of the canvas with
     ``segments`` (integer labels (target, target); None: ``felzenszwalb_labels(canvas)``, the one host step), ``enhanced_style_finish``,
     the crop of :270-277 exactly as written (its ``min(target, int(...))`` sizes leave an image larger than the canvas in both
-    directions uncropped) and the LANCZOS resize back under the condition of :280."""
+    directions uncropped) and the LANCZOS resize back under the condition of :280.  ``segmentation="slic"``: ``slic_labels(canvas)``
+    in the place of the host step; the labels stay on the device and the map gets ``slic_segment_bound`` for its size, so nothing
+    leaves the device and nothing synchronises.  ``segments``, when given, wins."""
+    if segmentation not in SEGMENTATIONS:
+        raise ValueError(f"mstg_hip image: segmentation {segmentation!r} is none of {SEGMENTATIONS}")
     canvas, (width, height) = letterbox_black(img_u8, target)
     x = to_tensor(canvas).unsqueeze(0)
     with torch.no_grad():
         y = model(x)
     styled = to_u8(y[0])
-    if segments is None:
+    num_segments = None
+    if segments is None and segmentation == "slic":
+        segments, num_segments = slic_labels(canvas), slic_segment_bound(target, target) + 1  # labels 1 .. count <= bound
+    elif segments is None:
         segments = felzenszwalb_labels(canvas)
-    blend_map = segment_blend_map(canvas, segments)
+    blend_map = segment_blend_map(canvas, segments, num_segments)
     out = enhanced_style_finish(canvas, styled, blend_map)
     if width != height:
         new_width = min(target, int(height * (width / height)))
