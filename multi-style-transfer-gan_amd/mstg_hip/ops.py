@@ -213,7 +213,15 @@ def _kernel_name(d: ConvDesc, which: int) -> str:
 #   * torch in-place ops on the parameter (load_state_dict, p.copy_, ...)         -> p._version
 #   * torch in-place ops on the optimizer's flat buffer it is a view of             -> flat._version (FlatAdam sets p._mstg_flat)
 #   * raw-pointer writers: the fused Adam step, the DP broadcast of the flat buffer -> PACK_EPOCH, bumped by those call sites
-#   * p.data re-homed (module.to / .half / a new FlatAdam)                          -> data_ptr
+#   * p.data re-homed (module.to / .half / a new FlatAdam)                          -> data_ptr.  Re-homing moves no version counter,
+#     and the allocator likes to hand the block just freed to the next tensor of its size (module.half().float() lands on the old
+#     address with other values), so every cache entry keeps an alias of the storages it was packed from: while the entry lives,
+#     nothing else can be given their addresses, and an equal data_ptr means the same memory
+# NOT seen by the stamp, so the layer goes on with the old pack and reports nothing:
+#   * in-place ops through .data (p.data.mul_(2), p.data.copy_(w)): that alias has a version counter of its own and p._version
+#     does not move (p.detach() shares the counter and is seen)
+#   * raw-pointer writes by anything other than the call sites above (a foreign kernel or collective handed p.data_ptr())
+#   After either, call bump_pack_epoch(); or write through the parameter itself (with torch.no_grad(): p.mul_(2)).
 # The cache dies with the parameter object (no address-reuse hazard), is per stream (the two halves of the train step never share
 # a workspace) and is never used for tensors that are not Parameters (the discriminator's W / sigma temporaries).
 # MSTG_NO_PACK_CACHE=1 switches it off.
@@ -230,6 +238,11 @@ def _pack_stamp(owners):
                  for t in owners) + (PACK_EPOCH[0],)
 
 
+def _pack_storages(owners):
+    """Aliases that keep the owners' present storages allocated (see 'p.data re-homed' above)."""
+    return tuple(None if t is None else t.data for t in owners)
+
+
 def _cached_ws(owners, kind, dkey, nbytes: int, device):
     """(workspace, 1 if it still holds this call's filter pack else 0)"""
     if (not owners or owners[0] is None or os.environ.get("MSTG_NO_PACK_CACHE", "0") == "1"
@@ -242,12 +255,13 @@ def _cached_ws(owners, kind, dkey, nbytes: int, device):
     if ent is not None and ent[2] == stream and ent[0].numel() * 4 >= nbytes:
         if ent[1] == stamp:
             return ent[0], 1
-        packs[key] = (ent[0], stamp, stream)  # same stream: the re-pack is ordered behind every launch that still reads the old one
+        # same stream: the re-pack is ordered behind every launch that still reads the old one
+        packs[key] = (ent[0], stamp, stream, _pack_storages(owners))
         return ent[0], 0
     # first use, or a use from ANOTHER stream than the last one (launches of the other stream may still read the old workspace:
     # it is left alone and dropped; in steady state a layer always runs on the same stream)
     ws = _ws(nbytes, device)
-    packs[key] = (ws, stamp, stream)
+    packs[key] = (ws, stamp, stream, _pack_storages(owners))
     return ws, 0
 
 
@@ -392,7 +406,10 @@ class ConvFn(torch.autograd.Function):
             src = getattr(ctx, "norm_src", None)
             if src is not None and conv_dgrad_bsums_supported(d):
                 # x was ReLU(InstanceNorm(src[0])): the reductions of that norm's backward come out of this launch's epilogue
-                dx._mstg_bsums = (conv_dgrad_bsums_raw(d, dy, w, dx, src[0], src[1], owners=(ctx.prefs[0],)), src[2])
+                # (dx._version: when the norm's output has another consumer, autograd adds that gradient into this very tensor in
+                # place and the attribute stays on it; the sums then cover one share only and the norm's backward must not use them)
+                sums = conv_dgrad_bsums_raw(d, dy, w, dx, src[0], src[1], owners=(ctx.prefs[0],))
+                dx._mstg_bsums = (sums, src[2], dx._version)
             else:
                 conv_dgrad_raw(d, dy, w, dx, owners=(ctx.prefs[0],))
         want_db = ctx.has_bias and ctx.needs_input_grad[2]
@@ -692,8 +709,10 @@ class InstNormActFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             got = getattr(dy, "_mstg_bsums", None)
-            if got is not None and getattr(ctx, "token", None) is not None and got[1] is ctx.token and ctx.act == ACT_RELU:
-                # the consumer convolution's input-gradient launch already summed what this backward reduces (ConvFn.backward)
+            if (got is not None and getattr(ctx, "token", None) is not None and got[1] is ctx.token and got[2] == dy._version
+                    and ctx.act == ACT_RELU):
+                # the consumer convolution's input-gradient launch already summed what this backward reduces (ConvFn.backward), and
+                # nothing was added to that gradient since (a second consumer of this norm's output: the sums miss its share)
                 _timed("norm_apply_kernel<true>", 0, 4 * x.numel() * 3, lambda: _lib.check(
                     lib.mstg_norm_bwd_apply(_p(x), _p(stats), _p(dy), _p(got[0]), 1, _p(dx), N, H * W, Cn, ACT_RELU, _stream()),
                     "mstg_norm_bwd_apply"))
