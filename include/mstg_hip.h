@@ -1168,6 +1168,101 @@ int mstg_detail_enhanced_finish(const unsigned char* styled, const unsigned char
                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * FRECHET DISTANCE of two feature sets: calculate_fid of the reference's m_test.py (:37-50), its only evaluation of a trained model,
+ * without the InceptionV3 that feeds it.  X1 (n1, d) and X2 (n2, d), float32 or float64, row-major on the device.  Everything below is
+ * float64 on the device, every operation rounded (no contraction outside the MFMA), every order fixed: two runs give the same bits.
+ * No floating-point atomics, no host synchronisation, no workgroup waits on another.
+ *
+ *   1. x = (double)X.  Converting float32 features BEFORE the mean is THIS BUILD'S: the reference's mean(0) of float32 features stays
+ *        in float32 (np.cov converts first, as here).
+ *   2. mu[c] = (s0 + s1 + s2 + s3) / n, s_g = the sum of x[r][c] over the rows r = g, g + 4, g + 8, ... in ascending order, the four
+ *        added left to right.
+ *   3. A[r][c] = (x1[r][c] - mu1[c]) * (1 / sqrt(n1 - 1)), B likewise from X2: A^T A and B^T B are np.cov(rowvar=False).
+ *   4. per column: e[c] = (mu1[c] - mu2[c])^2, a[c] = sum of A[r][c]^2, b[c] = sum of B[r][c]^2, both in the row order of step 2.
+ *        ssdiff, tr1, tr2 = the sums of e, a, b over the columns: thread t of 256 adds the columns t, t + 256, ..., a butterfly over
+ *        each wave of 64, the four waves left to right.  tr1 = tr S1 and tr2 = tr S2.
+ *   5. M = A B^T (n1 x n2) on v_mfma_f64_16x16x4_f64: a 16 x 16 tile of M per workgroup; wave w of 4 runs the K steps k0 = 4 w,
+ *        4 w + 16, ... in ascending order (each step is one instruction over the features k0 .. k0 + 3, zeros past d and past the last
+ *        row), the four partial tiles are added left to right.
+ *   6. The nuclear norm of M.  tr sqrtm(S1 S2) of the reference equals it: S1 S2 = A^T (A B^T) B has the nonzero eigenvalues of
+ *        M M^T, and the trace of the square root is the sum of their square roots.  (The d x d product is never formed; for
+ *        d = 2048 and 100 samples it has rank 99 at most, and sqrtm's result on it is noise above that.)  One-sided (Hestenes) Jacobi,
+ *        THIS BUILD'S choice, on G = M if n2 <= n1, else M^T: p rows, q = min(n1, n2) columns.
+ *          pairing: cyclic round robin of q' = q rounded up to even players, q' - 1 rounds a sweep; slot 0 of round r pairs q' - 1
+ *          with r, slot i > 0 pairs (r + i) mod (q' - 1) with (r - i) mod (q' - 1); the lower index is a, the higher b; a pair with
+ *          the phantom column q (odd q) is a bye.  The pairs of a round touch disjoint columns and run side by side.
+ *          pair: alpha = g_a . g_a, beta = g_b . g_b, gamma = g_a . g_b (lane l of 16 adds the rows l, l + 16, ..., then a butterfly);
+ *          bar = tol * (sqrt(alpha) * sqrt(beta)), tol = DBL_EPSILON * sqrt(p); |gamma| <= bar: the pair is settled; a NaN on either
+ *          side: the pair is UNDECIDED and does not rotate; else
+ *          zeta = (beta - alpha) / (2 gamma), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (0 for a non-finite zeta),
+ *          c = 1 / sqrt(1 + t^2), s = c t, g_a' = c g_a - s g_b, g_b' = s g_a + c g_b.
+ *          end: after the first sweep without a rotation (converged if that sweep met no undecided pair, else not), or after
+ *          MSTG_FRECHET_MAX_SWEEPS sweeps (not converged).
+ *          sigma_j = sqrt(g_j . g_j), sorted descending; nuclear = their sum from the largest down.
+ *        One workgroup runs a problem; G lives in LDS when p * q <= 16384 doubles, else in the workspace.
+ *        MSTG_FRECHET_MAX_SWEEPS is MEASURED: tests/fid_ref.py runs this Jacobi in numpy; over the shapes of tests/test_m_test_cpu.py
+ *        (up to (256, 256, 32), float32 and float64 draws, identical sets, a constant column) the largest count is 22 sweeps; the
+ *        bound is twice that.  M of centred factors always has a null space, which is what takes the sweeps.  Non-finite features
+ *        give non-finite outputs and converged = 0 after at most that many sweeps, never a hang.
+ *   7. fid = ((ssdiff + tr1) + tr2) - 2 nuclear.
+ *   out = {ssdiff, tr1, tr2, nuclear, fid}; info = {sweeps used, converged (1 / 0)}.  Four launches.
+ *   Refused by name before any launch: n1 or n2 below 2, d below 1 (MSTG_E_BADARG); min(n1, n2) above MSTG_FRECHET_MAX_SAMPLES
+ *   (MSTG_E_UNSUPPORTED: the d x d form, which more samples than that need, is not built; the reference uses 100); a product
+ *   n1 d, n2 d or n1 n2 that does not fit 31 bits; null pointers; a workspace that is null or too small (MSTG_E_WORKSPACE).
+ *   Not built: InceptionV3 (its weights come from the network), so run_model needs the caller's feature extractor.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_FRECHET_MAX_SAMPLES 256
+#define MSTG_FRECHET_MAX_SWEEPS 44
+/* bytes mstg_frechet_distance needs: (n1 d + n2 d + 3 d + 2 n1 n2 + min(n1, n2) + 1) doubles; 0 for a refused shape (mstg_last_error
+ * says which) */
+size_t mstg_frechet_workspace_bytes(int n1, int n2, int d);
+/* x1, x2: float64 if is_f64 != 0, else float32; out[5], info[2], workspace 8-byte aligned */
+int mstg_frechet_distance(const void* x1, const void* x2, int is_f64, int n1, int n2, int d, double* out, int* info, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* bytes mstg_singular_values needs: (m n + 1) doubles; 0 for a refused shape */
+size_t mstg_singular_values_workspace_bytes(int m, int n);
+/* step 6 alone on M (m, n) float64 row-major, min(m, n) <= MSTG_FRECHET_MAX_SAMPLES: sigma[min(m, n)] descending, info[2]; one launch */
+int mstg_singular_values(const double* M, int m, int n, double* sigma, int* info, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * DISPLAY FINISH: process_image of the reference's m_test.py (:52-78), which runs twice per test image: gamma 1.1, the cast to bytes,
+ * the 8-bit COLOR_RGB2YUV, equalizeHist of Y, the 8-bit COLOR_YUV2RGB.  N images per launch, any H, W >= 1, H * W * 3 below 2^31,
+ * 64-bit offsets.  The OpenCV steps are restated as recalled, not compared with an OpenCV binary (tests/display_finish_ref.py is
+ * the same restatement in numpy).  `out` and the workspace must not overlap an input (MSTG_E_BADARG).
+ *
+ *   1. gamma (:58-71): y (N, 3, H, W) float32 or float16, the generator's output -> bytes (N, H, W, 3).
+ *        v = (float)y * 0.5f + 0.5f in float32;
+ *        v = v > 0 ? (v < 1 ? v : 1) : 0: the clamp to [0, 1] is THIS BUILD'S (a NaN gives 0); the reference raises a negative v to
+ *        the power, gets a NaN and casts that to a byte, which C leaves undefined;
+ *        p = (float)pow((double)v, gamma), gamma a double in (0, 16] (the reference: 1.1);
+ *        byte = (uint8)(p * 255.f), one float32 product, truncated.
+ *        pow is the device library's; the GPU test asserts first that no input of it lies within 64 double ulps of a float32
+ *        rounding midpoint, four times OpenCL's bound for pow.
+ *   2. the 8-bit COLOR_RGB2YUV (:71), 14-bit fixed point, arithmetic shifts, constants as recalled:
+ *        Y = (4899 R + 9617 G + 1868 B + 8192) >> 14;
+ *        U = sat_u8((8061 (B - Y) + (128 << 14) + 8192) >> 14);  V = sat_u8((14369 (R - Y) + (128 << 14) + 8192) >> 14).
+ *   3. equalizeHist of Y (:72), per image: hist = the 256-bin histogram (integer atomics in LDS; the chunks of an image are added
+ *        in ascending order); i0 = the first non-empty bin; if hist[i0] = H W the plane is constant and stays as it is; else
+ *        scale = 255.f / (float)(H W - hist[i0]) (one float32 division), lut[i] = 0 for i <= i0 and
+ *        lut[i] = sat_u8(cvRound((float)(hist[i0 + 1] + ... + hist[i]) * scale)) above it (one float32 product, round half to even).
+ *   4. the 8-bit COLOR_YUV2RGB (:73) of (lut[Y], U, V), constants as recalled, u = U - 128, v = V - 128:
+ *        B = sat_u8(Y + ((33292 u + 8192) >> 14));  G = sat_u8(Y + ((-6472 u - 9519 v + 8192) >> 14));
+ *        R = sat_u8(Y + ((18678 v + 8192) >> 14)).
+ *   Steps 2 to 4 take three launches whatever N (the histograms; the tables; one point-wise kernel).  The reference's / 255.0 and
+ *   clip to [0, 1] are the Python side's (m_test.py's process_image here).
+ *   Steps 2 to 4 are also the colour step of the reference's `advanced` local-style mode (batch_process_images.py:391-393), which is
+ *   broken there and stays refused here: nothing calls them from that mode.
+ *   Not built: a comparison with an OpenCV binary; the matplotlib figures.
+ * ---------------------------------------------------------------------------------------------- */
+/* step 1; one launch */
+int mstg_gamma_u8(const void* y, int is_half, int N, int H, int W, double gamma, unsigned char* out, void* stream);
+/* bytes mstg_equalize_luma_u8 needs: N * chunks * 256 ints and N * 256 bytes, chunks = min(ceil(H W / 4096), 256); 0 for an invalid shape */
+size_t mstg_equalize_luma_workspace_bytes(int N, int H, int W);
+/* steps 2 to 4 on (N, H, W, 3) bytes; workspace 4-byte aligned; three launches */
+int mstg_equalize_luma_u8(const unsigned char* in, int N, int H, int W, unsigned char* out, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * BUILD-DEFINED StructuralTransformerBlock pieces. The reference imports the class from a file its snapshot does not contain
  * (enhanced_generator.py:4; call shape :115, :218-225) -- parity unpinned; definition in structural_transformer.py.
  * The block's Linear layers go through mstg_conv2d_* (a Linear over tokens (N, L, dim) is a 1x1 convolution on NHWC).

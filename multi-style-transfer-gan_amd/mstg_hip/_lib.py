@@ -248,8 +248,16 @@ SIGNATURES = {
     "mstg_contrast_enhanced_finish_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_contrast_enhanced_finish": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _sz, _vp]),
     "mstg_detail_enhanced_finish": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _sz, _vp]),
+    "mstg_frechet_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_frechet_distance": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_singular_values_workspace_bytes": (_sz, [_i, _i]),
+    "mstg_singular_values": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_gamma_u8": (_i, [_vp, _i, _i, _i, _i, C.c_double, _vp, _vp]),
+    "mstg_equalize_luma_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_equalize_luma_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
+FRECHET_MAX_SAMPLES, FRECHET_MAX_SWEEPS = 256, 44  # MSTG_FRECHET_MAX_SAMPLES, MSTG_FRECHET_MAX_SWEEPS
 APP_EDGE_KSIZE = 21  # MSTG_APP_EDGE_KSIZE
 LOCAL_STYLE_MAX_PIXELS = 147456  # MSTG_LOCAL_STYLE_MAX_PIXELS
 BILATERAL_COLOR_WEIGHTS, BILATERAL_MAX_TAPS = 768, 49  # MSTG_BILATERAL_COLOR_WEIGHTS, MSTG_BILATERAL_MAX_TAPS

@@ -1707,3 +1707,41 @@ def process_advanced(model, img_u8: torch.Tensor, setting, seed=0) -> torch.Tens
         return contrast_enhanced_finish(styled)
     orig = resize_u8(img, (256, 256), LANCZOS)
     return detail_enhanced_finish(styled, orig) if setting == "detail" else local_regions_finish(styled, orig, seed)
+
+
+# ---- the display finish of the reference's m_test.py (csrc/display_finish.hip) -------------------------------------------------------
+def gamma_u8(y: torch.Tensor, gamma=1.1) -> torch.Tensor:
+    """The head of ``process_image`` (m_test.py:58-71) on the GPU: (3, H, W) or (N, 3, H, W) float32 / float16 generator output ->
+    (N, H, W, 3) uint8: ``v = y * 0.5 + 0.5`` in float32, clamped to [0, 1] (this build's: the reference raises a negative value to
+    the power and casts the NaN; here a NaN gives 0), ``(float)pow((double)v, gamma)``, ``* 255`` in float32, truncated.  One launch."""
+    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dim() not in (3, 4) or y.shape[-3] != 3:
+        raise RuntimeError("mstg_hip image: expected a (3, H, W) or (N, 3, H, W) tensor on the GPU")
+    if y.dtype not in (torch.float32, torch.float16):
+        raise RuntimeError(f"mstg_hip image: gamma_u8 takes float32 or float16, got {y.dtype}")
+    x = (y.unsqueeze(0) if y.dim() == 3 else y).contiguous()
+    if x.shape[0] < 1:
+        raise RuntimeError("mstg_hip image: gamma_u8 needs at least one image")
+    N, _, H, W = x.shape
+    out = torch.empty((N, H, W, 3), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().mstg_gamma_u8(_p(x), int(x.dtype == torch.float16), N, H, W, float(gamma), _p(out), _stream()), "mstg_gamma_u8")
+    return out
+
+
+def equalize_luma_u8(img_u8: torch.Tensor) -> torch.Tensor:
+    """``cv2.cvtColor(img, COLOR_RGB2YUV)``, ``cv2.equalizeHist`` of Y, ``cv2.cvtColor(..., COLOR_YUV2RGB)`` (m_test.py:71-73) of an
+    (H, W, 3) or (N, H, W, 3) uint8 image on the GPU, each image with its own histogram: OpenCV's 8-bit integer paths as
+    include/mstg_hip.h defines them; three launches whatever N.  Restated as recalled, not compared with an OpenCV binary."""
+    single, x = _stage_u8(img_u8, "image")
+    N, H, W = x.shape[:3]
+    lib = _lib.load()
+    out = torch.empty_like(x)
+    nbytes = lib.mstg_equalize_luma_workspace_bytes(N, H, W)  # 0 for a bad shape: the call below names what is wrong
+    ws = torch.empty(max(nbytes // 4 + 1, 1), dtype=torch.int32, device=x.device)
+    _lib.check(lib.mstg_equalize_luma_u8(_p(x), N, H, W, _p(out), _p(ws), ws.numel() * 4, _stream()), "mstg_equalize_luma_u8")
+    return out[0] if single else out
+
+
+def display_finish(y: torch.Tensor, gamma=1.1) -> torch.Tensor:
+    """``process_image`` of the reference's m_test.py (:52-78) up to its bytes: ``equalize_luma_u8(gamma_u8(y, gamma))``, (N, H, W, 3)
+    uint8 for (3, H, W) or (N, 3, H, W) generator output; four launches whatever N.  The reference's ``/ 255.0`` is the caller's."""
+    return equalize_luma_u8(gamma_u8(y, gamma))

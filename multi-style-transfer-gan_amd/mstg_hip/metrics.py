@@ -3,6 +3,8 @@ image pairs as compare_image_quality.py:14-33, image_quality_comparison.py:11-34
 improved_image_compare.py:8-27 compute them (images / 255, ``np.mean((a - b) ** 2)``, skimage ``peak_signal_noise_ratio`` and
 ``structural_similarity(channel_axis=2)`` with ``data_range=1.0``).  The images stay on the GPU, e.g. straight from
 ``image.process_cyclegan``; only ``calculate_metrics`` and ``evaluate_pairs`` bring numbers to the host, once per call.
+Below them the Frechet distance of two feature sets as the reference's m_test.py:37-50 computes it (csrc/frechet.hip):
+``frechet_distance``, its Jacobi SVD alone (``singular_values``) and ``calculate_fid`` with the reference's signature.
 """
 from __future__ import annotations
 
@@ -108,3 +110,85 @@ def evaluate_pairs(pairs):
     n = len(results)
     averages = {k: sum(r[k] for r in results) / n for k in ("mse", "psnr", "ssim")}
     return results, averages
+
+
+# ---- the Frechet distance of the reference's m_test.py (csrc/frechet.hip) ------------------------------------------------------------
+MAX_SAMPLES, MAX_SWEEPS = _lib.FRECHET_MAX_SAMPLES, _lib.FRECHET_MAX_SWEEPS
+
+
+def _req_features(t, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"mstg_hip metrics: {name} must be a torch tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise RuntimeError(f"mstg_hip metrics: {name} must live on the GPU, got a {t.device} tensor")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"mstg_hip metrics: {name} must be float32 or float64, got {t.dtype}")
+    if t.dim() != 2:
+        raise RuntimeError(f"mstg_hip metrics: {name} must be (n, d), got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _frechet_launch(real: torch.Tensor, fake: torch.Tensor):
+    """-> (out (5,) float64 cuda {ssdiff, tr1, tr2, nuclear, fid}, info (2,) int32 cuda {sweeps, converged})"""
+    a, b = _req_features(real, "real"), _req_features(fake, "fake")
+    if a.dtype != b.dtype or a.device != b.device:
+        raise RuntimeError(f"mstg_hip metrics: feature sets differ in dtype or device: {a.dtype} {a.device} vs {b.dtype} {b.device}")
+    if a.shape[1] != b.shape[1]:
+        raise RuntimeError(f"mstg_hip metrics: feature widths differ, {a.shape[1]} vs {b.shape[1]}")
+    lib = _lib.load()
+    n1, n2, d = a.shape[0], b.shape[0], a.shape[1]
+    out = torch.empty(5, dtype=torch.float64, device=a.device)
+    info = torch.empty(2, dtype=torch.int32, device=a.device)
+    nbytes = lib.mstg_frechet_workspace_bytes(n1, n2, d)  # 0 for a refused shape: the call below names what is wrong
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=a.device)
+    _lib.check(lib.mstg_frechet_distance(_p(a), _p(b), int(a.dtype == torch.float64), n1, n2, d, _p(out), _p(info), _p(ws), ws.numel() * 8,
+                                         _stream()), "mstg_frechet_distance")
+    return out, info
+
+
+def frechet_distance(real: torch.Tensor, fake: torch.Tensor, return_parts=False):
+    """``calculate_fid`` of the reference's m_test.py (:37-50) for (n1, d) and (n2, d) float32 or float64 feature sets on the GPU,
+    in float64 throughout: ``|mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr sqrtm(S1 S2)`` with the last trace taken as the nuclear norm of
+    ``A B^T`` (A, B the centred features over sqrt(n - 1)), found by a one-sided Jacobi SVD (include/mstg_hip.h).  Returns the
+    distance as a 0-dim float64 cuda tensor; with ``return_parts`` a dict of 0-dim tensors ``ssdiff``, ``tr1``, ``tr2``, ``nuclear``,
+    ``fid`` and the int32 tensor ``info`` = (sweeps used, converged).  No host synchronisation: the caller reads ``info``.
+    ``min(n1, n2)`` above ``MAX_SAMPLES`` is refused (the d x d form is not built)."""
+    out, info = _frechet_launch(real, fake)
+    if return_parts:
+        return {"ssdiff": out[0], "tr1": out[1], "tr2": out[2], "nuclear": out[3], "fid": out[4], "info": info}
+    return out[4]
+
+
+def singular_values(M: torch.Tensor, return_info=False):
+    """The singular values of a float64 (m, n) cuda matrix, descending, by the one-sided Jacobi of ``frechet_distance`` alone
+    (``min(m, n)`` at most ``MAX_SAMPLES``); one launch, no host synchronisation.  ``return_info``: also the int32 tensor
+    (sweeps used, converged)."""
+    if not isinstance(M, torch.Tensor) or not M.is_cuda or M.dtype != torch.float64 or M.dim() != 2:
+        raise RuntimeError("mstg_hip metrics: singular_values takes a float64 (m, n) matrix on the GPU")
+    x = M.contiguous()
+    lib = _lib.load()
+    m, n = x.shape
+    sigma = torch.empty(max(min(m, n), 1), dtype=torch.float64, device=x.device)
+    info = torch.empty(2, dtype=torch.int32, device=x.device)
+    nbytes = lib.mstg_singular_values_workspace_bytes(m, n)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=x.device)
+    _lib.check(lib.mstg_singular_values(_p(x), m, n, _p(sigma), _p(info), _p(ws), ws.numel() * 8, _stream()), "mstg_singular_values")
+    sigma = sigma[:min(m, n)]
+    return (sigma, info) if return_info else sigma
+
+
+def calculate_fid(real_features, fake_features) -> float:
+    """``calculate_fid`` of m_test.py as the reference calls it: numpy arrays or cuda tensors in, a Python float out after ONE
+    device-to-host copy.  Raises if the Jacobi did not converge within ``MAX_SWEEPS`` sweeps."""
+    def stage(x):
+        if isinstance(x, np.ndarray):
+            if x.dtype not in (np.float32, np.float64):
+                x = x.astype(np.float64)
+            x = np.ascontiguousarray(x)
+            return torch.from_numpy(x if x.flags.writeable else x.copy()).cuda()
+        return x
+    out, info = _frechet_launch(stage(real_features), stage(fake_features))
+    host = torch.cat([out, info.to(torch.float64)]).cpu().tolist()  # the one device-to-host copy
+    if int(host[6]) != 1:
+        raise RuntimeError(f"mstg_hip metrics: the Jacobi SVD did not converge within {int(host[5])} sweeps (non-finite features?)")
+    return host[4]
