@@ -12,6 +12,22 @@
  *   - activations are fp32 NHWC ("channels last") unless a descriptor flag says NCHW (only the 3-channel
  *     image tensors at the module boundary are NCHW); weights stay in PyTorch's own layouts
  *     (Conv2d OIHW, ConvTranspose2d IOHW) so reference state_dicts are consumed as they are.
+ *
+ * Memory contract of every entry point (tests/test_gpu_memory_contract.py runs the hot path under it):
+ *
+ *   - it writes only its declared outputs, and at most workspace_bytes -- what the matching *_workspace_bytes query returned -- of
+ *     the workspace; not one byte in front of or behind either;
+ *   - it reads nothing that neither it nor the caller wrote: no element past the end of an input, nothing from an output or from
+ *     the workspace before the call itself has filled it (with workspace_packed != 0: before the earlier call has);
+ *   - it leaves every argument declared `const` unchanged;
+ *   - it needs no more than 16-byte alignment of any device pointer (less where an entry says so: a slice `x_coff` / `y_coff`
+ *     floats into a row, byte images, the scalar fall-backs of the element-wise kernels).
+ *
+ *   Written in place, by contract: the power-iteration vectors u and v of mstg_spectral_norm* (training != 0); running_mean /
+ *   running_var of the BatchNorm forwards in training mode; p, m and v of the Adam steps, and the step state of the mixed-precision
+ *   train step; the gradient buffer of the clip-by-norm entry; every gradient output of an entry called with accumulate != 0
+ *   (mstg_conv_desc.accumulate: y or dx; dw / dbias; the attention, multi-scale, spectral-norm and LayerNorm parameter gradients),
+ *   which is then read as well as written.
  */
 #ifndef MSTG_HIP_H
 #define MSTG_HIP_H
