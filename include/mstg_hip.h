@@ -582,6 +582,83 @@ int mstg_image_metrics_u8(const unsigned char* a, const unsigned char* b, int N,
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixed-size image comparison (csrc/compare.hip).  When the processed image and the original differ in shape, the reference's
+ * four folder-comparison scripts resize the processed one with cv2.resize(img, (W, H)) -- the 8-bit INTER_LINEAR -- and only then
+ * measure (compare_image_quality.py:100-106, :299-301, image_quality_comparison.py:17-18, complete_comparison.py:16-17,
+ * improved_image_compare.py:11-12).  The resize is restated from its definition below, as recalled, not compared with an OpenCV
+ * binary (tests/cv_resize_ref.py is the same restatement in numpy).
+ *
+ * cv2.resize(src, (Wd, Hd)) of an 8-bit image, INTER_LINEAR, per channel.
+ *   Per axis, source extent s >= 1, destination extent d >= 1:
+ *        scale = 1.0 / ((double)d / (double)s)   (both divisions in double: OpenCV forms inv_scale and then its reciprocal);
+ *        for i = 0 .. d-1: f = (float)((i + 0.5) * scale - 0.5) (double arithmetic, a product and a difference, ONE rounding to
+ *        float); p = floor(f); f = f - (float)p (a float subtraction);
+ *        HORIZONTAL axis only: p < 0 -> p = 0, f = 0; p >= s - 1 -> p = s - 1, f = 0;
+ *        w0 = (short)rint((1.f - f) * 2048.f), w1 = (short)rint(f * 2048.f): float operations, each rounded, ties to even,
+ *        saturated to int16.
+ *   Horizontal pass on a source row S: q = min(p + 1, s - 1); T[x] = S[p] * w0 + S[q] * w1 in int32.
+ *   Vertical pass: the rows are clamp(p, 0, s-1) and clamp(p + 1, 0, s-1); the weights b0, b1 come from the UNCLAMPED fraction and
+ *        are not reset at the borders (that asymmetry is the library's);
+ *        out = (uchar)((((b0 * (T0 >> 4)) >> 16) + ((b1 * (T1 >> 4)) >> 16) + 2) >> 2).
+ *   The result is a pure function of four source bytes and four weights: nothing separable has to be stored.  Equal extents give
+ *   the identity, an exact 2x reduction gives (a + b + c + d + 2) >> 2 (what OpenCV's switch to its area path computes at that
+ *   ratio, so there is no special case).
+ *   w0 + w1 == 2048 whenever d <= 4096: f * 2048 is exact; 1 - f is exact unless p == 0, and there the unrounded position lies
+ *   either on a point (k + 0.5) / 2048 or at least 1 / (4096 d) >= 2^-24 from it, so f (rounded by at most 2^-26) stays more than
+ *   2^-25 from it, which is the most 1 - f can lose: the two rint never disagree.  With both sums 2048 the value before the cast
+ *   lies in 0..255 and the cast changes nothing (tests/test_compare_cpu.py holds both).  For larger d a sum of 2049 is conceivable;
+ *   the cast is C's conversion of an int to unsigned char, the low 8 bits, and that is what the kernels store (the value stays
+ *   below 256 there too: 255 * (2049 / 2048)^2 < 255.3).
+ *
+ * mstg_cv_resize_coeffs: HOST only, touches no device; the table above for one axis, index[dst] and weights[dst][2] = {w0, w1}.
+ * It is the one place where the double and float steps are evaluated: the tables are built on the host and uploaded.
+ * DEVICE TABLE of an axis: int32 [2 dst] = index[dst] followed by the bytes of weights[dst][2] (one int32 per pair, w0 low).
+ * The kernels clamp every index to its source before they use it.
+ *
+ * mstg_cv_resize_linear_u8: src (N, Hs, Ws, 3) -> dst (N, Hd, Wd, 3), contiguous, one launch, 64-bit offsets; table_v / table_h =
+ * device tables of (Hs -> Hd, vertical) and (Ws -> Wd, horizontal).  H * W * 3 < 2^31 for both shapes, N <= 65535; the output
+ * must not overlap the input (BADARG).
+ *
+ * mstg_pair_metrics_u8: out[P][6] (fp64, the meaning of mstg_image_metrics_u8's rows) for P pairs (a_i, b_i) of ANY shapes, where
+ * b_i is resized to a_i's shape by the definition above while its patch is staged -- the resized image is never written to
+ * memory; a pair of equal shape is staged as mstg_image_metrics_u8 stages it.  TWO launches whatever P and however many distinct
+ * shapes: MSTG_PAIR_METRICS_LAUNCHES = tiles, finish.  One descriptor per pair; one host-built tile list, four int32 per tile
+ * {pair, ty, tx, 0}, pair after pair, each pair's tiles in the row-major order of mstg_image_metrics_u8 on a_i; the workspace holds
+ * four 8-byte words per tile; `table` = the device tables of the resized pairs packed in one int32 buffer (host copy for
+ * validation, device copy for the kernels).  The kernels check every tile against its descriptor before they touch memory.
+ * Row i is BIT FOR BIT mstg_image_metrics_u8(a_i, mstg_cv_resize_linear_u8(b_i)): the same tile decomposition of a_i, every sum
+ * in the same fixed order, no atomics; it does not depend on P or on the order of the pairs.  The same image may appear in any
+ * number of pairs.
+ * Refused, naming the pair index and the value in mstg_last_error: an extent below 1 (BADARG); a smaller than the 7x7 SSIM window
+ * (BADARG); H * W * 3 >= 2^31 for either image (UNSUPPORTED); a total tile count above 2^24 - 1, the workgroups of one launch --
+ * which covers every count that does not fit int32 (UNSUPPORTED).
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_PAIR_METRICS_LAUNCHES 2
+typedef struct mstg_pair_desc {
+    const unsigned char* a; /* device: (ha, wa, 3), contiguous */
+    const unsigned char* b; /* device: (hb, wb, 3), contiguous */
+    int32_t ha, wa, hb, wb;
+    int32_t tile0, ntiles;    /* first tile of the pair in the tile list and its tile count (mstg_pair_metrics_tiles fills them) */
+    int64_t table_v, table_h; /* int32 index of the device tables (hb -> ha, vertical) and (wb -> wa, horizontal) in the packed
+                                 table buffer; not read for a pair of equal shape */
+} mstg_pair_desc;
+int mstg_cv_resize_coeffs(int src, int dst, int horizontal, int32_t* index, int16_t* weights /* [dst][2] */);
+int mstg_cv_resize_linear_u8(const unsigned char* src, int N, int Hs, int Ws, int Hd, int Wd, const int32_t* table_v,
+                             const int32_t* table_h, unsigned char* dst, void* stream);
+/* Host only, touches no device: the refusals above, non-null image pointers, tile0 / ntiles as mstg_pair_metrics_tiles fills
+ * them, table offsets inside `table_len` words and (table != NULL) every index inside its source.  A refusal names the pair
+ * index.  mstg_pair_metrics_u8 calls it first. */
+int mstg_pair_metrics_validate(const mstg_pair_desc* descs, int P, const int32_t* table, size_t table_len);
+size_t mstg_pair_metrics_workspace_bytes(const mstg_pair_desc* descs, int P); /* from the shapes alone; 0 for a refused set */
+/* fills tile0 / ntiles of every descriptor and returns the number of tiles (negative: error); writes the tile list when
+ * tiles != NULL (cap = tiles the buffer holds) */
+int mstg_pair_metrics_tiles(mstg_pair_desc* descs, int P, int32_t* tiles, size_t cap);
+/* descs / table: host copies; descs_dev / tiles_dev / table_dev: the same bytes on the device (8 / 16 / 4-byte aligned) */
+int mstg_pair_metrics_u8(const mstg_pair_desc* descs, int P, const int32_t* table, size_t table_len, const void* descs_dev,
+                         const int32_t* tiles_dev, int ntiles, const int32_t* table_dev, double* out /* [P][6] */, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The per-pixel weight map of process_local_style(mode='enhanced') (batch_process_images.py:312-342, detect_sky :126-150; the same
  * map with coefficient 0.4 in mode 'advanced', :355-384), built on the device for N canvases (N, H, W, 3) uint8 in three launches
  * whatever N.  OpenCV's 8-bit integer algorithms are restated from their definitions (not compared with an OpenCV binary):

@@ -3,7 +3,8 @@ the metrics computed on the GPU (mstg_hip.metrics, csrc/metrics.hip).  PIL decod
 size then goes through one batched launch and the numbers come back in one copy.
 
 Differences from the reference, on purpose: images of different shapes raise ValueError instead of being resized with cv2.resize
-(resize with ``mstg_hip.image.resize_u8`` first), and no spreadsheet or chart is written (``output_excel`` / ``output_chart`` must
+(``mstg_hip.metrics.evaluate_pairs_resized`` and the drop-ins compare_image_quality.py / complete_comparison.py /
+improved_image_compare.py resize as the reference does), and no spreadsheet or chart is written (``output_excel`` / ``output_chart`` must
 stay None): ``compare_folders`` returns the per-pair list and the three averages.
 """
 from __future__ import annotations

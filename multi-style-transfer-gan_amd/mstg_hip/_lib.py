@@ -40,6 +40,15 @@ class ImgDesc(C.Structure):
 
 IMG_PASS_H, IMG_PASS_V_TENSOR, IMG_PASS_V_U8 = 0, 1, 2
 
+
+class PairDesc(C.Structure):
+    """mirror of mstg_pair_desc"""
+    _fields_ = ([("a", C.c_void_p), ("b", C.c_void_p)] + [(n, C.c_int32) for n in ("ha", "wa", "hb", "wb", "tile0", "ntiles")] +
+                [("table_v", C.c_int64), ("table_h", C.c_int64)])
+
+
+PAIR_METRICS_LAUNCHES = 2  # MSTG_PAIR_METRICS_LAUNCHES
+
 _vp, _fp, _sz, _i, _f = C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float
 _dp = C.POINTER(ConvDesc)
 _hp = C.POINTER(F16ConvDesc)
@@ -185,6 +194,12 @@ SIGNATURES = {
     "mstg_img_batch_tensor_to_u8": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "mstg_image_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_image_metrics_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mstg_cv_resize_coeffs": (_i, [_i, _i, _i, _vp, _vp]),
+    "mstg_cv_resize_linear_u8": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mstg_pair_metrics_validate": (_i, [_vp, _i, _vp, _sz]),
+    "mstg_pair_metrics_workspace_bytes": (_sz, [_vp, _i]),
+    "mstg_pair_metrics_tiles": (_i, [_vp, _i, _vp, _sz]),
+    "mstg_pair_metrics_u8": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "mstg_local_style_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_local_style_prepare": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mstg_local_style_hysteresis": (_i, [_vp, _i, _i, _i, _vp, _vp]),

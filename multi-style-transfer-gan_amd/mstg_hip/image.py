@@ -81,6 +81,37 @@ def resize_u8(img: torch.Tensor, size, filt: int = BILINEAR) -> torch.Tensor:
     return cur
 
 
+@lru_cache(maxsize=1024)
+def _cv_table_host(src: int, dst: int, horizontal: bool) -> np.ndarray:
+    """The device table of one axis of ``cv_resize_u8`` (include/mstg_hip.h): int32 [2 dst] = the index of each destination
+    position, then its int16 weight pair as one int32.  Built by the host-only ``mstg_cv_resize_coeffs``."""
+    index, weights = np.zeros(max(dst, 0), dtype=np.int32), np.zeros((max(dst, 0), 2), dtype=np.int16)
+    _lib.check(_lib.load().mstg_cv_resize_coeffs(src, dst, int(horizontal), index.ctypes.data, weights.ctypes.data), "mstg_cv_resize_coeffs")
+    return np.concatenate([index, weights.view(np.int32).reshape(-1)])
+
+
+def cv_resize_u8(img: torch.Tensor, size) -> torch.Tensor:
+    """``cv2.resize(img, (width, height))`` of 8-bit images, i.e. INTER_LINEAR, as the reference's folder comparisons call it
+    (compare_image_quality.py:102, complete_comparison.py:17): ``size`` = (new_w, new_h) as ``resize_u8`` takes it, ``img`` an
+    (H, W, 3) or (N, H, W, 3) uint8 tensor on the GPU; one launch for the whole batch.  This build's restatement of OpenCV's
+    arithmetic (include/mstg_hip.h), not compared with an OpenCV binary -- and not Pillow's resampling, which ``resize_u8`` is.
+    The coefficient tables are built on the host and cached on the device per (source extent, destination extent, axis)."""
+    if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.uint8 or img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise RuntimeError("mstg_hip image: cv_resize_u8 expects a uint8 (H, W, 3) or (N, H, W, 3) tensor on the GPU")
+    x = img.contiguous()
+    batch = x if x.dim() == 4 else x.unsqueeze(0)
+    N, H, W = batch.shape[:3]
+    new_w, new_h = int(size[0]), int(size[1])
+    if min(N, H, W, new_w, new_h) < 1:
+        raise RuntimeError(f"mstg_hip image: cv_resize_u8 of {N} image(s) {H} x {W} to {new_h} x {new_w}: every extent must be at least 1")
+    tv = _device_table(("cv_resize", H, new_h, 0), x.device, lambda: _cv_table_host(H, new_h, False))
+    th = _device_table(("cv_resize", W, new_w, 1), x.device, lambda: _cv_table_host(W, new_w, True))
+    out = torch.empty((N, new_h, new_w, 3), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.load().mstg_cv_resize_linear_u8(_p(batch), N, H, W, new_h, new_w, _p(tv), _p(th), _p(out), _stream()),
+               "mstg_cv_resize_linear_u8")
+    return out if x.dim() == 4 else out[0]
+
+
 def paste_u8(src, window, dst_hw, at, fill=255) -> torch.Tensor:
     """New (dh, dw) canvas filled with ``fill`` with ``src[window]`` pasted at ``at`` = (y, x); window = (y0, x0, h, w)."""
     src = _req_u8(src)
