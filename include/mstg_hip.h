@@ -1110,7 +1110,7 @@ int mstg_felzenszwalb_u8(const unsigned char* img, int H, int W, double scale, d
  *        number of owners <= H * W / max(min_size, 1) + 1 (integer division; every owner but that of pixel 0 has min_size pixels),
  *        a bound the host can compute, so a caller sizes its per-segment buffers without reading count back.
  *        Components above max_size are NOT split: not built.
- *   Still not built: `quickshift`; the max_size split; a comparison with a scikit-image binary.
+ *   Still not built: the max_size split; a comparison with a scikit-image binary.  (`quickshift` is the next block.)
  * ---------------------------------------------------------------------------------------------- */
 #define MSTG_SLIC_MAX_CENTRES 4096
 #define MSTG_SLIC_SUMS 6 /* per centre: n, sum y, x, L, a, b */
@@ -1130,6 +1130,59 @@ size_t mstg_connect_labels_workspace_bytes(int N, int H, int W);
 /* step 4 on any int32 labels (N, H, W), any H, W >= 1 with H * W <= MSTG_SEGMENT_MAX_PIXELS; min_size <= 1: nothing is small */
 int mstg_connect_labels(const int* labels_in, int N, int H, int W, int min_size, int* labels_out, int* count, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * QUICKSHIFT, the second DEVICE segmentation for the local style above: the `quickshift` method that the reference's
+ * get_segmentation_mask names (enhanced_local_style.py:69-70: skimage.segmentation.quickshift(img, kernel_size=3, max_dist=6,
+ * ratio=0.5)), per image for N images (N, H, W, 3) uint8 RGB, N images per launch, 64-bit offsets, no host step and no host
+ * synchronisation.  The definition is RESTATED AS RECALLED, NOT COMPARED WITH A SCIKIT-IMAGE BINARY (tests/quickshift_ref.py is the
+ * same restatement in numpy); every place where it is THIS BUILD'S OWN says so.  No floating-point atomics and no floating-point
+ * sum at all: the density is an exact integer, so it does not depend on how a window is split over lanes; everything else has a
+ * fixed order: bit-reproducible and independent of N.  A parameter outside what is built is refused with MSTG_E_UNSUPPORTED or
+ * MSTG_E_BADARG and a message naming it, on the host before any launch, never approximated.  An output or the workspace must not
+ * overlap an input.  idx = r * W + c is a pixel's raster index.
+ *
+ *   1. features.  (L, a, b) are the bytes of mstg_lab_u8 (lab_table = the entries of mstg_lab_tables on the device, as for
+ *        mstg_slic_u8).  THIS BUILD'S OWN: scikit-image converts with a float64 rgb2lab.
+ *   2. window and distance.  w = (int)ceil(3 * kernel_size); the window of pixel p is |dr| <= w, |dc| <= w, clipped to the image.
+ *        For p and a tap p': q = (100 * dL)^2 + 65025 * (da^2 + db^2), an exact integer (up to 9.1e9: above 2^32, exact in int64
+ *        and in a double); s = dr^2 + dc^2; D = (double)q * kc + (double)s, two roundings, no fused multiply-add;
+ *        kc = (ratio * ratio) / 65025.0 in double on the host.  That is ratio^2 * |dLab|^2 with L on the scale 0 .. 100 (the byte
+ *        times 100 / 255) and a, b free of their offset, plus the squared pixel distance.
+ *   3. density.  THIS BUILD'S OWN (fixed point; scikit-image sums float64):
+ *        T(p) = sum over the clipped window, p itself included, of rint_half_even(exp(D * inv) * 2^32),
+ *        inv = -0.5 / (kernel_size * kernel_size) in double on the host, exp in float64; int64 (N, H, W), at most 961 * 2^32.
+ *        Two pixels whose windows hold the same terms tie EXACTLY; a float64 sum leaves mirror-image windows 1 ulp apart, and
+ *        such near-ties decide parents.  Two float64 exp that differ by a few ulp move a term by at most one unit.
+ *   4. parent.  p' is HIGHER than p iff T(p') > T(p), or T(p') == T(p) and idx' < idx.  THE TIE RULE IS THIS BUILD'S OWN:
+ *        scikit-image adds normal(scale = 1e-5) noise from a seeded generator to the densities, which shatters every flat region
+ *        (the bars of a letterboxed image) into random specks.  The parent of p is the higher tap of the smallest D, among equal D
+ *        the lowest idx' (scikit-image's row-major scan with a strict <).  p is a root (its own parent) if no tap is higher or if
+ *        that D > max_dist * max_dist (the product a double from the host; scikit-image compares sqrt(D) > max_dist).
+ *        Since D >= s the search needs only |dr|, |dc| <= min(w, floor(max_dist)): a parent with D <= max_dist^2 lies inside that
+ *        square and so does every tap that ties with it.
+ *   5. labels.  Every pixel follows its parents to a root (no cycle: HIGHER is a strict total order).  The roots are numbered
+ *        0, 1, ... in ascending idx (np.unique(..., return_inverse=True)); labels (N, H, W) int32 in 0 .. count - 1, count (N)
+ *        int32.  Segments need not be connected, as in scikit-image.  count <= H * W is the only bound the host can know.
+ *   Refused by name: kernel_size < 1 or not finite; w above MSTG_QUICKSHIFT_MAX_RADIUS; max_dist <= 0 or not finite; ratio outside
+ *   [0, 1]; H * W above MSTG_SEGMENT_MAX_PIXELS; H or W < 1; a workspace that is too small; an output or workspace that overlaps
+ *   an input.  Not built: sigma != 0, convert2lab=False, return_tree, scikit-image's noise.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_QUICKSHIFT_MAX_RADIUS 15
+/* bytes mstg_quickshift_u8 needs; 0 for a refused shape or kernel_size (mstg_last_error says which) */
+size_t mstg_quickshift_workspace_bytes(int N, int H, int W, double kernel_size);
+/* steps 1 to 3: density (N, H, W) int64 on the device, 8-byte aligned; one launch */
+int mstg_quickshift_density_u8(const unsigned char* img, int N, int H, int W, double ratio, double kernel_size,
+                               const unsigned short* lab_table, long long* density_i64, void* stream);
+/* step 4 on a GIVEN density (an input: any int64 (N, H, W)): parent (N, H, W) int32, raster indices inside the pixel's image, a
+ * root its own parent; one launch */
+int mstg_quickshift_parents_u8(const unsigned char* img, const long long* density_i64, int N, int H, int W, double ratio, double kernel_size,
+                               double max_dist, const unsigned short* lab_table, int* parent_i32, void* stream);
+/* steps 1 to 5: labels (N, H, W) int32 in 0 .. count - 1, count (N) int32, both on the device; workspace 16-byte aligned.
+ * 6 + max(ceil(log16(H * W)), 1) launches (10 at 256 x 256), whatever N and the image: density, parents, the rounds of pointer
+ * jumping and the four launches of the numbering that mstg_connect_labels uses too */
+int mstg_quickshift_u8(const unsigned char* img, int N, int H, int W, double ratio, double kernel_size, double max_dist,
+                       const unsigned short* lab_table, int* labels, int* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The FIVE SETTINGS of the reference's advanced_transform.py (:129-311: standard, contrast, multi-scale fusion, detail, K-means

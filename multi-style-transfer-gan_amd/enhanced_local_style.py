@@ -10,7 +10,12 @@ value means of ``avg_color_hsv`` as NaN (the device record holds the saturation 
 comparison chart is written (the reference's ``create_comparison`` needs matplotlib); ``enhanced_local_style_transfer`` and the
 command line take ``segmentation`` / ``--segmentation``: 'felzenszwalb' (the reference's choice, the default) or 'slic', the
 device segmentation ``mstg_hip.image.slic_labels`` (8-bit Lab features and a connectivity step of this build's own), with which the
-whole call stays on the GPU.  The OpenCV and scikit-image steps are
+whole call stays on the GPU.  ``--device-segmentation {slic,quickshift}`` (``segments=`` of
+``enhanced_local_style_transfer``: a callable such as ``mstg_hip.image.quickshift_segmenter()``), when given, takes the place of
+``--segmentation``: that is how quickshift (``mstg_hip.image.quickshift_labels`` with the reference's kernel_size 3, max_dist 6,
+ratio 0.5; a fixed-point density and a tie rule by raster index of this build's own) is reached.  It is not a value of
+``--segmentation`` because that option, ``segmentation=`` and ``get_segmentation_mask`` keep refusing 'quickshift' by name, as
+they did before it was built, and callers may rely on that.  The OpenCV and scikit-image steps are
 restated from their definitions (include/mstg_hip.h) and have not been compared with an OpenCV or scikit-image binary.
 """
 from __future__ import annotations
@@ -114,17 +119,21 @@ def determine_blend_ratios(segment_stats, segments, img_shape):
     return dimg.gaussian_reflect_f32(torch.from_numpy(blend_map).to("cuda")).cpu().numpy()
 
 
-def enhanced_local_style_transfer(model, img_path, output_path, device, segmentation="felzenszwalb"):
+def enhanced_local_style_transfer(model, img_path, output_path, device, segmentation="felzenszwalb", segments=None):
     """:178-292 without the comparison chart: decode, ``mstg_hip.image.process_enhanced_local_style``, encode -> PIL image.
-    ``segmentation``: 'felzenszwalb' (on the host) or 'slic' (on the device)."""
+    ``segmentation``: 'felzenszwalb' (on the host) or 'slic' (on the device); ``segments``: passed through (labels, or a callable
+    such as ``mstg_hip.image.quickshift_segmenter()``), wins when given."""
     original = Image.open(img_path).convert("RGB")
-    out = dimg.process_enhanced_local_style(model, _u8(original, device), segmentation=segmentation)
+    out = dimg.process_enhanced_local_style(model, _u8(original, device), segments=segments, segmentation=segmentation)
     final_img = Image.fromarray(out.cpu().numpy())
     if os.path.dirname(output_path):
         os.makedirs(os.path.dirname(output_path), exist_ok=True)
     final_img.save(output_path)
     print(f"saved the enhanced image to {output_path}")
     return final_img
+
+
+DEVICE_SEGMENTERS = {"slic": dimg.slic_segmenter, "quickshift": dimg.quickshift_segmenter}
 
 
 def build_parser():
@@ -136,6 +145,8 @@ def build_parser():
     parser.add_argument("--blocks", type=int, default=1, help="transformer blocks")
     parser.add_argument("--segmentation", choices=dimg.SEGMENTATIONS, default="felzenszwalb",
                         help="felzenszwalb: the reference's, on the host; slic: on the device")
+    parser.add_argument("--device-segmentation", choices=tuple(DEVICE_SEGMENTERS), default=None,
+                        help="a segmentation that stays on the device; when given it takes the place of --segmentation")
     return parser
 
 
@@ -146,7 +157,8 @@ def main(argv=None):
     device = torch.device("cuda")
     print(f"device: {device}")
     model, _ = load_model(args.model, device, args.channels, args.blocks)
-    enhanced_local_style_transfer(model, args.image, args.output, device, args.segmentation)
+    segments = DEVICE_SEGMENTERS[args.device_segmentation]() if args.device_segmentation else None
+    enhanced_local_style_transfer(model, args.image, args.output, device, args.segmentation, segments)
 
 
 if __name__ == "__main__":

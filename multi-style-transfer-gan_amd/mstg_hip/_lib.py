@@ -249,6 +249,10 @@ SIGNATURES = {
     "mstg_slic_assign_u8": (_i, [_vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mstg_connect_labels_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_connect_labels": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_quickshift_workspace_bytes": (_sz, [_i, _i, _i, C.c_double]),
+    "mstg_quickshift_density_u8": (_i, [_vp, _i, _i, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "mstg_quickshift_parents_u8": (_i, [_vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "mstg_quickshift_u8": (_i, [_vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mstg_lab_inverse_tables": (_i, [_vp]),
     "mstg_gaussian_sigma_taps": (_i, [C.c_double, _vp, _vp]),
     "mstg_lab_u8": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -282,6 +286,7 @@ BILATERAL_WIDE_TABLE_FLOATS = 768 + 90 * 90 + 1  # MSTG_BILATERAL_WIDE_TABLE_FLO
 SEGMENT_SUMS, SEGMENT_MAX_PIXELS, SEGMENT_TILE_SLOTS = 11, 1 << 20, 128  # MSTG_SEGMENT_SUMS, _MAX_PIXELS, _TILE_SLOTS
 CLAHE_TILES = 8  # MSTG_CLAHE_TILES
 SLIC_MAX_CENTRES, SLIC_SUMS = 4096, 6  # MSTG_SLIC_MAX_CENTRES, MSTG_SLIC_SUMS
+QUICKSHIFT_MAX_RADIUS = 15  # MSTG_QUICKSHIFT_MAX_RADIUS
 LAB_INV_TABLE_U16, GAUSSIAN_SIGMA_MAX_KSIZE = 15696, 31  # MSTG_LAB_INV_TABLE_U16, MSTG_GAUSSIAN_SIGMA_MAX_KSIZE
 KMEANS_MAX_K, KMEANS_MAX_ATTEMPTS, KMEANS_MAX_ITERS, FUSE_MAX_SCALES = 16, 16, 100, 8  # MSTG_KMEANS_MAX_*, MSTG_FUSE_MAX_SCALES
 STANDARD_MODEL_TYPES = {"photo_to_monet": 0, "monet_to_photo": 1}  # MSTG_STANDARD_PHOTO_TO_MONET, MSTG_STANDARD_MONET_TO_PHOTO

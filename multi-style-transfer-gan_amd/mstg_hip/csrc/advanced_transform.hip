@@ -33,7 +33,6 @@
 namespace mstg {
 
 constexpr int AT_THREADS = 256;
-constexpr int LT_GAMMA = 256, LT_CBRT = 3072, LT_COEF = LT_GAMMA + LT_CBRT;  // the forward table (mstg_lab_tables)
 constexpr int LI_FY = 0, LI_A = 256, LI_B = 512, LI_CUBE = 768, LI_CUBE_N = MSTG_LAB_INV_CUBE, LI_COEF = LI_CUBE + LI_CUBE_N;
 constexpr int LI_GAMMA = LI_COEF + 9, LI_GAMMA_N = 8193;  // the inverse table (mstg_lab_inverse_tables)
 static_assert(LI_GAMMA + LI_GAMMA_N <= MSTG_LAB_INV_TABLE_U16, "the inverse table holds fy, a, b, cube, the coefficients and the gamma");
@@ -56,20 +55,7 @@ struct FuseWeights {
 };
 
 // ---- Lab ------------------------------------------------------------------------------------------------------------------------
-// RGB (packed) -> L, a, b (packed): the integer path of mstg_color_block_mask completed with L
-__device__ __forceinline__ unsigned lab_px(unsigned q, const unsigned short* __restrict__ t) {
-    const int R = t[q & 0xffu], G = t[(q >> 8) & 0xffu], B = t[q >> 16];
-    const unsigned short* cbr = t + LT_GAMMA;
-    const unsigned short* c = t + LT_COEF;
-    const int fx = cbr[(R * c[0] + G * c[1] + B * c[2] + 2048) >> 12];
-    const int fy = cbr[(R * c[3] + G * c[4] + B * c[5] + 2048) >> 12];
-    const int fz = cbr[(R * c[6] + G * c[7] + B * c[8] + 2048) >> 12];
-    const int L = (296 * fy - 1336934 + 16384) >> 15;  // arithmetic shifts of the signed sums
-    const int a = (500 * (fx - fy) + 128 * 32768 + 16384) >> 15;
-    const int b = (200 * (fy - fz) + 128 * 32768 + 16384) >> 15;
-    return (unsigned)min(max(L, 0), 255) | (unsigned)min(max(a, 0), 255) << 8 | (unsigned)min(max(b, 0), 255) << 16;
-}
-
+// (lab_px, RGB -> Lab, is in u8_image.h: quickshift.hip uses it too)
 // f (scale 32768) -> the linear value (scale 8192): two neighbouring entries of the table, interpolated linearly
 __device__ __forceinline__ int lab_cube(int f, const unsigned short* __restrict__ cube) {
     f = min(max(f, 0), 8 * (LI_CUBE_N - 1) - 1);

@@ -29,6 +29,8 @@
 //    so reading a neighbour's newer value only shortens the work), then the numbering: cc_count_kernel (owners per block of 1024 pixels), cc_scan_kernel (one
 //    workgroup per image: the blocks' offsets and the count), cc_number_kernel (the owners' numbers), cc_gather_kernel.
 //    Every loop of the union-find is capped by H * W (a parent is always a smaller index, so no path is longer).
+//    The pointer jumping and the numbering are cc_resolve_number (declared in u8_image.h): quickshift.hip ends with the same tail,
+//    its roots numbered from 0.
 //
 // No floating-point atomics; all sums are integers, so the result does not depend on the order: bit-reproducible, independent of N.
 #include <cmath>
@@ -44,7 +46,6 @@ constexpr int SL_SLOTS = 64;                      // label slots of a workgroup 
 constexpr int SL_F = MSTG_SLIC_SUMS;              // n, y, x, L, a, b
 constexpr int SL_C = 5;                           // floats of a centre: y, x, L, a, b
 constexpr int SL_ROUNDS = 10;
-constexpr int CC_BLOCK = 1024;                    // pixels per workgroup of the numbering: four per thread
 constexpr int CC_HOPS = 16;                       // pointers a thread follows per launch of the pointer jumping
 static_assert(SL_TH * SL_TW == SL_THREADS * SL_PX && SL_TW / SL_PX == 16, "four pixels per thread, sixteen threads per row");
 static_assert((SL_SLOTS & (SL_SLOTS - 1)) == 0 && SL_F == 6, "the hash takes the top bits");
@@ -435,9 +436,9 @@ __global__ __launch_bounds__(SL_THREADS) void cc_scan_kernel(int blocks, int* __
     if (tid == 0) count[blockIdx.x] = carry;
 }
 
-// num[p] = the number (from 1, ascending p) of owner p
+// num[p] = the number (from `first`, ascending p) of owner p
 __global__ __launch_bounds__(SL_THREADS) void cc_number_kernel(size_t hw, int blocks, const int* __restrict__ jump, const int* __restrict__ bsum,
-                                                               int* __restrict__ num) {
+                                                               int first, int* __restrict__ num) {
     __shared__ int tmp[SL_THREADS / WAVE];
     const int tid = threadIdx.x;
     const size_t n = blockIdx.x / blocks;
@@ -452,11 +453,11 @@ __global__ __launch_bounds__(SL_THREADS) void cc_number_kernel(size_t hw, int bl
         c += own[j];
     }
     int all;
-    int at = bsum[blockIdx.x] + cc_scan256(c, tid, tmp, &all);
+    int at = first + bsum[blockIdx.x] + cc_scan256(c, tid, tmp, &all);
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         const size_t p = (size_t)b * CC_BLOCK + (size_t)tid * PER + j;
-        if (own[j]) num[n * hw + p] = ++at;
+        if (own[j]) num[n * hw + p] = at++;
     }
 }
 
@@ -537,7 +538,7 @@ struct CcWorkspace {
 static CcWorkspace cc_workspace(int N, int H, int W) {
     const size_t plane = align16((size_t)N * H * W * sizeof(int));
     CcWorkspace w;
-    w.blocks = (int)cdivz((size_t)H * W, (size_t)CC_BLOCK);
+    w.blocks = cc_blocks((size_t)H * W);
     w.par = 0;
     w.size = plane;
     w.jump = 2 * plane;
@@ -548,10 +549,30 @@ static CcWorkspace cc_workspace(int N, int H, int W) {
 
 // launches of cc_jump_kernel: a path (a pixel, its root, the chain of small components) has fewer than H * W links, and the
 // shortest pointer grows CC_HOPS-fold per launch: the smallest r with CC_HOPS^r >= H * W, at least 1
-static int cc_rounds(size_t hw) {
+int cc_rounds(size_t hw) {
     int r = 1;
     for (size_t reach = CC_HOPS; reach < hw; reach *= CC_HOPS) ++r;
     return r;
+}
+
+int cc_resolve_number(int* jump, int N, int H, int W, int first, int* num, int* bsum, int* out, int* count, hipStream_t st) {
+    const size_t hw = (size_t)H * W, px = (size_t)N * hw;
+    const int blocks = cc_blocks(hw);
+    const int rounds = cc_rounds(hw);
+    for (int r = 0; r < rounds; ++r) {
+        MSTG_LAUNCH(cc_jump_kernel, sl_grid(px), dim3(SL_THREADS), 0, st, hw, px, jump);
+        MSTG_CHECK_LAUNCH("cc_jump_kernel");
+    }
+    const dim3 per_block((unsigned)((size_t)N * blocks));
+    MSTG_LAUNCH(cc_count_kernel, per_block, dim3(SL_THREADS), 0, st, hw, blocks, (const int*)jump, bsum);
+    MSTG_CHECK_LAUNCH("cc_count_kernel");
+    MSTG_LAUNCH(cc_scan_kernel, dim3((unsigned)N), dim3(SL_THREADS), 0, st, blocks, bsum, count);
+    MSTG_CHECK_LAUNCH("cc_scan_kernel");
+    MSTG_LAUNCH(cc_number_kernel, per_block, dim3(SL_THREADS), 0, st, hw, blocks, (const int*)jump, (const int*)bsum, first, num);
+    MSTG_CHECK_LAUNCH("cc_number_kernel");
+    MSTG_LAUNCH(cc_gather_kernel, sl_grid(px), dim3(SL_THREADS), 0, st, hw, px, (const int*)jump, (const int*)num, out);
+    MSTG_CHECK_LAUNCH("cc_gather_kernel");
+    return MSTG_OK;
 }
 
 static int cc_run(const int* labels, int N, int H, int W, int min_size, int* out, int* count, unsigned char* base, hipStream_t st) {
@@ -571,21 +592,7 @@ static int cc_run(const int* labels, int N, int H, int W, int min_size, int* out
     MSTG_CHECK_LAUNCH("cc_size_kernel");
     MSTG_LAUNCH(cc_link_kernel, sl_grid(px), dim3(SL_THREADS), 0, st, W, hw, px, min_size, (const int*)par, (const int*)size, jump);
     MSTG_CHECK_LAUNCH("cc_link_kernel");
-    const int rounds = cc_rounds(hw);
-    for (int r = 0; r < rounds; ++r) {
-        MSTG_LAUNCH(cc_jump_kernel, sl_grid(px), dim3(SL_THREADS), 0, st, hw, px, jump);
-        MSTG_CHECK_LAUNCH("cc_jump_kernel");
-    }
-    const dim3 per_block((unsigned)((size_t)N * ws.blocks));
-    MSTG_LAUNCH(cc_count_kernel, per_block, dim3(SL_THREADS), 0, st, hw, ws.blocks, (const int*)jump, bsum);
-    MSTG_CHECK_LAUNCH("cc_count_kernel");
-    MSTG_LAUNCH(cc_scan_kernel, dim3((unsigned)N), dim3(SL_THREADS), 0, st, ws.blocks, bsum, count);
-    MSTG_CHECK_LAUNCH("cc_scan_kernel");
-    MSTG_LAUNCH(cc_number_kernel, per_block, dim3(SL_THREADS), 0, st, hw, ws.blocks, (const int*)jump, (const int*)bsum, size);
-    MSTG_CHECK_LAUNCH("cc_number_kernel");
-    MSTG_LAUNCH(cc_gather_kernel, sl_grid(px), dim3(SL_THREADS), 0, st, hw, px, (const int*)jump, (const int*)size, out);
-    MSTG_CHECK_LAUNCH("cc_gather_kernel");
-    return MSTG_OK;
+    return cc_resolve_number(jump, N, H, W, 1, size, bsum, out, count, st);  // scikit-image's start_label = 1
 }
 
 // the workspace of the assignment: the Lab bytes, two centre buffers, the sums; for mstg_slic_u8 also the raw labels and the

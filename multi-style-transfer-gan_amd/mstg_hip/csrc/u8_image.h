@@ -1,5 +1,5 @@
 // Device and host helpers shared by the 8-bit image filters (local_style.hip, standard_mode.hip, app_local_style.hip,
-// color_blocks.hip, segment_style.hip, advanced_transform.hip, slic.hip).  Every device helper is a bit-exact restatement of an OpenCV / numpy
+// color_blocks.hip, segment_style.hip, advanced_transform.hip, slic.hip, quickshift.hip).  Every device helper is a bit-exact restatement of an OpenCV / numpy
 // definition; a primitive that more than one of those files uses is defined HERE, once, so that a fix reaches every user (DESIGN.md,
 // "Shared 8-bit image helpers").  All __forceinline__: a kernel compiles to the code it had with the body written out in place.
 #pragma once
@@ -239,6 +239,28 @@ __device__ __forceinline__ int gain_u8(int v, float gain) {
     return (int)fminf(fmaxf(__builtin_rintf((float)v * gain), 0.f), 255.f);
 }
 
+// ---- shared by advanced_transform.hip and quickshift.hip: the 8-bit COLOR_RGB2LAB ------------------------------------------------
+constexpr int LT_GAMMA = 256, LT_CBRT = 3072, LT_COEF = LT_GAMMA + LT_CBRT;  // the forward table (mstg_lab_tables)
+// RGB (packed) -> L, a, b (packed): the integer path of mstg_color_block_mask completed with L
+__device__ __forceinline__ unsigned lab_px(unsigned q, const unsigned short* __restrict__ t) {
+    const int R = t[q & 0xffu], G = t[(q >> 8) & 0xffu], B = t[q >> 16];
+    const unsigned short* cbr = t + LT_GAMMA;
+    const unsigned short* c = t + LT_COEF;
+    const int fx = cbr[(R * c[0] + G * c[1] + B * c[2] + 2048) >> 12];
+    const int fy = cbr[(R * c[3] + G * c[4] + B * c[5] + 2048) >> 12];
+    const int fz = cbr[(R * c[6] + G * c[7] + B * c[8] + 2048) >> 12];
+    const int L = (296 * fy - 1336934 + 16384) >> 15;  // arithmetic shifts of the signed sums
+    const int a = (500 * (fx - fy) + 128 * 32768 + 16384) >> 15;
+    const int b = (200 * (fy - fz) + 128 * 32768 + 16384) >> 15;
+    // The compiler packs the two saturated shifts of L and a with v_ashr_pk_u8_i32, which writes 16 bits and LEAVES the upper half
+    // of its destination as it was, and then ors b in as if that half were zero: in quickshift.hip's staging the destination was the
+    // register of the unshifted L, whose upper half ended up in b (measured on an MI355X: densities equal to a restatement with
+    // exactly that word).  The empty asm hides the value from the compiler, so the mask that follows is really executed.
+    unsigned la = (unsigned)min(max(L, 0), 255) | (unsigned)min(max(a, 0), 255) << 8;
+    asm("" : "+v"(la));
+    return (la & 0xffffu) | (unsigned)min(max(b, 0), 255) << 16;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 inline bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
@@ -275,6 +297,16 @@ inline int check_shape_16x64(const char* who, int N, int H, int W) {
     const long long blocks = (long long)N * cdiv(H, 16) * cdiv(W, 64);
     return check_grid(who, blocks, 24, "N * tiles", blocks);
 }
+
+// ---- shared by slic.hip and quickshift.hip (defined in slic.hip): the tail of a segmentation whose pixels point at an owner ------------
+// jump (N, H, W): per pixel an index inside its image; an owner points at itself, and following the pointers from any pixel ends
+// at an owner after fewer than H * W links.  cc_resolve_number launches cc_rounds(H * W) rounds of pointer jumping in place, then
+// numbers the owners first, first + 1, ... in ascending index: out (N, H, W) = the number of each pixel's owner, count (N) = the
+// owners.  num: N * H * W ints, bsum: N * cc_blocks(H * W) ints of workspace.  cc_rounds(H * W) + 4 launches whatever N.
+constexpr int CC_BLOCK = 1024;  // pixels per workgroup of the numbering: four per thread
+inline int cc_blocks(size_t hw) { return (int)((hw + CC_BLOCK - 1) / CC_BLOCK); }
+int cc_rounds(size_t hw);
+int cc_resolve_number(int* jump, int N, int H, int W, int first, int* num, int* bsum, int* out, int* count, hipStream_t st);
 
 // cv2.Canny's hysteresis (local_style_hysteresis_kernel) keeps one byte per pixel of an image in LDS; extra = words for the
 // message between "pixels; " and "the hysteresis" (with their trailing blank), or "".

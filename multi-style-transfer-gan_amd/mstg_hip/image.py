@@ -1326,6 +1326,80 @@ def connect_labels(labels, min_size, return_count=False):
     return (out, count) if return_count else out
 
 
+def _quickshift_args(ratio, kernel_size, max_dist=None):
+    return (float(ratio), float(kernel_size)) + (() if max_dist is None else (float(max_dist),))
+
+
+def quickshift_density(img_u8, ratio=1.0, kernel_size=5):
+    """The density of ``skimage.segmentation.quickshift(img, ratio, kernel_size)`` (steps 1 to 3 of the header's definition) of an
+    (H, W, 3) or (N, H, W, 3) uint8 image on the GPU -> int64 (H, W) / (N, H, W) on the device: per pixel the sum over its window
+    of ``rint(exp(-D / (2 kernel_size^2)) * 2^32)``, an exact integer (this build's own form: bit-reproducible however the window
+    is split).  One launch.  A parameter that is not built raises, naming the value.  Not compared with scikit-image."""
+    single, x = _stage_u8(img_u8, "image")
+    N, H, W = x.shape[:3]
+    dens = torch.empty((N, H, W), dtype=torch.int64, device=x.device)
+    _lib.check(_lib.load().mstg_quickshift_density_u8(_p(x), N, H, W, *_quickshift_args(ratio, kernel_size), _p(_lab_table(x.device)), _p(dens),
+                                                      _stream()), "mstg_quickshift_density_u8")
+    return dens[0] if single else dens
+
+
+def quickshift_parents(img_u8, density, ratio=1.0, kernel_size=5, max_dist=10):
+    """Step 4 of the header's definition on a GIVEN int64 density (H, W) / (N, H, W) (numpy or tensor) -> int32 of the same shape on
+    the device: every pixel's parent as a raster index inside its image, a root its own parent.  Among equal densities the lower
+    raster index is the higher pixel (this build's tie rule).  One launch."""
+    single, x = _stage_u8(img_u8, "image")
+    N, H, W = x.shape[:3]
+    d = torch.from_numpy(np.ascontiguousarray(density)) if isinstance(density, np.ndarray) else density
+    d = d.to(device=x.device, dtype=torch.int64).contiguous()
+    if d.dim() == 2:
+        d = d.unsqueeze(0)
+    if tuple(d.shape) != (N, H, W):
+        raise RuntimeError(f"mstg_hip segmentation: expected a density of shape {(N, H, W)}, got {tuple(d.shape)}")
+    parent = torch.empty((N, H, W), dtype=torch.int32, device=x.device)
+    _lib.check(_lib.load().mstg_quickshift_parents_u8(_p(x), _p(d), N, H, W, *_quickshift_args(ratio, kernel_size, max_dist),
+                                                      _p(_lab_table(x.device)), _p(parent), _stream()), "mstg_quickshift_parents_u8")
+    return parent[0] if single else parent
+
+
+def quickshift_labels(img_u8, ratio=1.0, kernel_size=5, max_dist=10, return_count=False):
+    """``skimage.segmentation.quickshift(img, ratio, kernel_size, max_dist)`` of an (H, W, 3) or (N, H, W, 3) uint8 image on the GPU
+    as include/mstg_hip.h defines it -> int32 (H, W) / (N, H, W) on the device, labels 0 .. count - 1 numbered by ascending root;
+    with ``return_count`` also the count, an int32 tensor () / (N,) on the device.  The 8-bit Lab features, the fixed-point density
+    and the tie rule by raster index are this build's own (see the header); no host step and no host synchronisation;
+    bit-reproducible.  The defaults are scikit-image's; the reference calls it with (0.5, 3, 6): ``quickshift_segmenter``.  A
+    parameter that is not built raises, naming the value.  Not compared with scikit-image."""
+    single, x = _stage_u8(img_u8, "image")
+    N, H, W = x.shape[:3]
+    lib = _lib.load()
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=x.device)
+    count = torch.empty((N,), dtype=torch.int32, device=x.device)
+    need = lib.mstg_quickshift_workspace_bytes(N, H, W, float(kernel_size))  # 0: the call below names what is wrong
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.mstg_quickshift_u8(_p(x), N, H, W, *_quickshift_args(ratio, kernel_size, max_dist), _p(_lab_table(x.device)), _p(labels),
+                                      _p(count), _p(ws), need, _stream()), "mstg_quickshift_u8")
+    if single:
+        labels, count = labels[0], count[0]
+    return (labels, count) if return_count else labels
+
+
+def quickshift_segmenter(ratio=0.5, kernel_size=3, max_dist=6):
+    """A callable for ``process_enhanced_local_style(segments=...)``: canvas -> (``quickshift_labels(canvas, ...)``, H * W).  The
+    defaults are the reference's call (enhanced_local_style.py:70).  H * W is the only bound on the count the host can know, so
+    the map is sized by it and nothing synchronises."""
+    def segment(canvas):
+        return quickshift_labels(canvas, ratio, kernel_size, max_dist), int(canvas.shape[-3]) * int(canvas.shape[-2])
+    return segment
+
+
+def slic_segmenter(n_segments=100, compactness=10.0):
+    """A callable for ``process_enhanced_local_style(segments=...)``: canvas -> (``slic_labels(canvas, ...)``, bound + 1); with the
+    defaults what ``segmentation="slic"`` does."""
+    def segment(canvas):
+        H, W = int(canvas.shape[-3]), int(canvas.shape[-2])
+        return slic_labels(canvas, n_segments, compactness), slic_segment_bound(H, W, n_segments) + 1  # labels 1 .. count <= bound
+    return segment
+
+
 def _req_labels(labels, shape, device):
     lab = torch.from_numpy(np.ascontiguousarray(labels)) if isinstance(labels, np.ndarray) else labels
     lab = lab.to(device=device, dtype=torch.int32).contiguous()
@@ -1483,7 +1557,10 @@ def process_enhanced_local_style(model, img_u8: torch.Tensor, segments=None, tar
     the crop of :270-277 exactly as written (its ``min(target, int(...))`` sizes leave an image larger than the canvas in both
     directions uncropped) and the LANCZOS resize back under the condition of :280.  ``segmentation="slic"``: ``slic_labels(canvas)``
     in the place of the host step; the labels stay on the device and the map gets ``slic_segment_bound`` for its size, so nothing
-    leaves the device and nothing synchronises.  ``segments``, when given, wins."""
+    leaves the device and nothing synchronises.  ``segments``, when given, wins; it may also be a CALLABLE that takes the device
+    canvas and returns labels or ``(labels, num_segments)`` (``quickshift_segmenter()``, ``slic_segmenter()``): the labels then never
+    leave the device, and with a ``num_segments`` nothing synchronises.  Quickshift is reached this way and not through
+    ``segmentation``, whose values stay ``SEGMENTATIONS``."""
     if segmentation not in SEGMENTATIONS:
         raise ValueError(f"mstg_hip image: segmentation {segmentation!r} is none of {SEGMENTATIONS}")
     canvas, (width, height) = letterbox_black(img_u8, target)
@@ -1492,8 +1569,12 @@ def process_enhanced_local_style(model, img_u8: torch.Tensor, segments=None, tar
         y = model(x)
     styled = to_u8(y[0])
     num_segments = None
-    if segments is None and segmentation == "slic":
-        segments, num_segments = slic_labels(canvas), slic_segment_bound(target, target) + 1  # labels 1 .. count <= bound
+    if callable(segments):
+        segments = segments(canvas)
+        if isinstance(segments, tuple):
+            segments, num_segments = segments
+    elif segments is None and segmentation == "slic":
+        segments, num_segments = slic_segmenter()(canvas)
     elif segments is None:
         segments = felzenszwalb_labels(canvas)
     blend_map = segment_blend_map(canvas, segments, num_segments)
