@@ -18,8 +18,9 @@ namespace mstg {
 
 constexpr int MS_TH = 8, MS_PH = MS_TH + 8, MS_PW = 16 + 8, MS_CKP = 20;
 
+// (The synchronous form: every tile waits out its own staging.  MSTG_MS_WGRAD_PF=0 selects it; wgrad_ms_kernel below is the default.)
 template <int CH>
-__global__ __launch_bounds__(256) void wgrad_ms_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+__global__ __launch_bounds__(256) void wgrad_ms_sync_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                        float* __restrict__ partial, int N, int H, int W, int tiles_x, int tiles_y,
                                                        int ntiles) {
     constexpr int NFH = CH / 16, C4 = CH / 4, U = NFH + 24, UW = (U + 3) / 4, BNP = CH + 4, NG = CH / 16;
@@ -367,7 +368,7 @@ struct MsPk {
 };
 
 template <int CH>
-__global__ __launch_bounds__(256) void wgrad_msp_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+__global__ __launch_bounds__(256) void wgrad_msp_sync_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                         float* __restrict__ partial, int N, int H, int W, int tiles_x, int tiles_y,
                                                         int ntiles) {
     typedef MsPk<CH> G;
@@ -444,6 +445,303 @@ __global__ __launch_bounds__(256) void wgrad_msp_kernel(const float* __restrict_
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[(4 * g + e) * 16 + i] = acc[k][mf][e];
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The default weight-gradient kernels: the two above with the recipe of ms_fwd4b_kernel.  Tile to workgroup mapping, grid, the
+// order in which every accumulator receives its pixels and the order of the bias sums are those of the synchronous kernels,
+// so the partial slabs are the same bit for bit.
+//  * The NEXT tile's windows are in flight in registers while this tile is multiplied (loads issued right after the barrier
+//    that publishes a tile, committed to LDS after the barrier that retires it).
+//  * A wave's units are role, role + 4, ... with role = (wave + a per-workgroup rotation) & 3 instead of wave: the waves with one
+//    unit fewer (U is no multiple of 4) and the bias sums then do not all sit on the same SIMD of a CU, and a short wave really
+//    skips the unit it does not own (the synchronous kernels multiply the last unit twice there).
+//  * The bias column sums belong to the short waves (the last CH / 16 roles, 16 channels each, every 16-lane group of the wave
+//    computing the same sum): 16 LDS reads per tile row are issued in front of the row's products and added behind them.
+//  * The four pixel groups of a tile row are unrolled: one lane-constant LDS address per operand stream and row, the rest immediates
+//    (0.4 - 0.8 vector instructions per MFMA instead of 2.6 - 7.4).  The x tile and, in wgrad_ms_kernel, both operands lie in LDS at
+//    a conflict-free pitch (ms_op_pitch).
+// ---------------------------------------------------------------------------------------------------------------------
+
+// One thread's share of a ROWS x COLS pixel window of an NHWC image (NQ channel quads per pixel): fetch() issues the loads of one
+// tile's window, commit() writes them to the LDS image (LD floats per pixel), zero where the window leaves the image.
+template <int ROWS, int COLS, int NQ, int LD>
+struct MsTileWindow {
+    static constexpr int NV = ROWS * COLS * NQ / 256;
+    static_assert(ROWS * COLS * NQ == NV * 256 && NV <= 32, "the window's quads divide evenly over the workgroup");
+    f32x4 v[NV];
+    unsigned rel[NV];  // byte offset ((r * W + c) * ctot + 4 * q) * 4 of this thread's quads from the window's first pixel
+    unsigned ok;       // bit k: v[k] lies inside the image
+    bool full;         // (uniform) the whole window does
+    __device__ __forceinline__ void init(int W, int ctot, int tid) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const unsigned e = 256u * k + tid, p = e / NQ, q = e % NQ, r = p / COLS, c = p % COLS;
+            rel[k] = ((r * W + c) * ctot + 4 * q) * 4u;
+        }
+        ok = 0;
+        full = false;
+    }
+    // img: first channel (of this window's channel range) of pixel (0, 0) of the image
+    __device__ __forceinline__ void fetch(const float* __restrict__ img, int y0, int x0, int H, int W, int ctot, int tid) {
+        const int base = (y0 * W + x0) * ctot;
+        full = y0 >= 0 && x0 >= 0 && y0 + ROWS <= H && x0 + COLS <= W;
+        if (full) {  // interior tile: one scalar base and the 32-bit offsets, no bounds
+            const char* t = reinterpret_cast<const char*>(img + base);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) v[k] = *reinterpret_cast<const f32x4*>(t + rel[k]);
+        } else {
+            ok = 0;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                const unsigned e = 256u * k + tid, p = e / NQ, r = p / COLS, c = p % COLS;
+                const int iy = y0 + (int)r, ix = x0 + (int)c;
+                const bool in = (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+                const unsigned off = in ? (unsigned)(4 * base) + rel[k] : 0u;  // outside: any valid address
+                v[k] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(img) + off);
+                ok |= (in ? 1u : 0u) << k;
+            }
+        }
+    }
+    __device__ __forceinline__ void commit(float* __restrict__ lds, int tid) const {
+        if (full) {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                const unsigned e = 256u * k + tid, p = e / NQ, q = e % NQ;
+                *reinterpret_cast<f32x4*>(&lds[p * LD + 4 * q]) = v[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+                const unsigned e = 256u * k + tid, p = e / NQ, q = e % NQ;
+                *reinterpret_cast<f32x4*>(&lds[p * LD + 4 * q]) = ((ok >> k) & 1) ? v[k] : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+    }
+};
+
+// Workgroups 8 apart share an XCD, and an XCD deals its workgroups to its 32 CUs in turn: the rotation differs between the
+// workgroups that share a CU whichever of the two strides the dispatcher walks first.
+__device__ __forceinline__ int ms_wave_role(int wave) {
+    const int j = blockIdx.x >> 3;
+    return __builtin_amdgcn_readfirstlane((wave + j + (j >> 5)) & 3);
+}
+
+// LDS pitch of a pixel whose channels are read as an MFMA operand by lanes (column c0 + (lane >> 4), channel f + (lane & 15)): a
+// pitch of 16 mod 64 floats puts the four 16-lane groups on four different quarters of the 64 banks (CH + 4 is a two-way conflict)
+__host__ __device__ constexpr int ms_op_pitch(int ch) { return ch == 16 ? 16 : ch + 16; }
+
+// products of one tile for the NU units of a wave of wgrad_msp_kernel; xa / dyl: this lane's element of pixel (0, 0) of the x tile
+// and of the dy tile (inside its halo), bo: the units' B offsets, bb: the wave's bias channel
+template <int CH, bool BIAS, int NU>
+__device__ __forceinline__ void msp_tile_products(f32x4 (&acc)[MsPk<CH>::UW][MsPk<CH>::NG], float& bsum, const float* __restrict__ xa,
+                                                  const float* __restrict__ dyl, const int (&bo)[MsPk<CH>::UW], const float* __restrict__ bb) {
+    constexpr int MG = MsPk<CH>::NG, LDY = MsPk<CH>::LDY, LDX = ms_op_pitch(CH);
+#pragma unroll 1
+    for (int r = 0; r < MS_TH; ++r) {  // (unrolled, the compiler hoists a tile's every LDS read in front of the products and spills;
+                                       // reading row r + 1 behind scheduling barriers while row r is multiplied measured 20 - 50 % slower)
+        float bv[16];
+        if (BIAS) {
+#pragma unroll
+            for (int c = 0; c < 16; ++c) bv[c] = bb[(r * MS_PW + c) * LDY];
+        }
+#pragma unroll
+        for (int xs4 = 0; xs4 < 4; ++xs4) {
+            float af[MG], bf[NU];
+#pragma unroll
+            for (int mf = 0; mf < MG; ++mf) af[mf] = xa[(r * 16 + 4 * xs4) * LDX + 16 * mf];
+#pragma unroll
+            for (int k = 0; k < NU; ++k) bf[k] = dyl[bo[k] + (r * MS_PW + 4 * xs4) * LDY];
+#pragma unroll
+            for (int k = 0; k < NU; ++k)
+#pragma unroll
+                for (int mf = 0; mf < MG; ++mf) acc[k][mf] = mfma16(af[mf], bf[k], acc[k][mf]);
+        }
+        if (BIAS) {
+#pragma unroll
+            for (int c = 0; c < 16; ++c) bsum += bv[c];
+        }
+    }
+}
+
+template <int CH>
+__global__ __launch_bounds__(256, CH == 16 ? 4 : 2) void wgrad_msp_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                          float* __restrict__ partial, int N, int H, int W, int tiles_x,
+                                                                          int tiles_y, int ntiles) {
+    typedef MsPk<CH> G;
+    constexpr int UW = G::UW, U = G::U, LDY = G::LDY, MG = G::NG, LDX = ms_op_pitch(CH);
+    constexpr int NUS = U % 4 ? UW - 1 : UW;  // units of a short wave (role >= U % 4)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* xs = smem;                      // [TH*16][LDX]   all input channels
+    float* dyp = smem + MS_TH * 16 * LDX;  // [PH][PW][LDY]  all CH output-gradient channels, halo 4
+
+    const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
+    const int role = ms_wave_role(tid >> 6);
+
+    f32x4 acc[UW][MG];
+    int bo[UW];  // per-lane offset of this unit's B element inside the dy patch, relative to this lane's element of the tile
+#pragma unroll
+    for (int k = 0; k < UW; ++k) {
+        const int u = min(role + 4 * k, U - 1);
+        int off;
+        if (u < G::NFH) {
+            off = 16 * u;  // centre tap: dy channel 16 u + i
+        } else {
+            const int j = 1 + (u - G::NFH) / G::UPB, m = (u - G::NFH) % G::UPB;  // branch, unit inside the ring
+            const int sidx = i / G::C4, co = i % G::C4, i8 = m * G::TPU + sidx, t9 = i8 < 4 ? i8 : i8 + 1, d = 1 << (j - 1);
+            const int oy = (t9 / 3 - 1) * d, ox = (t9 % 3 - 1) * d;
+            off = (-oy * MS_PW - ox) * LDY + j * G::C4 + co - i;  // dy[p' - tap][branch channel]
+        }
+        bo[k] = off;
+#pragma unroll
+        for (int mf = 0; mf < MG; ++mf) acc[k][mf] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const bool short_wave = U % 4 != 0 && role >= U % 4, bias_wave = role >= 4 - CH / 16;
+    static_assert(U % 4 == 0 || 4 - CH / 16 >= U % 4, "the bias waves are short waves");
+    const int bch = 16 * (role - (4 - CH / 16)) + i;  // the channel a bias wave's lane sums
+    const float* xa = xs + g * LDX + i;
+    const float* dyl = dyp + (4 * MS_PW + 4 + g) * LDY + i;
+    const float* bb = dyp + (4 * MS_PW + 4) * LDY + (bias_wave ? bch : 0);
+
+    float bsum = 0.f;
+    const size_t plane = (size_t)H * W;
+    MsTileWindow<MS_TH, 16, CH / 4, LDX> wx;
+    MsTileWindow<MS_PH, MS_PW, CH / 4, LDY> wd;
+    wx.init(W, CH, tid);
+    wd.init(W, CH, tid);
+    auto fetch = [&](int tile) {
+        const int tx0 = tile % tiles_x, ty0 = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
+        wx.fetch(x + (size_t)n * plane * CH, ty0 * MS_TH, tx0 * 16, H, W, CH, tid);
+        wd.fetch(dy + (size_t)n * plane * CH, ty0 * MS_TH - 4, tx0 * 16 - 4, H, W, CH, tid);
+    };
+    if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        __syncthreads();  // the previous tile's products are done with the LDS
+        wx.commit(xs, tid);
+        wd.commit(dyp, tid);
+        __syncthreads();
+        if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x);
+        if (bias_wave) msp_tile_products<CH, true, NUS>(acc, bsum, xa, dyl, bo, bb);
+        else if (NUS != UW && short_wave) msp_tile_products<CH, false, NUS>(acc, bsum, xa, dyl, bo, bb);
+        else msp_tile_products<CH, false, UW>(acc, bsum, xa, dyl, bo, bb);
+    }
+    float* out = partial + (size_t)blockIdx.x * G::PSTRIDE;
+    if (bias_wave && g == 0) out[G::NG * U * 256 + bch] = bsum;
+    const int nu = (U - role + 3) / 4;
+#pragma unroll
+    for (int k = 0; k < UW; ++k) {
+        if (k >= nu) continue;
+        const int u = role + 4 * k;
+#pragma unroll
+        for (int mf = 0; mf < MG; ++mf) {
+            float* o = out + ((size_t)mf * U + u) * 256;  // [chunk mf][unit][m = input channel 4g + e][n = i]
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[(4 * g + e) * 16 + i] = acc[k][mf][e];
+        }
+    }
+}
+
+// products of one tile for the NU units of a wave of wgrad_ms_kernel; ao / ho: the units' A offsets in the patch and B offsets in
+// the dy tile (this lane's element of pixel (0, 0) included), bb: the wave's bias channel in the dy tile
+template <int CH, bool BIAS, int NU, int UW>
+__device__ __forceinline__ void ms_tile_products(f32x4 (&acc)[UW], float& bsum, const float* __restrict__ patch, const float* __restrict__ ht,
+                                                 const int (&ao)[UW], const int (&ho)[UW], const float* __restrict__ bb) {
+    constexpr int BNP = ms_op_pitch(CH), CKP = 16;  // (the dense patch: conflict-free, see ms_op_pitch)
+#pragma unroll 1
+    for (int r = 0; r < MS_TH; ++r) {  // (unrolled, the compiler hoists a tile's every LDS read in front of the products and spills;
+                                       // reading row r + 1 behind scheduling barriers while row r is multiplied measured 20 - 50 % slower)
+        float bv[16];
+        if (BIAS) {
+#pragma unroll
+            for (int c = 0; c < 16; ++c) bv[c] = bb[(r * 16 + c) * BNP];
+        }
+#pragma unroll
+        for (int xs4 = 0; xs4 < 4; ++xs4) {
+            float af[NU], bf[NU];
+#pragma unroll
+            for (int k = 0; k < NU; ++k) {
+                af[k] = patch[ao[k] + (r * MS_PW + 4 * xs4) * CKP];
+                bf[k] = ht[ho[k] + (r * 16 + 4 * xs4) * BNP];
+            }
+#pragma unroll
+            for (int k = 0; k < NU; ++k) acc[k] = mfma16(af[k], bf[k], acc[k]);
+        }
+        if (BIAS) {
+#pragma unroll
+            for (int c = 0; c < 16; ++c) bsum += bv[c];
+        }
+    }
+}
+
+template <int CH>
+__global__ __launch_bounds__(256, 2) void wgrad_ms_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                          float* __restrict__ partial, int N, int H, int W, int tiles_x, int tiles_y,
+                                                          int ntiles) {
+    constexpr int NFH = CH / 16, C4 = CH / 4, U = NFH + 24, UW = (U + 3) / 4, BNP = ms_op_pitch(CH), CKP = 16, NG = CH / 16;
+    constexpr int PSTRIDE = NG * U * 256 + CH, NUS = U % 4 ? UW - 1 : UW;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* patch = smem;                        // [PH][PW][CKP]   16 input channels of this chunk, dense
+    float* ht = smem + MS_PH * MS_PW * CKP;  // [TH*16][BNP]    all CH output-gradient channels
+
+    const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
+    const int role = ms_wave_role(tid >> 6);
+    const int gchunk = blockIdx.y, g0 = 16 * gchunk;
+
+    f32x4 acc[UW];
+    int ao[UW], ho[UW];
+#pragma unroll
+    for (int k = 0; k < UW; ++k) {
+        const int u = min(role + 4 * k, U - 1);
+        int dyp = 0, dxp = 0, frag = u;  // centre tap: fragment u
+        if (u >= NFH) {
+            const int r = (u - NFH) >> 3, i8 = (u - NFH) & 7, t9 = i8 < 4 ? i8 : i8 + 1, d = 1 << r;
+            dyp = (t9 / 3 - 1) * d;
+            dxp = (t9 % 3 - 1) * d;
+            frag = ((r + 1) * C4) / 16;
+        }
+        ao[k] = ((4 + dyp) * MS_PW + 4 + dxp + g) * CKP + i;
+        ho[k] = g * BNP + 16 * frag + i;
+        acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const bool short_wave = U % 4 != 0 && role >= U % 4, bias_wave = gchunk == 0 && role >= 4 - CH / 16;
+    static_assert(U % 4 == 0 || 4 - CH / 16 >= U % 4, "the bias waves are short waves");
+    const int bch = 16 * (role - (4 - CH / 16)) + i;  // the channel a bias wave's lane sums
+    const float* bb = ht + (bias_wave ? bch : 0);
+
+    float bsum = 0.f;
+    const size_t plane = (size_t)H * W;
+    MsTileWindow<MS_PH, MS_PW, 4, CKP> wx;
+    MsTileWindow<MS_TH, 16, CH / 4, BNP> wd;
+    wx.init(W, CH, tid);
+    wd.init(W, CH, tid);
+    auto fetch = [&](int tile) {
+        const int tx0 = tile % tiles_x, ty0 = (tile / tiles_x) % tiles_y, n = tile / (tiles_x * tiles_y);
+        wx.fetch(x + (size_t)n * plane * CH + g0, ty0 * MS_TH - 4, tx0 * 16 - 4, H, W, CH, tid);
+        wd.fetch(dy + (size_t)n * plane * CH, ty0 * MS_TH, tx0 * 16, H, W, CH, tid);
+    };
+    if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        __syncthreads();  // the previous tile's products are done with the LDS
+        wx.commit(patch, tid);
+        wd.commit(ht, tid);
+        __syncthreads();
+        if (tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x);
+        if (bias_wave) ms_tile_products<CH, true, NUS, UW>(acc, bsum, patch, ht, ao, ho, bb);
+        else if (NUS != UW && short_wave) ms_tile_products<CH, false, NUS, UW>(acc, bsum, patch, ht, ao, ho, bb);
+        else ms_tile_products<CH, false, UW, UW>(acc, bsum, patch, ht, ao, ho, bb);
+    }
+    float* out = partial + (size_t)blockIdx.x * PSTRIDE;
+    if (bias_wave && g == 0) out[NG * U * 256 + bch] = bsum;
+    const int nu = (U - role + 3) / 4;
+#pragma unroll
+    for (int k = 0; k < UW; ++k) {
+        if (k >= nu) continue;
+        const int u = role + 4 * k;
+        // accumulator element e of lane (i, g): row m = 4g + e (input channel g0 + m), column n = i
+        float* o = out + ((size_t)gchunk * U + u) * 256;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[(4 * g + e) * 16 + i] = acc[k][e];
     }
 }
 
@@ -875,32 +1173,39 @@ static int launch_ms_wgrad(const float* x, const float* dy, const MsGradPtrs& ou
     int S, tiles_x, tiles_y, ntiles;
     const size_t need = ms_wgrad_plan<CH>(N, H, W, S, tiles_x, tiles_y, ntiles);
     if (!ws || ws_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "msblock_wgrad: workspace too small");
-    const size_t lds = (size_t)(MS_PH * MS_PW * MS_CKP + MS_TH * 16 * (CH + 4)) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_ms_kernel<CH>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024);
-        if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(wgrad_ms)");
-        attr_set = true;
-    }
+    typedef void (*kern_t)(const float*, const float*, float*, int, int, int, int, int, int);
+    // MSTG_MS_WGRAD_PF=0: the synchronous kernels (same slabs, bit for bit)
+    const char* epf = env_get(ENV_MS_WGRAD_PF);
+    const int pf = !(epf && epf[0] == '0');
+    // the synchronous kernels pad a pixel's channels by 4 floats, the default ones by what ms_op_pitch says
+    const size_t lds =
+        (size_t)(pf ? MS_PH * MS_PW * 16 + MS_TH * 16 * ms_op_pitch(CH) : MS_PH * MS_PW * MS_CKP + MS_TH * 16 * (CH + 4)) * sizeof(float);
     if (ms_wgrad_packed<CH>()) {
-        typedef MsPk<CH> P;
-        const size_t ldsp = (size_t)(MS_TH * 16 * (CH + 4) + MS_PH * MS_PW * P::LDY) * sizeof(float);
-        static bool attr_set_p = false;
-        if (!attr_set_p) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_msp_kernel<CH>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        typedef MsPk<(CH <= 32 ? CH : 16)> P;
+        constexpr int CP = CH <= 32 ? CH : 16;
+        const size_t ldsp = (size_t)(MS_TH * 16 * (pf ? ms_op_pitch(CH) : CH + 4) + MS_PH * MS_PW * P::LDY) * sizeof(float);
+        const kern_t kern = pf ? &wgrad_msp_kernel<CP> : &wgrad_msp_sync_kernel<CP>;
+        static bool attr_set_p[2] = {false, false};
+        if (!attr_set_p[pf]) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(wgrad_msp)");
-            attr_set_p = true;
+            attr_set_p[pf] = true;
         }
         const int Sp = S * NG > ntiles ? ntiles : S * NG;  // one workgroup covers every input-channel chunk: keep the workgroup count
-        MSTG_LAUNCH((wgrad_msp_kernel<CH>), dim3(Sp, 1, 1), dim3(256), ldsp, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
+        MSTG_LAUNCH(kern, dim3(Sp, 1, 1), dim3(256), ldsp, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
         MSTG_CHECK_LAUNCH("wgrad_msp_kernel");
-        MSTG_LAUNCH((wgrad_msp_reduce_kernel<CH>), dim3(cdiv(P::PSTRIDE, 16)), dim3(256), 0, st, (const float*)ws, out, Sp, accumulate);
+        MSTG_LAUNCH((wgrad_msp_reduce_kernel<CP>), dim3(cdiv(P::PSTRIDE, 16)), dim3(256), 0, st, (const float*)ws, out, Sp, accumulate);
         MSTG_CHECK_LAUNCH("wgrad_msp_reduce_kernel");
         return MSTG_OK;
     }
-    MSTG_LAUNCH((wgrad_ms_kernel<CH>), dim3(S, NG, 1), dim3(256), lds, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
+    const kern_t kern = pf ? &wgrad_ms_kernel<CH> : &wgrad_ms_sync_kernel<CH>;
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[pf]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(wgrad_ms)");
+        attr_set[pf] = true;
+    }
+    MSTG_LAUNCH(kern, dim3(S, NG, 1), dim3(256), lds, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
     MSTG_CHECK_LAUNCH("wgrad_ms_kernel");
     MSTG_LAUNCH((wgrad_ms_reduce_kernel<CH>), dim3(cdiv(PSTRIDE, 16)), dim3(256), 0, st, (const float*)ws, out, S, accumulate);
     MSTG_CHECK_LAUNCH("wgrad_ms_reduce_kernel");
