@@ -115,7 +115,8 @@ int mstg_msblock_dgrad_cached(const float* dy, const float* w1, const float* w2,
                               float* dx, int N, int H, int W, int CH, void* workspace, size_t workspace_bytes, int workspace_packed,
                               void* stream);
 
-/* name of the kernel a pass (0 forward, 1 dgrad, 2 wgrad) of this layer launches, as a profiler prints it (for reports) */
+/* name of the kernel a pass (0 forward, 1 dgrad, 2 wgrad; 3 forward with the statistics epilogue of mstg_conv2d_fwd_norm, 4 dgrad with
+ * the backward-sums epilogue of mstg_conv2d_dgrad_bsums) of this layer launches, as a profiler prints it (for reports and pack keys) */
 const char* mstg_conv2d_kernel_name(const mstg_conv_desc* d, int pass);
 /* workspace of fwd and dgrad: room for the filter re-packed into the order the kernel stages it (a few 100 KB at most) */
 size_t mstg_conv2d_workspace_bytes(const mstg_conv_desc* d);
@@ -226,6 +227,11 @@ size_t mstg_window_attn_bwd_workspace_bytes(int N, int H, int W, int C);
 int mstg_window_attn_bwd(const float* x, const float* wqkv, const float* bqkv, const float* wproj, const float* bproj,
                          const float* dy, float* dx, float* dparams, int N, int H, int W, int C, void* workspace,
                          size_t workspace_bytes, void* stream);
+/* name of the kernel that does the arithmetic of a pass (0 forward, 1 backward) of the window-attention core (fused == 0; norm is
+ * ignored) or of the fused LocalAttention (fused != 0; norm != 0: the mstg_window_attn_norm_* forms) at width C, as a profiler
+ * prints it and under the switches as last read, e.g. "attn_core_bwd_blk4_kernel<256>", "attn_reg_bwd_kernel<16, true, 4>";
+ * "" for a width without such a path. */
+const char* mstg_window_attn_kernel_name(int fused, int pass, int C, int norm);
 
 /* ------------------------------------------------------------------------------------------------
  * Element-wise / reduction helpers of the training step (enhanced_train.py:49-52,72-115,36-43).
@@ -291,6 +297,11 @@ size_t mstg_msblock_wgrad_workspace_bytes(int N, int H, int W, int CH);
 int mstg_msblock_wgrad(const float* x, const float* dy, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3,
                        float* dw4, float* db4, int accumulate /* != 0: add to what the eight buffers hold */, int N, int H, int W,
                        int CH, void* workspace, size_t workspace_bytes, void* stream);
+/* name of the kernel that does the arithmetic of a pass (0 forward, 1 dgrad, 2 wgrad) of the block, as a profiler prints it and
+ * under the switches as last read, e.g. "ms_fwd4b_kernel<32>", "wgrad_msp_sync_kernel<16>"; "" for a width without fused path.
+ * bias_aligned: whether b1..b4 of the forward call all lie on 16-byte boundaries (the forward's route depends on it, and on H;
+ * a filter pack kept in the workspace belongs to the kernel named here). */
+const char* mstg_msblock_kernel_name(int pass, int N, int H, int W, int CH, int bias_aligned);
 
 /* torch.nn.utils.spectral_norm on a conv weight seen as an (M = Cout, K = Cin*kh*kw) matrix (enhanced_generator.py:269-271).
  * fwd: training != 0 runs the one power iteration in place on u (M) and v (K); always sigma = u.(W v), w_out = w / sigma.

@@ -64,6 +64,8 @@ SIGNATURES = {
     "mstg_prof_count": (_i, []),
     "mstg_prof_get": (_i, [_i, C.c_char_p, _sz, C.POINTER(C.c_float)]),
     "mstg_conv2d_kernel_name": (C.c_char_p, [_dp, _i]),
+    "mstg_msblock_kernel_name": (C.c_char_p, [_i] * 6),
+    "mstg_window_attn_kernel_name": (C.c_char_p, [_i] * 4),
     "mstg_conv2d_workspace_bytes": (_sz, [_dp]),
     "mstg_conv2d_fwd": (_i, [_dp, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "mstg_conv2d_dgrad": (_i, [_dp, _fp, _fp, _fp, _vp, _sz, _vp]),

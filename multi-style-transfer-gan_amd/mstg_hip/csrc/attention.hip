@@ -8,6 +8,7 @@
 //
 // Reference site replaced: enhanced_generator.py:22-35,39-42 (view/permute/contiguous window partition, two
 // F.normalize, two batched matmuls, softmax, inverse permute).
+#include "attn_route.h"
 #include "lanes.h"
 
 namespace mstg {
@@ -651,7 +652,6 @@ struct AttnGradDst {
     float* p[4];  // dWqkv (3C x C), dWp (C x C), dbqkv (3C), dbp (C)
     int accumulate;
 };
-thread_local AttnGradDst t_attn_dst = {{nullptr, nullptr, nullptr, nullptr}, 0};
 
 // out[e] = sum_s partial[s][e], fixed order; 16 outputs x 16 strided rows per workgroup
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ partial, float* __restrict__ out, int S, int n,
@@ -705,14 +705,12 @@ __global__ __launch_bounds__(256) void nsum_reduce_kernel(const float* __restric
     }
 }
 
-int attn_reg_bwd_blocks(int C);
-int attn_reg_bwd_waves(int C);
 // windows per run of the NORM backward: the largest divisor of the windows per image that is <= 16 -- and small enough that every
 // wave of the backward gets about two runs (a run is the unit of work there: with 16-window runs a 16-image batch at 128 x 128
 // gave half the waves nothing to do)
-static int norm_run_len(int N, int H, int W, int C) {
+static int norm_run_len(const AttnFusedRoute& r, int N, int H, int W) {
     const int wpi = (H / 4) * (W / 4);
-    const long waves = (long)attn_reg_bwd_blocks(C) * attn_reg_bwd_waves(C);
+    const long waves = (long)attn_reg_bwd_blocks(r) * r.bwd_waves;
     long cap = ((long)N * wpi) / (2 * waves);
     if (cap > 16) cap = 16;
     if (cap < 1) cap = 1;
@@ -727,43 +725,38 @@ static int fused_blocks(int N, int H, int W) {
     return nwin < 2048 ? nwin : 2048;  // one-wave workgroups: 8 per CU
 }
 
-// The register-resident kernels of csrc/attention_reg.hip (round 3): the default; MSTG_ATTN_REG=0 selects the LDS-tile kernels above.
-int attn_reg_fwd(int C, const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* bp,
-                 float* y, int N, int H, int W, hipStream_t st);
-int attn_reg_bwd(int C, const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* dy,
-                 float* dx, float* partial, float* nsum, int kblk, int nblocks, int N, int H, int W, hipStream_t st);
-static bool attn_reg_on() {
-    const char* e = env_get(ENV_ATTN_REG);
-    return !(e && e[0] == '0');
+// floats of one weight-gradient slab of the fused backward: dWqkv | dWp | dbqkv | dbp
+constexpr int fused_slab(int C) { return 4 * C * C + 4 * C; }
+// workspace of the fused backward: [weight-gradient slabs: nb * slab][norm forms: nsum rows, N * runs per image * 2C]
+static size_t fused_ws_bytes(const AttnFusedRoute& r, int N, int H, int W, bool norm) {
+    if (N <= 0 || H <= 0 || W <= 0 || r.kind == AF_NONE) return 0;
+    const size_t nsum = norm ? (size_t)N * ((H / 4) * (W / 4) / norm_run_len(r, N, H, W)) * 2 * r.C : 0;
+    return ((size_t)fused_blocks(N, H, W) * fused_slab(r.C) + nsum) * sizeof(float);
 }
 
-// in_stats != nullptr: x is the raw tensor in front of InstanceNorm + ReLU; backward then also fills norm_sums[N][2][C]
-// (workspace layout: [weight-gradient slabs: nb * SLAB][nsum rows: N * nb * 2C])
+// The route (attn_route.h) chooses the register-resident kernels of csrc/attention_reg.hip (round 3, the default) or the LDS-tile
+// kernels above.  in_stats != nullptr: x is the raw tensor in front of InstanceNorm + ReLU; backward then also fills
+// norm_sums[N][2][C].  dst: where the reduced parameter gradients go instead of `grads` (AttnGradDst)
 template <int C>
-struct FusedSlab {
-    static constexpr int SLAB = 4 * C * C + 4 * C;  // dWqkv | dWp | dbqkv | dbp
-};
-
-template <int C>
-static int launch_fused(bool bwd, const float* x, const float* wqkv, const float* bqkv, const float* wp, const float* bp,
-                        const float* dy, float* out, float* grads, float* partial, int N, int H, int W, hipStream_t st,
-                        const float* in_stats = nullptr, float* norm_sums = nullptr) {
-    typedef FusedSlab<C> F;
+static int launch_fused(const AttnFusedRoute& r, bool bwd, const float* x, const float* wqkv, const float* bqkv, const float* wp,
+                        const float* bp, const float* dy, float* out, float* grads, const AttnGradDst& dst, float* partial, int N, int H,
+                        int W, hipStream_t st, const float* in_stats, float* norm_sums) {
+    constexpr int SLAB = fused_slab(C);
     const int nb = fused_blocks(N, H, W);
-    if (attn_reg_on() || C > 32) {  // C = 64 exists only as the register-chain kernel
-        if (!bwd) return attn_reg_fwd(C, x, in_stats, wqkv, bqkv, wp, bp, out, N, H, W, st);
+    if (r.kind != AF_FUSED) {
+        if (!bwd) return attn_reg_fwd(r, x, in_stats, wqkv, bqkv, wp, bp, out, N, H, W, st);
         // slabs: one per workgroup of four waves, never more workgroups than runs / 4 (and so never more than the nb slabs the
         // workspace was sized for); the nsum rows sit behind the nb-slab region as before
-        const int kblk = in_stats ? norm_run_len(N, H, W, C) : 1, R = (H / 4) * (W / 4) / kblk, nrun = N * R;
-        int nbr = attn_reg_bwd_blocks(C);
-        if (nbr > cdiv(nrun, attn_reg_bwd_waves(C))) nbr = cdiv(nrun, attn_reg_bwd_waves(C));
-        float* nsum = partial + (size_t)nb * F::SLAB;
-        if (int rc = attn_reg_bwd(C, x, in_stats, wqkv, bqkv, wp, dy, out, partial, in_stats ? nsum : nullptr, kblk, nbr, N, H, W, st)) return rc;
+        const int kblk = in_stats ? norm_run_len(r, N, H, W) : 1, R = (H / 4) * (W / 4) / kblk, nrun = N * R;
+        int nbr = attn_reg_bwd_blocks(r);
+        if (nbr > cdiv(nrun, r.bwd_waves)) nbr = cdiv(nrun, r.bwd_waves);
+        float* nsum = partial + (size_t)nb * SLAB;
+        if (int rc = attn_reg_bwd(r, x, in_stats, wqkv, bqkv, wp, dy, out, partial, in_stats ? nsum : nullptr, kblk, nbr, N, H, W, st)) return rc;
         if (in_stats) {
             MSTG_LAUNCH(nsum_reduce_kernel, dim3(NSUM_SPLIT, N), dim3(256), 0, st, (const float*)nsum, norm_sums, R, NSUM_SPLIT, 2 * C);
             MSTG_CHECK_LAUNCH("nsum_reduce_kernel");
         }
-        MSTG_LAUNCH(slab_reduce_kernel, dim3(cdiv(F::SLAB, 16)), dim3(256), 0, st, (const float*)partial, grads, nbr, F::SLAB, t_attn_dst, C);
+        MSTG_LAUNCH(slab_reduce_kernel, dim3(cdiv(SLAB, 16)), dim3(256), 0, st, (const float*)partial, grads, nbr, SLAB, dst, C);
         MSTG_CHECK_LAUNCH("slab_reduce_kernel");
         return MSTG_OK;
     }
@@ -780,8 +773,8 @@ static int launch_fused(bool bwd, const float* x, const float* wqkv, const float
             return MSTG_OK;
         }
         if (in_stats) {
-            float* nsum = partial + (size_t)nb * F::SLAB;
-            const int kblk = norm_run_len(N, H, W, C), R = (H / 4) * (W / 4) / kblk;
+            float* nsum = partial + (size_t)nb * SLAB;
+            const int kblk = norm_run_len(r, N, H, W), R = (H / 4) * (W / 4) / kblk;
             MSTG_LAUNCH((attn_fused_bwd_kernel<C, true>), dim3(nb), dim3(64), (size_t)T::END_BWD * sizeof(float), st, x, wqkv, bqkv, wp, bp, dy,
                                out, partial, N, H, W, in_stats, nsum, kblk);
             MSTG_CHECK_LAUNCH("attn_fused_bwd_kernel<norm>");
@@ -792,7 +785,7 @@ static int launch_fused(bool bwd, const float* x, const float* wqkv, const float
                                out, partial, N, H, W, in_stats, (float*)nullptr, 1);
             MSTG_CHECK_LAUNCH("attn_fused_bwd_kernel");
         }
-        MSTG_LAUNCH(slab_reduce_kernel, dim3(cdiv(F::SLAB, 16)), dim3(256), 0, st, (const float*)partial, grads, nb, F::SLAB, t_attn_dst, C);
+        MSTG_LAUNCH(slab_reduce_kernel, dim3(cdiv(SLAB, 16)), dim3(256), 0, st, (const float*)partial, grads, nb, SLAB, dst, C);
         MSTG_CHECK_LAUNCH("slab_reduce_kernel");
     }
     return MSTG_OK;
@@ -1233,67 +1226,6 @@ __global__ __launch_bounds__(256) void attn_core_bwd_blk4_kernel(const float* __
     }
 }
 
-template <int CP>
-static int launch_attn_blk4(bool bwd, const float* qkv, const float* d_o, float* out, int N, int H, int W, int C, hipStream_t st) {
-    typedef Blk4Tiles<CP> T;
-    const size_t lds = (size_t)(bwd ? T::END_BWD : T::END_FWD) * sizeof(float);
-    const int nwin = N * (H / 4) * (W / 4);
-    int per_cu = (int)((160 * 1024) / lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 2 ? 2 : per_cu);
-    int grid = 256 * per_cu * 2;  // two rounds of resident workgroups: evens out windows of unequal cost at no extra LDS
-    if (grid > nwin) grid = nwin;
-    static bool set_f = false, set_b = false;
-    bool& set = bwd ? set_b : set_f;
-    if (!set) {
-        hipError_t e = bwd ? hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_core_bwd_blk4_kernel<CP>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-                           : hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_core_fwd_blk4_kernel<CP>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(attn_blk4)");
-        set = true;
-    }
-    if (bwd) MSTG_LAUNCH((attn_core_bwd_blk4_kernel<CP>), dim3(grid), dim3(256), lds, st, qkv, d_o, out, N, H, W, C);
-    else MSTG_LAUNCH((attn_core_fwd_blk4_kernel<CP>), dim3(grid), dim3(256), lds, st, qkv, out, N, H, W, C);
-    MSTG_CHECK_LAUNCH("attn_core_blk4_kernel");
-    return MSTG_OK;
-}
-
-template <int CP>
-static int launch_attn_blk(bool bwd, const float* qkv, const float* d_o, float* out, int N, int H, int W, int C, hipStream_t st) {
-    typedef BlkTiles<CP> T;
-    const size_t lds = (size_t)(bwd ? T::END_BWD : T::END_FWD) * sizeof(float);
-    const int nwin = N * (H / 4) * (W / 4);
-    int per_cu = (int)((160 * 1024) / lds);
-    per_cu = per_cu < 4 ? 4 : (per_cu > 8 ? 8 : per_cu);
-    int grid = 256 * per_cu;
-    if (grid > nwin) grid = nwin;
-    static bool set_f = false, set_b = false;
-    bool& set = bwd ? set_b : set_f;
-    if (!set) {
-        hipError_t e = bwd ? hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_core_bwd_blk_kernel<CP>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-                           : hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_core_fwd_blk_kernel<CP>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(attn_blk)");
-        set = true;
-    }
-    if (bwd) MSTG_LAUNCH((attn_core_bwd_blk_kernel<CP>), dim3(grid), dim3(64), lds, st, qkv, d_o, out, N, H, W, C);
-    else MSTG_LAUNCH((attn_core_fwd_blk_kernel<CP>), dim3(grid), dim3(64), lds, st, qkv, out, N, H, W, C);
-    MSTG_CHECK_LAUNCH("attn_core_blk_kernel");
-    return MSTG_OK;
-}
-
-static bool attn_blk4() {  // MSTG_ATTN_BLK4=0: one wave per window also above 64 channels
-    const char* e = env_get(ENV_ATTN_BLK4);
-    return !(e && e[0] == '0');
-}
-static bool attn_blk64() {
-    // 32 < C <= 64: the row-blocked kernel needs 26 KB of LDS per wave instead of 43 KB (6 waves per CU instead of 3) and was
-    // 1.4x (forward) / 1.65x (backward) faster at 256x256, C = 64; MSTG_ATTN_BLK64=0 selects the whole-matrix kernel
-    const char* e = env_get(ENV_ATTN_BLK64);
-    return !(e && e[0] == '0');
-}
-
 static int attn_check(int N, int H, int W, int C) {
     if (N <= 0 || H <= 0 || W <= 0 || C <= 0) return fail_arg(MSTG_E_BADARG, "window_attn: empty tensor");
     if (H % 4 || W % 4) return fail_arg(MSTG_E_BADARG, "window_attn: H and W must be multiples of the 4x4 window");
@@ -1302,54 +1234,115 @@ static int attn_check(int N, int H, int W, int C) {
     return MSTG_OK;
 }
 
-template <int CP>
+// ---- routing of the core passes: the only reader of MSTG_ATTN_BLK64 and MSTG_ATTN_BLK4 --------------------------------------------
+enum AttnCoreKind { AC_NONE, AC_WHOLE, AC_BLK, AC_BLK4 };  // attn_core_*_kernel / _blk_kernel / _blk4_kernel
+struct AttnCoreRoute {
+    AttnCoreKind kind;
+    int CP;         // C padded to the kernel's template width
+    char name[40];  // symbol of the pass's kernel, as the per-launch profiler reports it
+};
+static AttnCoreRoute attn_core_route(bool bwd, int C) {
+    AttnCoreRoute r{};
+    if (C <= 0 || C % 4 || C > 256) return r;
+    const char *e64 = env_get(ENV_ATTN_BLK64), *e4 = env_get(ENV_ATTN_BLK4);
+    r.CP = C <= 16 ? 16 : C <= 32 ? 32 : C <= 64 ? 64 : C <= 128 ? 128 : 256;
+    // 32 < C <= 64: the row-blocked kernel needs 26 KB of LDS per wave instead of 43 KB (6 waves per CU instead of 3) and was
+    // 1.4x (forward) / 1.65x (backward) faster at 256x256, C = 64; MSTG_ATTN_BLK64=0 selects the whole-matrix kernel.
+    // MSTG_ATTN_BLK4=0: one wave per window also above 64 channels
+    if (r.CP <= 32 || (r.CP == 64 && e64 && e64[0] == '0')) r.kind = AC_WHOLE;
+    else r.kind = r.CP == 64 || (e4 && e4[0] == '0') ? AC_BLK : AC_BLK4;
+    snprintf(r.name, sizeof(r.name), "attn_core_%s%s_kernel<%d>", bwd ? "bwd" : "fwd",
+             r.kind == AC_WHOLE ? "" : r.kind == AC_BLK ? "_blk" : "_blk4", r.CP);
+    return r;
+}
+
+// One launcher for the three kernel families.  Workgroups per CU (of 256): whole-matrix 8; row-blocked what the LDS holds, 4..8;
+// four-wave 1..2, times two rounds of resident workgroups (evens out windows of unequal cost at no extra LDS)
+template <int KIND, int CP>
 static int launch_attn(bool bwd, const float* qkv, const float* d_o, float* out, int N, int H, int W, int C, hipStream_t st) {
-    typedef AttnTiles<CP> T;
+    typedef std::conditional_t<KIND == AC_WHOLE, AttnTiles<CP>, std::conditional_t<KIND == AC_BLK, BlkTiles<CP>, Blk4Tiles<CP>>> T;
+    void (*kf)(const float*, float*, int, int, int, int);
+    void (*kb)(const float*, const float*, float*, int, int, int, int);
+    if constexpr (KIND == AC_WHOLE) kf = &attn_core_fwd_kernel<CP>, kb = &attn_core_bwd_kernel<CP>;
+    else if constexpr (KIND == AC_BLK) kf = &attn_core_fwd_blk_kernel<CP>, kb = &attn_core_bwd_blk_kernel<CP>;
+    else kf = &attn_core_fwd_blk4_kernel<CP>, kb = &attn_core_bwd_blk4_kernel<CP>;
     const size_t lds = (size_t)(bwd ? T::END_BWD : T::END_FWD) * sizeof(float);
-    const int nwin = N * (H / 4) * (W / 4);
-    int grid = 256 * 8;
+    const int nwin = N * (H / 4) * (W / 4), fit = (int)((160 * 1024) / lds);
+    int grid = 256 * (KIND == AC_WHOLE ? 8 : KIND == AC_BLK ? (fit < 4 ? 4 : fit > 8 ? 8 : fit) : 2 * (fit < 1 ? 1 : fit > 2 ? 2 : fit));
     if (grid > nwin) grid = nwin;
-    if (bwd) {
-        static bool set = false;
-        if (!set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_core_bwd_kernel<CP>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(attn_bwd)");
-            set = true;
-        }
-        MSTG_LAUNCH((attn_core_bwd_kernel<CP>), dim3(grid), dim3(64), lds, st, qkv, d_o, out, N, H, W, C);
-    } else {
-        MSTG_LAUNCH((attn_core_fwd_kernel<CP>), dim3(grid), dim3(64), lds, st, qkv, out, N, H, W, C);
+    static bool set[2] = {KIND == AC_WHOLE, false};  // (the whole-matrix forward stays below the default LDS limit)
+    if (!set[bwd]) {
+        hipError_t e = hipFuncSetAttribute(bwd ? (const void*)kb : (const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess)
+            return fail_launch(e, KIND == AC_WHOLE ? "hipFuncSetAttribute(attn_bwd)"
+                                                   : KIND == AC_BLK ? "hipFuncSetAttribute(attn_blk)" : "hipFuncSetAttribute(attn_blk4)");
+        set[bwd] = true;
     }
-    MSTG_CHECK_LAUNCH("attn_core_kernel");
+    const dim3 block(KIND == AC_BLK4 ? 256 : 64);
+    if (bwd) MSTG_LAUNCH(kb, dim3(grid), block, lds, st, qkv, d_o, out, N, H, W, C);
+    else MSTG_LAUNCH(kf, dim3(grid), block, lds, st, qkv, out, N, H, W, C);
+    MSTG_CHECK_LAUNCH(KIND == AC_WHOLE ? "attn_core_kernel" : KIND == AC_BLK ? "attn_core_blk_kernel" : "attn_core_blk4_kernel");
     return MSTG_OK;
 }
+
+static int attn_core(bool bwd, const float* qkv, const float* d_o, float* out, int N, int H, int W, int C, hipStream_t st) {
+    const AttnCoreRoute r = attn_core_route(bwd, C);
+    int rc = MSTG_OK;
+    if (r.kind == AC_WHOLE) for_width<16, 32, 64>(r.CP, [&](auto cp) { rc = launch_attn<AC_WHOLE, cp()>(bwd, qkv, d_o, out, N, H, W, C, st); });
+    else if (r.kind == AC_BLK) for_width<64, 128, 256>(r.CP, [&](auto cp) { rc = launch_attn<AC_BLK, cp()>(bwd, qkv, d_o, out, N, H, W, C, st); });
+    else for_width<128, 256>(r.CP, [&](auto cp) { rc = launch_attn<AC_BLK4, cp()>(bwd, qkv, d_o, out, N, H, W, C, st); });
+    return rc;
+}
+
+// Every fused entry point.  `entry` names it in the error messages; norm: x is the raw tensor in front of InstanceNorm + ReLU
+// (in_stats; the backward also fills norm_sums); the backward's parameter gradients go to dparams (flat) or, dst.p[0] set, to dst.
+static int attn_fused(const char* entry, bool bwd, bool norm, const float* x, const float* in_stats, const float* wqkv, const float* bqkv,
+                      const float* wproj, const float* bproj, const float* dy, float* out, float* dparams, const AttnGradDst& dst,
+                      float* norm_sums, int N, int H, int W, int C, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = attn_check(N, H, W, C)) return rc;
+    const auto fail = [&](int code, const char* what) {
+        snprintf(g_last_error, sizeof(g_last_error), "%s: %s", entry, what);
+        return code;
+    };
+    if (!x || (norm && !in_stats) || !wqkv || !bqkv || !wproj || !bproj || !out ||
+        (bwd && (!dy || (!dparams && !dst.p[0]) || (norm && !norm_sums) || !workspace)))
+        return fail(MSTG_E_BADARG, "null pointer");
+    const AttnFusedRoute r = attn_fused_route(bwd, C, norm);
+    if (r.kind == AF_NONE)
+        return fail(MSTG_E_UNSUPPORTED, bwd || norm ? "fused kernel exists for C = 16, 32 and 64"
+                                                    : "fused kernel exists for C = 16, 32 and 64 (use the qkv/core/proj chain otherwise)");
+    if (bwd && workspace_bytes < fused_ws_bytes(r, N, H, W, norm)) return fail(MSTG_E_WORKSPACE, "workspace too small");
+    int rc = MSTG_OK;
+    for_width<16, 32, 64>(C, [&](auto c) {
+        rc = launch_fused<c()>(r, bwd, x, wqkv, bqkv, wproj, bproj, dy, out, dparams, dst, (float*)workspace, N, H, W, (hipStream_t)stream,
+                               norm ? in_stats : nullptr, norm_sums);
+    });
+    return rc;
+}
+constexpr AttnGradDst NO_DST = {{nullptr, nullptr, nullptr, nullptr}, 0};
 
 }  // namespace mstg
 
 using namespace mstg;
 
+extern "C" const char* mstg_window_attn_kernel_name(int fused, int pass, int C, int norm) {
+    static thread_local char name[48];
+    if (pass != 0 && pass != 1) return "";
+    snprintf(name, sizeof(name), "%s", fused ? attn_fused_route(pass, C, norm != 0).name : attn_core_route(pass, C).name);
+    return name;
+}
+
 extern "C" int mstg_window_attn_core_fwd(const float* qkv, float* o, int N, int H, int W, int C, void* stream) {
     if (int rc = attn_check(N, H, W, C)) return rc;
     if (!qkv || !o) return fail_arg(MSTG_E_BADARG, "window_attn_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (C <= 16) return launch_attn<16>(false, qkv, nullptr, o, N, H, W, C, st);
-    if (C <= 32) return launch_attn<32>(false, qkv, nullptr, o, N, H, W, C, st);
-    if (C <= 64) return attn_blk64() ? launch_attn_blk<64>(false, qkv, nullptr, o, N, H, W, C, st) : launch_attn<64>(false, qkv, nullptr, o, N, H, W, C, st);
-    if (C <= 128) return attn_blk4() ? launch_attn_blk4<128>(false, qkv, nullptr, o, N, H, W, C, st) : launch_attn_blk<128>(false, qkv, nullptr, o, N, H, W, C, st);
-    return attn_blk4() ? launch_attn_blk4<256>(false, qkv, nullptr, o, N, H, W, C, st) : launch_attn_blk<256>(false, qkv, nullptr, o, N, H, W, C, st);
+    return attn_core(false, qkv, nullptr, o, N, H, W, C, (hipStream_t)stream);
 }
 
 extern "C" int mstg_window_attn_core_bwd(const float* qkv, const float* d_o, float* dqkv, int N, int H, int W, int C,
                                          void* stream) {
     if (int rc = attn_check(N, H, W, C)) return rc;
     if (!qkv || !d_o || !dqkv) return fail_arg(MSTG_E_BADARG, "window_attn_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (C <= 16) return launch_attn<16>(true, qkv, d_o, dqkv, N, H, W, C, st);
-    if (C <= 32) return launch_attn<32>(true, qkv, d_o, dqkv, N, H, W, C, st);
-    if (C <= 64) return attn_blk64() ? launch_attn_blk<64>(true, qkv, d_o, dqkv, N, H, W, C, st) : launch_attn<64>(true, qkv, d_o, dqkv, N, H, W, C, st);
-    if (C <= 128) return attn_blk4() ? launch_attn_blk4<128>(true, qkv, d_o, dqkv, N, H, W, C, st) : launch_attn_blk<128>(true, qkv, d_o, dqkv, N, H, W, C, st);
-    return attn_blk4() ? launch_attn_blk4<256>(true, qkv, d_o, dqkv, N, H, W, C, st) : launch_attn_blk<256>(true, qkv, d_o, dqkv, N, H, W, C, st);
+    return attn_core(true, qkv, d_o, dqkv, N, H, W, C, (hipStream_t)stream);
 }
 
 #ifdef MSTG_STAMPS
@@ -1360,92 +1353,58 @@ extern "C" int mstg_debug_stamps_attn_fwd(unsigned long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_att_fstamps), sizeof(unsigned long long) * 64 * 8);
 }
 #endif
-extern "C" int mstg_window_attn_fused_supported(int C) { return C == 16 || C == 32 || C == 64; }
+extern "C" int mstg_window_attn_fused_supported(int C) { return attn_fused_route(false, C, false).kind != AF_NONE; }
 
 extern "C" int mstg_window_attn_fwd(const float* x, const float* wqkv, const float* bqkv, const float* wproj, const float* bproj,
                                     float* y, int N, int H, int W, int C, void* stream) {
-    if (int rc = attn_check(N, H, W, C)) return rc;
-    if (!x || !wqkv || !bqkv || !wproj || !bproj || !y) return fail_arg(MSTG_E_BADARG, "window_attn_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (C == 16) return launch_fused<16>(false, x, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, nullptr, N, H, W, st);
-    if (C == 32) return launch_fused<32>(false, x, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, nullptr, N, H, W, st);
-    if (C == 64) return launch_fused<64>(false, x, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, nullptr, N, H, W, st);
-    return fail_arg(MSTG_E_UNSUPPORTED, "window_attn_fwd: fused kernel exists for C = 16, 32 and 64 (use the qkv/core/proj chain otherwise)");
+    return attn_fused("window_attn_fwd", false, false, x, nullptr, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, NO_DST, nullptr, N, H, W, C,
+                      nullptr, 0, stream);
 }
 
 extern "C" int mstg_window_attn_norm_fwd(const float* x_raw, const float* in_stats, const float* wqkv, const float* bqkv,
                                          const float* wproj, const float* bproj, float* y, int N, int H, int W, int C, void* stream) {
-    if (int rc = attn_check(N, H, W, C)) return rc;
-    if (!x_raw || !in_stats || !wqkv || !bqkv || !wproj || !bproj || !y) return fail_arg(MSTG_E_BADARG, "window_attn_norm_fwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (C == 16) return launch_fused<16>(false, x_raw, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, nullptr, N, H, W, st, in_stats);
-    if (C == 32) return launch_fused<32>(false, x_raw, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, nullptr, N, H, W, st, in_stats);
-    if (C == 64) return launch_fused<64>(false, x_raw, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, nullptr, N, H, W, st, in_stats);
-    return fail_arg(MSTG_E_UNSUPPORTED, "window_attn_norm_fwd: fused kernel exists for C = 16, 32 and 64");
+    return attn_fused("window_attn_norm_fwd", false, true, x_raw, in_stats, wqkv, bqkv, wproj, bproj, nullptr, y, nullptr, NO_DST, nullptr, N,
+                      H, W, C, nullptr, 0, stream);
 }
 
 extern "C" int mstg_window_attn_norm_sums_split(void) { return NSUM_SPLIT; }
 
 extern "C" size_t mstg_window_attn_norm_bwd_workspace_bytes(int N, int H, int W, int C) {
-    if (N <= 0 || H <= 0 || W <= 0 || !(C == 16 || C == 32 || C == 64)) return 0;
-    const size_t nb = (size_t)fused_blocks(N, H, W);
-    return (nb * (4 * C * C + 4 * C) + (size_t)N * ((H / 4) * (W / 4) / norm_run_len(N, H, W, C)) * 2 * C) * sizeof(float);
+    return fused_ws_bytes(attn_fused_route(true, C, true), N, H, W, true);
+}
+extern "C" size_t mstg_window_attn_bwd_workspace_bytes(int N, int H, int W, int C) {
+    return fused_ws_bytes(attn_fused_route(true, C, false), N, H, W, false);
 }
 
 extern "C" int mstg_window_attn_norm_bwd(const float* x_raw, const float* in_stats, const float* wqkv, const float* bqkv,
                                          const float* wproj, const float* bproj, const float* dy, float* dz, float* dparams,
                                          float* norm_sums, int N, int H, int W, int C, void* workspace, size_t workspace_bytes,
                                          void* stream) {
-    if (int rc = attn_check(N, H, W, C)) return rc;
-    if (!x_raw || !in_stats || !wqkv || !bqkv || !wproj || !bproj || !dy || !dz || (!dparams && !t_attn_dst.p[0]) || !norm_sums || !workspace)
-        return fail_arg(MSTG_E_BADARG, "window_attn_norm_bwd: null pointer");
-    if (!(C == 16 || C == 32 || C == 64)) return fail_arg(MSTG_E_UNSUPPORTED, "window_attn_norm_bwd: fused kernel exists for C = 16, 32 and 64");
-    if (workspace_bytes < mstg_window_attn_norm_bwd_workspace_bytes(N, H, W, C)) return fail_arg(MSTG_E_WORKSPACE, "window_attn_norm_bwd: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    if (C == 16) return launch_fused<16>(true, x_raw, wqkv, bqkv, wproj, bproj, dy, dz, dparams, (float*)workspace, N, H, W, st, in_stats, norm_sums);
-    if (C == 64) return launch_fused<64>(true, x_raw, wqkv, bqkv, wproj, bproj, dy, dz, dparams, (float*)workspace, N, H, W, st, in_stats, norm_sums);
-    return launch_fused<32>(true, x_raw, wqkv, bqkv, wproj, bproj, dy, dz, dparams, (float*)workspace, N, H, W, st, in_stats, norm_sums);
-}
-
-extern "C" size_t mstg_window_attn_bwd_workspace_bytes(int N, int H, int W, int C) {
-    if (N <= 0 || H <= 0 || W <= 0 || !(C == 16 || C == 32 || C == 64)) return 0;
-    return (size_t)fused_blocks(N, H, W) * (4 * C * C + 4 * C) * sizeof(float);
+    return attn_fused("window_attn_norm_bwd", true, true, x_raw, in_stats, wqkv, bqkv, wproj, bproj, dy, dz, dparams, NO_DST, norm_sums, N, H,
+                      W, C, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mstg_window_attn_bwd(const float* x, const float* wqkv, const float* bqkv, const float* wproj, const float* bproj,
                                     const float* dy, float* dx, float* dparams, int N, int H, int W, int C, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    if (int rc = attn_check(N, H, W, C)) return rc;
-    if (!x || !wqkv || !bqkv || !wproj || !bproj || !dy || !dx || (!dparams && !t_attn_dst.p[0]) || !workspace)
-        return fail_arg(MSTG_E_BADARG, "window_attn_bwd: null pointer");
-    if (!(C == 16 || C == 32 || C == 64)) return fail_arg(MSTG_E_UNSUPPORTED, "window_attn_bwd: fused kernel exists for C = 16, 32 and 64");
-    if (workspace_bytes < mstg_window_attn_bwd_workspace_bytes(N, H, W, C)) return fail_arg(MSTG_E_WORKSPACE, "window_attn_bwd: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    if (C == 16) return launch_fused<16>(true, x, wqkv, bqkv, wproj, bproj, dy, dx, dparams, (float*)workspace, N, H, W, st);
-    if (C == 64) return launch_fused<64>(true, x, wqkv, bqkv, wproj, bproj, dy, dx, dparams, (float*)workspace, N, H, W, st);
-    return launch_fused<32>(true, x, wqkv, bqkv, wproj, bproj, dy, dx, dparams, (float*)workspace, N, H, W, st);
+    return attn_fused("window_attn_bwd", true, false, x, nullptr, wqkv, bqkv, wproj, bproj, dy, dx, dparams, NO_DST, nullptr, N, H, W, C,
+                      workspace, workspace_bytes, stream);
 }
 
 // ---- the same two backward entry points with the reduced parameter gradients written (or added) straight into four tensors ----------
-namespace {
-struct AttnDstScope {
-    AttnDstScope(float* a, float* b, float* c, float* d, int acc) { t_attn_dst = AttnGradDst{{a, b, c, d}, acc}; }
-    ~AttnDstScope() { t_attn_dst = AttnGradDst{{nullptr, nullptr, nullptr, nullptr}, 0}; }
-};
-}  // namespace
 extern "C" int mstg_window_attn_bwd_direct(const float* x, const float* wqkv, const float* bqkv, const float* wproj, const float* bproj,
                                            const float* dy, float* dx, float* dwqkv, float* dbqkv, float* dwproj, float* dbproj,
                                            int accumulate, int N, int H, int W, int C, void* workspace, size_t workspace_bytes, void* stream) {
     if (!dwqkv || !dbqkv || !dwproj || !dbproj) return fail_arg(MSTG_E_BADARG, "window_attn_bwd_direct: null gradient pointer");
-    AttnDstScope scope(dwqkv, dwproj, dbqkv, dbproj, accumulate);
-    return mstg_window_attn_bwd(x, wqkv, bqkv, wproj, bproj, dy, dx, nullptr, N, H, W, C, workspace, workspace_bytes, stream);
+    return attn_fused("window_attn_bwd", true, false, x, nullptr, wqkv, bqkv, wproj, bproj, dy, dx, nullptr,
+                      AttnGradDst{{dwqkv, dwproj, dbqkv, dbproj}, accumulate}, nullptr, N, H, W, C, workspace, workspace_bytes, stream);
 }
 extern "C" int mstg_window_attn_norm_bwd_direct(const float* x_raw, const float* in_stats, const float* wqkv, const float* bqkv,
                                                 const float* wproj, const float* bproj, const float* dy, float* dz, float* dwqkv,
                                                 float* dbqkv, float* dwproj, float* dbproj, int accumulate, float* norm_sums, int N, int H,
                                                 int W, int C, void* workspace, size_t workspace_bytes, void* stream) {
     if (!dwqkv || !dbqkv || !dwproj || !dbproj) return fail_arg(MSTG_E_BADARG, "window_attn_norm_bwd_direct: null gradient pointer");
-    AttnDstScope scope(dwqkv, dwproj, dbqkv, dbproj, accumulate);
-    return mstg_window_attn_norm_bwd(x_raw, in_stats, wqkv, bqkv, wproj, bproj, dy, dz, nullptr, norm_sums, N, H, W, C, workspace,
-                                     workspace_bytes, stream);
+    return attn_fused("window_attn_norm_bwd", true, true, x_raw, in_stats, wqkv, bqkv, wproj, bproj, dy, dz, nullptr,
+                      AttnGradDst{{dwqkv, dwproj, dbqkv, dbproj}, accumulate}, norm_sums, N, H, W, C, workspace, workspace_bytes, stream);
 }
+

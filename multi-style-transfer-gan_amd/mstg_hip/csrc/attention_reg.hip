@@ -24,6 +24,7 @@
 // gradients stay in MFMA accumulators across all windows of a wave; the four waves of a workgroup add their slabs in LDS in a
 // fixed order, so the second-stage reduce reads 1/16 of what the one-wave kernels produced.  tools/sim_attn_layout.py is the
 // lane-level model this data flow was checked with (its xg_sum is col4_sum of lanes.h, its row sums row16_sum).
+#include "attn_route.h"
 #include "lanes.h"
 #include <stdlib.h>
 
@@ -1217,32 +1218,28 @@ __global__ __launch_bounds__(256, 1) void attn_big_bwd_kernel(const float* __res
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-// C = 32 through the C = 64 code path (test switch: the two implementations of one chain check each other)
-static bool big32() {
-    const char* e = env_get(ENV_ATTN_BIG32);
-    return e && e[0] == '1';
-}
-static bool use_big(int C) { return C == 64 || (C == 32 && big32()); }
-
-// waves per workgroup / workgroups per CU of the backward
+// waves per workgroup / workgroups per CU of the attn_reg backward
 constexpr int bwd_waves(int C) { return C == 16 ? 4 : 8; }
 constexpr int bwd_wgs_per_cu(int C) { return C == 16 ? 4 : 1; }
-// most workgroups the backward uses (= slabs in its workspace)
-int attn_reg_bwd_blocks(int C) { return use_big(C) ? cu_count() : cu_count() * bwd_wgs_per_cu(C); }
-int attn_reg_bwd_waves(int C) { return use_big(C) ? 4 : bwd_waves(C); }
 
-template <int C>
-static int reg_fwd(const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* bp, float* y,
-                   int N, int H, int W, hipStream_t st) {
-    const int nwin = N * (H / 4) * (W / 4);
-    int nb = cu_count() * fwd_waves_per_simd<C>();
-    if (nb * 4 > nwin) nb = cdiv(nwin, 4);
-    if (in_stats)
-        MSTG_LAUNCH((attn_reg_fwd_kernel<C, true>), dim3(nb), dim3(256), 0, st, x, wqkv, bqkv, wp, bp, y, N, H, W, in_stats);
-    else
-        MSTG_LAUNCH((attn_reg_fwd_kernel<C, false>), dim3(nb), dim3(256), 0, st, x, wqkv, bqkv, wp, bp, y, N, H, W, in_stats);
-    MSTG_CHECK_LAUNCH("attn_reg_fwd_kernel");
-    return MSTG_OK;
+// The one place that decides which kernel a fused pass runs (attn_route.h).  MSTG_ATTN_REG=0: the LDS-tile kernels of attention.hip
+// (C = 64 exists only as the register-chain kernel); MSTG_ATTN_BIG32=1: C = 32 through the C = 64 code path (test switch: the two
+// implementations of one chain check each other).  The backward's run length (attention.hip: norm_run_len) follows the
+// attention_reg.hip figures under either value of MSTG_ATTN_REG.
+AttnFusedRoute attn_fused_route(bool bwd, int C, bool norm) {
+    AttnFusedRoute r{};
+    if (!(C == 16 || C == 32 || C == 64)) return r;
+    const char *er = env_get(ENV_ATTN_REG), *eb = env_get(ENV_ATTN_BIG32);
+    const bool big = C == 64 || (C == 32 && eb && eb[0] == '1');
+    r.kind = er && er[0] == '0' && C <= 32 ? AF_FUSED : big ? AF_BIG : AF_REG;
+    r.C = C;
+    r.bwd_waves = big ? 4 : bwd_waves(C);
+    r.bwd_wgs_per_cu = big ? 1 : bwd_wgs_per_cu(C);
+    const int n = snprintf(r.name, sizeof(r.name), "attn_%s_%s_kernel<%d, %s", r.kind == AF_FUSED ? "fused" : big ? "big" : "reg",
+                           bwd ? "bwd" : "fwd", C, norm ? "true" : "false");
+    if (r.kind == AF_REG && bwd) snprintf(r.name + n, sizeof(r.name) - n, ", %d>", r.bwd_waves);  // <C, NORM, WAVES>
+    else snprintf(r.name + n, sizeof(r.name) - n, ">");
+    return r;
 }
 
 template <int C>
@@ -1270,25 +1267,27 @@ static int set_lds(K kern, size_t lds, const char* what) {
     return e == hipSuccess ? MSTG_OK : fail_launch(e, what);
 }
 
-template <int C>
-static int big_fwd(const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* bp, float* y,
+// forward of attn_reg (filters from L2, no dynamic LDS) and of attn_big (BIG: filters in LDS)
+template <int C, bool BIG>
+static int reg_fwd(const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* bp, float* y,
                    int N, int H, int W, hipStream_t st) {
-    typedef BigLds<C> S;
-    const size_t lds = (size_t)S::FWD_FLOATS * sizeof(float);
+    typedef void (*kern_t)(const float*, const float*, const float*, const float*, const float*, float*, int, int, int, const float*);
+    kern_t kn, kp;  // with / without the norm on load
+    size_t lds = 0;
+    if constexpr (BIG) kn = attn_big_fwd_kernel<C, true>, kp = attn_big_fwd_kernel<C, false>, lds = (size_t)BigLds<C>::FWD_FLOATS * sizeof(float);
+    else kn = attn_reg_fwd_kernel<C, true>, kp = attn_reg_fwd_kernel<C, false>;
     const int nwin = N * (H / 4) * (W / 4);
-    int nb = cu_count() * 2;
+    int nb = cu_count() * (BIG ? 2 : fwd_waves_per_simd<C>());
     if (nb * 4 > nwin) nb = cdiv(nwin, 4);
-    static bool ready = false;
+    static bool ready = !BIG;
     if (!ready) {
-        if (int rc = set_lds(attn_big_fwd_kernel<C, true>, lds, "hipFuncSetAttribute(attn_big_fwd<norm>)")) return rc;
-        if (int rc = set_lds(attn_big_fwd_kernel<C, false>, lds, "hipFuncSetAttribute(attn_big_fwd)")) return rc;
+        if (int rc = set_lds(kn, lds, "hipFuncSetAttribute(attn_big_fwd<norm>)")) return rc;
+        if (int rc = set_lds(kp, lds, "hipFuncSetAttribute(attn_big_fwd)")) return rc;
         ready = true;
     }
-    if (in_stats)
-        MSTG_LAUNCH((attn_big_fwd_kernel<C, true>), dim3(nb), dim3(256), lds, st, x, wqkv, bqkv, wp, bp, y, N, H, W, in_stats);
-    else
-        MSTG_LAUNCH((attn_big_fwd_kernel<C, false>), dim3(nb), dim3(256), lds, st, x, wqkv, bqkv, wp, bp, y, N, H, W, in_stats);
-    MSTG_CHECK_LAUNCH("attn_big_fwd_kernel");
+    const kern_t kern = in_stats ? kn : kp;
+    MSTG_LAUNCH(kern, dim3(nb), dim3(256), lds, st, x, wqkv, bqkv, wp, bp, y, N, H, W, in_stats);
+    MSTG_CHECK_LAUNCH(BIG ? "attn_big_fwd_kernel" : "attn_reg_fwd_kernel");
     return MSTG_OK;
 }
 
@@ -1311,18 +1310,20 @@ static int big_bwd(const float* x, const float* in_stats, const float* wqkv, con
     return MSTG_OK;
 }
 
-int attn_reg_fwd(int C, const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* bp,
-                 float* y, int N, int H, int W, hipStream_t st) {
-    if (C == 64) return big_fwd<64>(x, in_stats, wqkv, bqkv, wp, bp, y, N, H, W, st);
-    if (C == 32 && big32()) return big_fwd<32>(x, in_stats, wqkv, bqkv, wp, bp, y, N, H, W, st);
-    return C == 16 ? reg_fwd<16>(x, in_stats, wqkv, bqkv, wp, bp, y, N, H, W, st) : reg_fwd<32>(x, in_stats, wqkv, bqkv, wp, bp, y, N, H, W, st);
+int attn_reg_fwd(const AttnFusedRoute& r, const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp,
+                 const float* bp, float* y, int N, int H, int W, hipStream_t st) {
+    int rc = MSTG_OK;
+    if (r.kind == AF_BIG) for_width<32, 64>(r.C, [&](auto c) { rc = reg_fwd<c(), true>(x, in_stats, wqkv, bqkv, wp, bp, y, N, H, W, st); });
+    else for_width<16, 32>(r.C, [&](auto c) { rc = reg_fwd<c(), false>(x, in_stats, wqkv, bqkv, wp, bp, y, N, H, W, st); });
+    return rc;
 }
-int attn_reg_bwd(int C, const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp, const float* dy,
-                 float* dx, float* partial, float* nsum, int kblk, int nblocks, int N, int H, int W, hipStream_t st) {
-    if (C == 64) return big_bwd<64>(x, in_stats, wqkv, bqkv, wp, dy, dx, partial, nsum, kblk, nblocks, N, H, W, st);
-    if (C == 32 && big32()) return big_bwd<32>(x, in_stats, wqkv, bqkv, wp, dy, dx, partial, nsum, kblk, nblocks, N, H, W, st);
-    return C == 16 ? reg_bwd<16>(x, in_stats, wqkv, bqkv, wp, dy, dx, partial, nsum, kblk, nblocks, N, H, W, st)
-                   : reg_bwd<32>(x, in_stats, wqkv, bqkv, wp, dy, dx, partial, nsum, kblk, nblocks, N, H, W, st);
+int attn_reg_bwd(const AttnFusedRoute& r, const float* x, const float* in_stats, const float* wqkv, const float* bqkv, const float* wp,
+                 const float* dy, float* dx, float* partial, float* nsum, int kblk, int nblocks, int N, int H, int W, hipStream_t st) {
+    int rc = MSTG_OK;
+    if (r.kind == AF_BIG)
+        for_width<32, 64>(r.C, [&](auto c) { rc = big_bwd<c()>(x, in_stats, wqkv, bqkv, wp, dy, dx, partial, nsum, kblk, nblocks, N, H, W, st); });
+    else for_width<16, 32>(r.C, [&](auto c) { rc = reg_bwd<c()>(x, in_stats, wqkv, bqkv, wp, dy, dx, partial, nsum, kblk, nblocks, N, H, W, st); });
+    return rc;
 }
 
 }  // namespace mstg

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "mstg_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -198,6 +200,14 @@ __device__ __forceinline__ void stage_window_c4(const float* __restrict__ img, f
             }
         }
     }
+}
+
+// Runtime width -> template argument: calls f(std::integral_constant<int, W>) for the W of the list that equals w (a launcher is
+// then instantiated for exactly the listed widths); false when w is not in the list.
+//   for_width<16, 32, 64>(CH, [&](auto w) { rc = launch<w()>(...); })
+template <int... Ws, typename F>
+inline bool for_width(int w, F&& f) {
+    return ((w == Ws && (f(std::integral_constant<int, Ws>{}), true)) || ...);
 }
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -1299,17 +1299,18 @@ extern "C" int mstg_conv2d_dgrad_cached(const mstg_conv_desc* d, const float* dy
     return mstg_conv2d_dgrad(d, dy, w, dx, workspace, workspace_bytes, stream);
 }
 
-// kernel symbol (as rocprofv3 prints it, without namespace/arguments) a forward (0) / dgrad (1) call would launch
+// kernel symbol (as rocprofv3 prints it, without namespace/arguments) a forward (0) / dgrad (1) call would launch; 3 / 4: the same two
+// passes with the statistics / backward-sums epilogue of the persistent kernel
 const char* igemm_kernel_name(const mstg_conv_desc* d, int pass) {
     static thread_local char name[64];
     IGemmArgs a{};
     if (check_desc(d)) return "";
-    if (pass == 0) fill_fwd_args(d, a);
+    if (pass == 0 || pass == 3) fill_fwd_args(d, a);
     else if (fill_dgrad_args(d, a)) return "";
     const IGemmRoute r = route_igemm(a);
     const IGemmPlan& p = r.plan;  // the fields the MSTG_DISPATCH table of launch_igemm reads
     if (r.kind == IG_NONE) return "";
-    if (r.kind == IG_P32) return p32_kernel_name(r.p32);
+    if (r.kind == IG_P32) return p32_kernel_name(r.p32, pass == 3 ? 1 : pass == 4 ? 2 : 0);
     if (r.kind == IG_IMG_DGRAD) snprintf(name, sizeof(name), "conv_img_dgrad_kernel<%d>", a.Co);
     else if (p.stream) snprintf(name, sizeof(name), "igemm_stream_kernel<%d, %d, %d, %d>", p.V, p.nfw, p.pf, p.src);
     else if (p.heavy) snprintf(name, sizeof(name), "igemm_heavy_kernel<%d, %d, %d>", p.V, p.nfw, p.src);

@@ -1081,16 +1081,16 @@ int launch_p32(const IGemmArgs& g, const P32Route& r, const float* in_stats, flo
     return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32: no kernel variant");
 }
 
-const char* p32_kernel_name(const P32Route& r) {
+const char* p32_kernel_name(const P32Route& r, int stats) {
     static thread_local char name[64];
     if (r.kind == P32_CO1) return "conv_co1_kernel";
     if (r.kind == P32_IMG) return "conv_p32i_kernel";
     if (r.kind == P32_HEAD) return r.head_th == 16 ? "conv_p32d_kernel<4, 8>" : "conv_p32d_kernel<2, 6>";
     if (r.kind != P32_GENERIC) return "";
-    // as rocprofv3 prints it; the last argument is STATS: 0 here, 1 with the statistics epilogue (mstg_conv2d_fwd_norm with out_stats),
+    // as rocprofv3 prints it; the last argument is STATS: 0 plain, 1 with the statistics epilogue (mstg_conv2d_fwd_norm with out_stats),
     // 2 with the backward-sums epilogue (mstg_conv2d_dgrad_bsums)
-    snprintf(name, sizeof(name), "conv_p32_kernel<%d, %d, %d, %s, 0>", r.plan.TH / 4, r.plan.NF, p32_npf_regs(r.plan),
-             r.plan.wlds ? "true" : "false");
+    snprintf(name, sizeof(name), "conv_p32_kernel<%d, %d, %d, %s, %d>", r.plan.TH / 4, r.plan.NF, p32_npf_regs(r.plan),
+             r.plan.wlds ? "true" : "false", stats);
     return name;
 }
 

@@ -77,7 +77,7 @@ P32Route p32_route(const IGemmArgs& a);
 // dz [aux^ > 0] and of dz [aux^ > 0] aux^.  Either epilogue needs r.stats_bytes of workspace.
 int launch_p32(const IGemmArgs& a, const P32Route& r, const float* in_stats, float* out_stats, const float* aux, const float* aux_stats,
                void* workspace, size_t workspace_bytes, hipStream_t st);
-const char* p32_kernel_name(const P32Route& r);  // the instantiation a launch without an epilogue runs
+const char* p32_kernel_name(const P32Route& r, int stats);  // stats: the generic kernel's STATS argument (0 = no epilogue)
 
 // conv_img.hip: input gradient of the discriminator's image-side layer, Conv2d(3, C, 4, 2, 1) on the NCHW image, on the vector pipe
 bool img_dgrad_eligible(const IGemmArgs& a);

@@ -1142,148 +1142,163 @@ __global__ __launch_bounds__(256) void wgrad_msp_reduce_kernel(const float* __re
     *o = accumulate ? *o + r : r;
 }
 
-template <int CH>
-static bool ms_wgrad_packed() {
-    const char* e = env_get(ENV_MS_WGRAD_PACKED);
-    return CH <= 32 && !(e && e[0] == '0');
-}
+// ---- routing ---------------------------------------------------------------------------------------------------------
+// ms_route is the one place that decides which kernel a pass of the block runs: the launchers, the *_workspace_bytes queries and
+// mstg_msblock_kernel_name read its answer, and nothing else in this file reads a MSTG_MS_* switch.  The answer depends on the
+// arguments and the switches only (cu_count() sizes grids, never a route, a name or a workspace).
+enum MsKind { MS_NONE, MS_FWD, MS_FWD4, MS_FWD4B, MS_DGRAD, MS_WGRAD, MS_WGRADP };
+struct MsRoute {
+    MsKind kind;    // MS_NONE: no fused path at this width
+    bool pf;        // weight gradient: the prefetching kernels (MSTG_MS_WGRAD_PF=0: the synchronous ones, same slabs bit for bit)
+    int S;          // weight gradient: slabs of the unit layout
+    char name[40];  // symbol of the kernel that does the pass's arithmetic, as the per-launch profiler reports it
+    size_t need, query, lds;  // workspace bytes the launch asks for / the query returns (the most of any route); dynamic LDS bytes
+};
+// NG channel chunks x (NG + 24) units x 256 floats, then CH biases: the filter pack of ms_fwd_kernel and one slab of wgrad_ms_kernel
+constexpr size_t ms_unit_floats(int ch) { return (size_t)(ch / 16) * (ch / 16 + 24) * 256 + ch; }
+// the filter pack of ms_fwd4b_kernel: 28 taps x CH/4 rows of pitch ms_fwd4b_ldw, then CH biases
+constexpr int ms_fwd4b_ldw(int ch) { return ch == 16 ? ch : ch + 4; }
+constexpr int ms_fwd4b_pack_floats(int ch) { return 28 * (ch / 4) * ms_fwd4b_ldw(ch) + ch; }
 
 template <int CH>
-static size_t ms_wgrad_plan(int N, int H, int W, int& S, int& tiles_x, int& tiles_y, int& ntiles) {
-    constexpr int NFH = CH / 16, U = NFH + 24, NG = CH / 16, PSTRIDE = NG * U * 256 + CH;  // the unit layout is the larger one
-    tiles_x = cdiv(W, 16);
-    tiles_y = cdiv(H, MS_TH);
-    ntiles = N * tiles_x * tiles_y;
-    S = 768 / NG;
-    if (S > ntiles) S = ntiles;
-    if (S < 1) S = 1;
-    size_t need = (size_t)S * PSTRIDE;
-    if (CH <= 32) {  // the tap-packed kernel: S * NG workgroups, smaller slabs
-        const size_t sp = (size_t)S * NG > (size_t)ntiles ? (size_t)ntiles : (size_t)S * NG;
-        const size_t np = sp * MsPk<(CH <= 32 ? CH : 16)>::PSTRIDE;
-        if (np > need) need = np;
-    }
-    return need * sizeof(float);
-}
-
-template <int CH>
-static int launch_ms_wgrad(const float* x, const float* dy, const MsGradPtrs& out, int accumulate, int N, int H, int W, void* ws,
-                           size_t ws_bytes, hipStream_t st) {
-    constexpr int NFH = CH / 16, U = NFH + 24, NG = CH / 16, PSTRIDE = NG * U * 256 + CH;
-    int S, tiles_x, tiles_y, ntiles;
-    const size_t need = ms_wgrad_plan<CH>(N, H, W, S, tiles_x, tiles_y, ntiles);
-    if (!ws || ws_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "msblock_wgrad: workspace too small");
-    typedef void (*kern_t)(const float*, const float*, float*, int, int, int, int, int, int);
-    // MSTG_MS_WGRAD_PF=0: the synchronous kernels (same slabs, bit for bit)
-    const char* epf = env_get(ENV_MS_WGRAD_PF);
-    const int pf = !(epf && epf[0] == '0');
-    // the synchronous kernels pad a pixel's channels by 4 floats, the default ones by what ms_op_pitch says
-    const size_t lds =
-        (size_t)(pf ? MS_PH * MS_PW * 16 + MS_TH * 16 * ms_op_pitch(CH) : MS_PH * MS_PW * MS_CKP + MS_TH * 16 * (CH + 4)) * sizeof(float);
-    if (ms_wgrad_packed<CH>()) {
-        typedef MsPk<(CH <= 32 ? CH : 16)> P;
-        constexpr int CP = CH <= 32 ? CH : 16;
-        const size_t ldsp = (size_t)(MS_TH * 16 * (pf ? ms_op_pitch(CH) : CH + 4) + MS_PH * MS_PW * P::LDY) * sizeof(float);
-        const kern_t kern = pf ? &wgrad_msp_kernel<CP> : &wgrad_msp_sync_kernel<CP>;
-        static bool attr_set_p[2] = {false, false};
-        if (!attr_set_p[pf]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(wgrad_msp)");
-            attr_set_p[pf] = true;
+static MsRoute ms_route_width(int pass, int N, int H, int W, bool bias_aligned) {
+    constexpr int CP = CH <= 32 ? CH : 16, NG = CH / 16;  // CP: the 4x4x1 forward and the tap-packed weight gradient exist up to 32 channels
+    constexpr size_t TILE = (size_t)MS_PH * MS_PW * MS_CKP * sizeof(float);
+    MsRoute r{};
+    const char* stem;
+    if (pass == 0) {
+        // MSTG_MS_FWD4: unset / 3 = the branch-per-wave 4x4x1 kernel at CH = 16 and 32; 1 = the pixel-per-wave 4x4x1 kernel at CH = 16
+        // (round 2); 2 = that kernel at CH = 32 too; 0 = the 16-row-tile kernel everywhere.  Both 4x4x1 kernels load the biases as
+        // 16-byte vectors and work on 16-row tiles
+        const char* e = env_get(ENV_MS_FWD4);
+        const bool use4b = CH <= 32 && (!e || e[0] == '3');
+        const bool use4 = !use4b && ((CH == 16 && !(e && e[0] == '0')) || (CH == 32 && e && e[0] == '2'));
+        r.kind = !((use4 || use4b) && bias_aligned && H >= 16) ? MS_FWD : use4b ? MS_FWD4B : MS_FWD4;
+        r.query = ms_unit_floats(CH) * sizeof(float);
+        if (r.kind == MS_FWD) stem = "ms_fwd_kernel", r.need = r.query, r.lds = TILE;
+        else if (r.kind == MS_FWD4B)
+            stem = "ms_fwd4b_kernel", r.need = ms_fwd4b_pack_floats(CP) * sizeof(float),
+            r.lds = (size_t)(M4_PH * M4B_ROW + 28 * (CP / 4) * ms_fwd4b_ldw(CP)) * sizeof(float);
+        else stem = "ms_fwd4_kernel", r.lds = (size_t)(M4_PH * MS_PW * MS_CKP + 28 * (CP / 4) * CP) * sizeof(float);  // (packs nothing)
+    } else if (pass == 1) {
+        r.kind = MS_DGRAD, stem = "ms_dgrad_kernel", r.lds = TILE;
+        r.need = r.query = (size_t)ms_dg_quads_before<CH>(NG) * NG * 256 * sizeof(float);
+    } else {
+        const char *ep = env_get(ENV_MS_WGRAD_PACKED), *epf = env_get(ENV_MS_WGRAD_PF);
+        r.kind = CH <= 32 && !(ep && ep[0] == '0') ? MS_WGRADP : MS_WGRAD;
+        r.pf = !(epf && epf[0] == '0');
+        const int ntiles = N * cdiv(W, 16) * cdiv(H, MS_TH);
+        r.S = ntiles < 1 ? 1 : ntiles < 768 / NG ? ntiles : 768 / NG;
+        size_t slabs = r.S * ms_unit_floats(CH);
+        if (CH <= 32) {  // the tap-packed kernel: S * NG workgroups, smaller slabs; the workspace serves either layout
+            const size_t sp = (size_t)(r.S * NG > ntiles ? ntiles : r.S * NG) * MsPk<CP>::PSTRIDE;
+            if (sp > slabs) slabs = sp;
         }
+        r.need = r.query = slabs * sizeof(float);
+        // the synchronous kernels pad a pixel's channels by 4 floats, the default ones by what ms_op_pitch says
+        const int xrow = MS_TH * 16 * (r.pf ? ms_op_pitch(CH) : CH + 4);
+        if (r.kind == MS_WGRADP) stem = r.pf ? "wgrad_msp_kernel" : "wgrad_msp_sync_kernel", r.lds = xrow + MS_PH * MS_PW * MsPk<CP>::LDY;
+        else stem = r.pf ? "wgrad_ms_kernel" : "wgrad_ms_sync_kernel", r.lds = xrow + MS_PH * MS_PW * (r.pf ? 16 : MS_CKP);
+        r.lds *= sizeof(float);
+    }
+    snprintf(r.name, sizeof(r.name), "%s<%d>", stem, CH);
+    return r;
+}
+
+static MsRoute ms_route(int pass, int N, int H, int W, int CH, bool bias_aligned) {
+    MsRoute r{};
+    for_width<16, 32, 64>(CH, [&](auto ch) { r = ms_route_width<ch()>(pass, N, H, W, bias_aligned); });
+    return r;
+}
+
+template <int CH>
+static int launch_ms_wgrad(const MsRoute& r, const float* x, const float* dy, const MsGradPtrs& out, int accumulate, int N, int H, int W,
+                           void* ws, size_t ws_bytes, hipStream_t st) {
+    constexpr int CP = CH <= 32 ? CH : 16, NG = CH / 16;
+    if (!ws || ws_bytes < r.need) return fail_arg(MSTG_E_WORKSPACE, "msblock_wgrad: workspace too small");
+    const int tiles_x = cdiv(W, 16), tiles_y = cdiv(H, MS_TH), ntiles = N * tiles_x * tiles_y, S = r.S;
+    typedef void (*kern_t)(const float*, const float*, float*, int, int, int, int, int, int);
+    const bool packed = r.kind == MS_WGRADP;
+    const kern_t kern = packed ? (r.pf ? &wgrad_msp_kernel<CP> : &wgrad_msp_sync_kernel<CP>) : (r.pf ? &wgrad_ms_kernel<CH> : &wgrad_ms_sync_kernel<CH>);
+    static bool attr_set[2][2] = {};
+    if (!attr_set[packed][r.pf]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return fail_launch(e, packed ? "hipFuncSetAttribute(wgrad_msp)" : "hipFuncSetAttribute(wgrad_ms)");
+        attr_set[packed][r.pf] = true;
+    }
+    if (packed) {
         const int Sp = S * NG > ntiles ? ntiles : S * NG;  // one workgroup covers every input-channel chunk: keep the workgroup count
-        MSTG_LAUNCH(kern, dim3(Sp, 1, 1), dim3(256), ldsp, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
+        MSTG_LAUNCH(kern, dim3(Sp, 1, 1), dim3(256), r.lds, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
         MSTG_CHECK_LAUNCH("wgrad_msp_kernel");
-        MSTG_LAUNCH((wgrad_msp_reduce_kernel<CP>), dim3(cdiv(P::PSTRIDE, 16)), dim3(256), 0, st, (const float*)ws, out, Sp, accumulate);
+        MSTG_LAUNCH((wgrad_msp_reduce_kernel<CP>), dim3(cdiv(MsPk<CP>::PSTRIDE, 16)), dim3(256), 0, st, (const float*)ws, out, Sp, accumulate);
         MSTG_CHECK_LAUNCH("wgrad_msp_reduce_kernel");
         return MSTG_OK;
     }
-    const kern_t kern = pf ? &wgrad_ms_kernel<CH> : &wgrad_ms_sync_kernel<CH>;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[pf]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(wgrad_ms)");
-        attr_set[pf] = true;
-    }
-    MSTG_LAUNCH(kern, dim3(S, NG, 1), dim3(256), lds, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
+    MSTG_LAUNCH(kern, dim3(S, NG, 1), dim3(256), r.lds, st, x, dy, (float*)ws, N, H, W, tiles_x, tiles_y, ntiles);
     MSTG_CHECK_LAUNCH("wgrad_ms_kernel");
-    MSTG_LAUNCH((wgrad_ms_reduce_kernel<CH>), dim3(cdiv(PSTRIDE, 16)), dim3(256), 0, st, (const float*)ws, out, S, accumulate);
+    MSTG_LAUNCH((wgrad_ms_reduce_kernel<CH>), dim3(cdiv((int)ms_unit_floats(CH), 16)), dim3(256), 0, st, (const float*)ws, out, S, accumulate);
     MSTG_CHECK_LAUNCH("wgrad_ms_reduce_kernel");
     return MSTG_OK;
 }
 
 template <int CH>
-static int launch_ms_fwd(const float* x, const MsParamPtrs& prm, float* y, int N, int H, int W, void* ws, size_t ws_bytes, hipStream_t st) {
-    typedef MsUnits<CH> G;
-    {
-        const char* e = env_get(ENV_MS_FWD4);
-        bool aligned = true;
-        for (int k = 0; k < 4; ++k) aligned = aligned && (reinterpret_cast<uintptr_t>(prm.b[k]) & 15) == 0;
-        // MSTG_MS_FWD4: unset / 3 = the branch-per-wave 4x4x1 kernel at CH = 16 and 32; 1 = the pixel-per-wave 4x4x1 kernel at CH = 16
-        // (round 2); 2 = that kernel at CH = 32 too; 0 = the 16-row-tile kernel everywhere
-        const bool use4b = CH <= 32 && (!e || e[0] == '3');
-        const bool use4 = !use4b && ((CH == 16 && !(e && e[0] == '0')) || (CH == 32 && e && e[0] == '2'));
-        if ((use4 || use4b) && aligned && H >= 16) {
-            constexpr int C4K = (CH <= 32 ? CH : 16);
-            const int tiles_x = cdiv(W, 16), tiles_y = cdiv(H, M4_TH);
-            constexpr int LDW4B = C4K == 16 ? C4K : C4K + 4;
-            const size_t lds = use4b ? (size_t)(M4_PH * M4B_ROW + 28 * (C4K / 4) * LDW4B) * sizeof(float)
-                                     : (size_t)(M4_PH * MS_PW * MS_CKP + 28 * (C4K / 4) * C4K) * sizeof(float);
-            static bool attr4 = false;
-            if (!attr4) {
-                hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(&ms_fwd4_kernel<C4K>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (er == hipSuccess)
-                    er = hipFuncSetAttribute(reinterpret_cast<const void*>(&ms_fwd4b_kernel<C4K>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             160 * 1024);
-                if (er != hipSuccess) return fail_launch(er, "hipFuncSetAttribute(ms_fwd4)");
-                attr4 = true;
-            }
-            if (use4b) {
-                constexpr int PACKED = 28 * (C4K / 4) * LDW4B + C4K;
-                if (!ws || ws_bytes < (size_t)PACKED * sizeof(float)) return fail_arg(MSTG_E_WORKSPACE, "msblock_fwd: workspace too small");
-                MSTG_PACK_LAUNCH((ms_pack_fwd4b_kernel<C4K>), dim3(cdiv(PACKED, 256)), dim3(256), 0, st, prm, (float*)ws);
-                MSTG_CHECK_LAUNCH("ms_pack_fwd4b_kernel");
-                const int ntiles = N * tiles_x * tiles_y, slots = (C4K == 16 ? 3 : 2) * cu_count();  // workgroups a CU's LDS holds
-                MSTG_LAUNCH((ms_fwd4b_kernel<C4K>), dim3(ntiles < slots ? ntiles : slots), dim3(256), lds, st, x, (const float*)ws, y, N, H, W,
-                            tiles_x, tiles_y, ntiles);
-            } else MSTG_LAUNCH((ms_fwd4_kernel<C4K>), dim3(N * tiles_x * tiles_y), dim3(256), lds, st, x, prm, y, N, H, W, tiles_x, tiles_y);
-            MSTG_CHECK_LAUNCH("ms_fwd4_kernel");
-            return MSTG_OK;
+static int launch_ms_fwd(const MsRoute& r, const float* x, const MsParamPtrs& prm, float* y, int N, int H, int W, void* ws, size_t ws_bytes,
+                         hipStream_t st) {
+    const int tiles_x = cdiv(W, 16), tiles_y = cdiv(H, r.kind == MS_FWD ? MS_TH : M4_TH), ntiles = N * tiles_x * tiles_y;
+    if (r.kind != MS_FWD) {
+        constexpr int C4K = (CH <= 32 ? CH : 16);
+        static bool attr4 = false;
+        if (!attr4) {
+            hipError_t er = hipFuncSetAttribute(reinterpret_cast<const void*>(&ms_fwd4_kernel<C4K>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (er == hipSuccess)
+                er = hipFuncSetAttribute(reinterpret_cast<const void*>(&ms_fwd4b_kernel<C4K>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         160 * 1024);
+            if (er != hipSuccess) return fail_launch(er, "hipFuncSetAttribute(ms_fwd4)");
+            attr4 = true;
         }
+        if (r.kind == MS_FWD4B) {
+            if (!ws || ws_bytes < r.need) return fail_arg(MSTG_E_WORKSPACE, "msblock_fwd: workspace too small");
+            MSTG_PACK_LAUNCH((ms_pack_fwd4b_kernel<C4K>), dim3(cdiv(ms_fwd4b_pack_floats(C4K), 256)), dim3(256), 0, st, prm, (float*)ws);
+            MSTG_CHECK_LAUNCH("ms_pack_fwd4b_kernel");
+            const int slots = (C4K == 16 ? 3 : 2) * cu_count();  // workgroups a CU's LDS holds
+            MSTG_LAUNCH((ms_fwd4b_kernel<C4K>), dim3(ntiles < slots ? ntiles : slots), dim3(256), r.lds, st, x, (const float*)ws, y, N, H, W,
+                        tiles_x, tiles_y, ntiles);
+        } else MSTG_LAUNCH((ms_fwd4_kernel<C4K>), dim3(ntiles), dim3(256), r.lds, st, x, prm, y, N, H, W, tiles_x, tiles_y);
+        MSTG_CHECK_LAUNCH("ms_fwd4_kernel");
+        return MSTG_OK;
     }
-    constexpr int NCH = CH / 16;
-    const size_t need = (size_t)(NCH * G::U * 256 + CH) * sizeof(float);
-    if (!ws || ws_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "msblock_fwd: workspace too small");
-    float* wp = (float*)ws;
-    MSTG_PACK_LAUNCH((ms_pack_fwd_kernel<CH>), dim3(cdiv(NCH * G::U * 256 + CH, 256)), dim3(256), 0, st, prm, wp);
+    if (!ws || ws_bytes < r.need) return fail_arg(MSTG_E_WORKSPACE, "msblock_fwd: workspace too small");
+    MSTG_PACK_LAUNCH((ms_pack_fwd_kernel<CH>), dim3(cdiv((int)ms_unit_floats(CH), 256)), dim3(256), 0, st, prm, (float*)ws);
     MSTG_CHECK_LAUNCH("ms_pack_fwd_kernel");
-    const int tiles_x = cdiv(W, 16), tiles_y = cdiv(H, MS_TH);
-    const size_t lds = (size_t)(MS_PH * MS_PW * MS_CKP) * sizeof(float);
-    MSTG_LAUNCH((ms_fwd_kernel<CH>), dim3(N * tiles_x * tiles_y), dim3(256), lds, st, x, (const float*)wp, y, N, H, W, tiles_x,
-                       tiles_y);
+    MSTG_LAUNCH((ms_fwd_kernel<CH>), dim3(ntiles), dim3(256), r.lds, st, x, (const float*)ws, y, N, H, W, tiles_x, tiles_y);
     MSTG_CHECK_LAUNCH("ms_fwd_kernel");
     return MSTG_OK;
 }
 
 template <int CH>
-static size_t ms_dgrad_ws_floats() {
-    return (size_t)ms_dg_quads_before<CH>(CH / 16) * (CH / 16) * 256;
-}
-
-template <int CH>
-static int launch_ms_dgrad(const float* dy, const MsParamPtrs& prm, const float* dres, float* dx, int N, int H, int W, void* ws,
-                           size_t ws_bytes, hipStream_t st) {
-    const size_t need = ms_dgrad_ws_floats<CH>() * sizeof(float);
-    if (!ws || ws_bytes < need) return fail_arg(MSTG_E_WORKSPACE, "msblock_dgrad: workspace too small");
-    float* wp = (float*)ws;
-    MSTG_PACK_LAUNCH((ms_pack_dgrad_kernel<CH>), dim3(cdiv((int)ms_dgrad_ws_floats<CH>(), 1024)), dim3(256), 0, st, prm, wp);
+static int launch_ms_dgrad(const MsRoute& r, const float* dy, const MsParamPtrs& prm, const float* dres, float* dx, int N, int H, int W,
+                           void* ws, size_t ws_bytes, hipStream_t st) {
+    if (!ws || ws_bytes < r.need) return fail_arg(MSTG_E_WORKSPACE, "msblock_dgrad: workspace too small");
+    MSTG_PACK_LAUNCH((ms_pack_dgrad_kernel<CH>), dim3(cdiv((int)(r.need / sizeof(float)), 1024)), dim3(256), 0, st, prm, (float*)ws);
     MSTG_CHECK_LAUNCH("ms_pack_dgrad_kernel");
     const int tiles_x = cdiv(W, 16), tiles_y = cdiv(H, MS_TH);
-    const size_t lds = (size_t)(MS_PH * MS_PW * MS_CKP) * sizeof(float);
-    MSTG_LAUNCH((ms_dgrad_kernel<CH>), dim3(N * tiles_x * tiles_y), dim3(256), lds, st, dy, (const float*)wp, dres, dx, N, H, W,
-                       tiles_x, tiles_y);
+    MSTG_LAUNCH((ms_dgrad_kernel<CH>), dim3(N * tiles_x * tiles_y), dim3(256), r.lds, st, dy, (const float*)ws, dres, dx, N, H, W, tiles_x,
+                tiles_y);
     MSTG_CHECK_LAUNCH("ms_dgrad_kernel");
+    return MSTG_OK;
+}
+
+// the argument checks the three passes share
+static int ms_fail(int code, const char* entry, const char* what) {
+    snprintf(g_last_error, sizeof(g_last_error), "%s: %s", entry, what);
+    return code;
+}
+static int ms_check(const char* entry, bool null_ptr, int N, int H, int W, int CH) {
+    if (null_ptr) return ms_fail(MSTG_E_BADARG, entry, "null pointer");
+    if (N <= 0 || H <= 0 || W <= 0) return ms_fail(MSTG_E_BADARG, entry, "bad shape");
+    if ((uint64_t)H * W * CH >= (1ull << 30)) return ms_fail(MSTG_E_UNSUPPORTED, entry, "one image must stay below 2^30 elements");
+    if (!mstg_msblock_fused_supported(CH)) return ms_fail(MSTG_E_UNSUPPORTED, entry, "fused path exists for 16, 32 and 64 channels");
     return MSTG_OK;
 }
 
@@ -1291,45 +1306,41 @@ static int launch_ms_dgrad(const float* dy, const MsParamPtrs& prm, const float*
 
 using namespace mstg;
 
-extern "C" size_t mstg_msblock_dgrad_workspace_bytes(int CH) {
-    if (CH == 16) return ms_dgrad_ws_floats<16>() * sizeof(float);
-    if (CH == 32) return ms_dgrad_ws_floats<32>() * sizeof(float);
-    if (CH == 64) return ms_dgrad_ws_floats<64>() * sizeof(float);
-    return 0;
+extern "C" int mstg_msblock_fused_supported(int CH) { return CH == 16 || CH == 32 || CH == 64; }
+
+extern "C" const char* mstg_msblock_kernel_name(int pass, int N, int H, int W, int CH, int bias_aligned) {
+    static thread_local MsRoute r;
+    r = pass < 0 || pass > 2 ? MsRoute{} : ms_route(pass, N, H, W, CH, bias_aligned != 0);
+    return r.name;
+}
+
+extern "C" size_t mstg_msblock_fwd_workspace_bytes(int CH) { return ms_route(0, 1, 1, 1, CH, true).query; }
+extern "C" size_t mstg_msblock_dgrad_workspace_bytes(int CH) { return ms_route(1, 1, 1, 1, CH, true).query; }
+extern "C" size_t mstg_msblock_wgrad_workspace_bytes(int N, int H, int W, int CH) {
+    return N <= 0 || H <= 0 || W <= 0 ? 0 : ms_route(2, N, H, W, CH, true).query;
 }
 
 extern "C" int mstg_msblock_dgrad(const float* dy, const float* w1, const float* w2, const float* w3, const float* w4, const float* dres,
                                   float* dx, int N, int H, int W, int CH, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!dy || !dx || !w1 || !w2 || !w3 || !w4) return fail_arg(MSTG_E_BADARG, "msblock_dgrad: null pointer");
-    if (N <= 0 || H <= 0 || W <= 0) return fail_arg(MSTG_E_BADARG, "msblock_dgrad: bad shape");
-    if ((uint64_t)H * W * CH >= (1ull << 30)) return fail_arg(MSTG_E_UNSUPPORTED, "msblock_dgrad: one image must stay below 2^30 elements");
+    if (int rc = ms_check("msblock_dgrad", !dy || !dx || !w1 || !w2 || !w3 || !w4, N, H, W, CH)) return rc;
     MsParamPtrs prm{{w1, w2, w3, w4}, {nullptr, nullptr, nullptr, nullptr}};
-    hipStream_t st = (hipStream_t)stream;
-    if (CH == 16) return launch_ms_dgrad<16>(dy, prm, dres, dx, N, H, W, workspace, workspace_bytes, st);
-    if (CH == 32) return launch_ms_dgrad<32>(dy, prm, dres, dx, N, H, W, workspace, workspace_bytes, st);
-    if (CH == 64) return launch_ms_dgrad<64>(dy, prm, dres, dx, N, H, W, workspace, workspace_bytes, st);
-    return fail_arg(MSTG_E_UNSUPPORTED, "msblock_dgrad: fused path exists for 16, 32 and 64 channels");
-}
-
-extern "C" int mstg_msblock_fused_supported(int CH) { return CH == 16 || CH == 32 || CH == 64; }
-
-extern "C" size_t mstg_msblock_fwd_workspace_bytes(int CH) {
-    if (!mstg_msblock_fused_supported(CH)) return 0;
-    return (size_t)((CH / 16) * (CH / 16 + 24) * 256 + CH) * sizeof(float);
+    const MsRoute r = ms_route(1, N, H, W, CH, true);
+    int rc = MSTG_OK;
+    for_width<16, 32, 64>(CH, [&](auto ch) { rc = launch_ms_dgrad<ch()>(r, dy, prm, dres, dx, N, H, W, workspace, workspace_bytes, (hipStream_t)stream); });
+    return rc;
 }
 
 extern "C" int mstg_msblock_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                                 const float* b3, const float* w4, const float* b4, float* y, int N, int H, int W, int CH, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    if (!x || !y || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4) return fail_arg(MSTG_E_BADARG, "msblock_fwd: null pointer");
-    if (N <= 0 || H <= 0 || W <= 0) return fail_arg(MSTG_E_BADARG, "msblock_fwd: bad shape");
-    if ((uint64_t)H * W * CH >= (1ull << 30)) return fail_arg(MSTG_E_UNSUPPORTED, "msblock_fwd: one image must stay below 2^30 elements");
+    if (int rc = ms_check("msblock_fwd", !x || !y || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4, N, H, W, CH)) return rc;
     MsParamPtrs prm{{w1, w2, w3, w4}, {b1, b2, b3, b4}};
-    hipStream_t st = (hipStream_t)stream;
-    if (CH == 16) return launch_ms_fwd<16>(x, prm, y, N, H, W, workspace, workspace_bytes, st);
-    if (CH == 32) return launch_ms_fwd<32>(x, prm, y, N, H, W, workspace, workspace_bytes, st);
-    if (CH == 64) return launch_ms_fwd<64>(x, prm, y, N, H, W, workspace, workspace_bytes, st);
-    return fail_arg(MSTG_E_UNSUPPORTED, "msblock_fwd: fused path exists for 16, 32 and 64 channels");
+    bool aligned = true;
+    for (int k = 0; k < 4; ++k) aligned = aligned && (reinterpret_cast<uintptr_t>(prm.b[k]) & 15) == 0;
+    const MsRoute r = ms_route(0, N, H, W, CH, aligned);
+    int rc = MSTG_OK;
+    for_width<16, 32, 64>(CH, [&](auto ch) { rc = launch_ms_fwd<ch()>(r, x, prm, y, N, H, W, workspace, workspace_bytes, (hipStream_t)stream); });
+    return rc;
 }
 
 // the same two entry points for a caller that caches the packed filters (common.h: t_ws_packed)
@@ -1350,25 +1361,13 @@ extern "C" int mstg_msblock_dgrad_cached(const float* dy, const float* w1, const
     return rc;
 }
 
-extern "C" size_t mstg_msblock_wgrad_workspace_bytes(int N, int H, int W, int CH) {
-    int S, tx, ty, nt;
-    if (N <= 0 || H <= 0 || W <= 0) return 0;
-    if (CH == 16) return ms_wgrad_plan<16>(N, H, W, S, tx, ty, nt);
-    if (CH == 32) return ms_wgrad_plan<32>(N, H, W, S, tx, ty, nt);
-    if (CH == 64) return ms_wgrad_plan<64>(N, H, W, S, tx, ty, nt);
-    return 0;
-}
-
 extern "C" int mstg_msblock_wgrad(const float* x, const float* dy, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3,
                                   float* dw4, float* db4, int accumulate, int N, int H, int W, int CH, void* workspace,
                                   size_t workspace_bytes, void* stream) {
-    if (!x || !dy || !dw1 || !db1 || !dw2 || !db2 || !dw3 || !db3 || !dw4 || !db4) return fail_arg(MSTG_E_BADARG, "msblock_wgrad: null pointer");
-    if (N <= 0 || H <= 0 || W <= 0) return fail_arg(MSTG_E_BADARG, "msblock_wgrad: bad shape");
-    if ((uint64_t)H * W * CH >= (1ull << 30)) return fail_arg(MSTG_E_UNSUPPORTED, "msblock_wgrad: one image must stay below 2^30 elements");
+    if (int rc = ms_check("msblock_wgrad", !x || !dy || !dw1 || !db1 || !dw2 || !db2 || !dw3 || !db3 || !dw4 || !db4, N, H, W, CH)) return rc;
     MsGradPtrs out{{dw1, dw2, dw3, dw4}, {db1, db2, db3, db4}};
-    hipStream_t st = (hipStream_t)stream;
-    if (CH == 16) return launch_ms_wgrad<16>(x, dy, out, accumulate, N, H, W, workspace, workspace_bytes, st);
-    if (CH == 32) return launch_ms_wgrad<32>(x, dy, out, accumulate, N, H, W, workspace, workspace_bytes, st);
-    if (CH == 64) return launch_ms_wgrad<64>(x, dy, out, accumulate, N, H, W, workspace, workspace_bytes, st);
-    return fail_arg(MSTG_E_UNSUPPORTED, "msblock_wgrad: fused path exists for 16, 32 and 64 channels");
+    const MsRoute r = ms_route(2, N, H, W, CH, true);
+    int rc = MSTG_OK;
+    for_width<16, 32, 64>(CH, [&](auto ch) { rc = launch_ms_wgrad<ch()>(r, x, dy, out, accumulate, N, H, W, workspace, workspace_bytes, (hipStream_t)stream); });
+    return rc;
 }

@@ -203,6 +203,14 @@ def _kernel_name(d: ConvDesc, which: int) -> str:
     return _lib.load().mstg_conv2d_kernel_name(C.byref(d), which).decode() if KernelTimer.enabled else ""
 
 
+def _ms_kernel_name(which: int, N, H, W, ch) -> str:
+    return _lib.load().mstg_msblock_kernel_name(which, N, H, W, ch, 1).decode() if KernelTimer.enabled else ""
+
+
+def _attn_kernel_name(fused: bool, which: int, Cn, norm=False) -> str:
+    return _lib.load().mstg_window_attn_kernel_name(int(fused), which, Cn, int(norm)).decode() if KernelTimer.enabled else ""
+
+
 # ----------------------------------------------------------------------------------------------------------
 # Filter packs kept between launches
 # ----------------------------------------------------------------------------------------------------------
@@ -309,7 +317,7 @@ def conv_dgrad_bsums_raw(d: ConvDesc, dy, w, dx, x_raw, x_stats, owners=None):
     lib = _lib.load()
     sums = torch.empty((d.N, 1, 2, d.Cin), dtype=torch.float32, device=dy.device)
     ws, packed = _cached_ws(owners, "dgrad_bsums", _dkey(d, 1), lib.mstg_conv2d_dgrad_bsums_workspace_bytes(C.byref(d)), dy.device)
-    _timed(_kernel_name(d, 1), fl, by + 4 * x_raw.numel(), lambda: _lib.check(
+    _timed(_kernel_name(d, 4), fl, by + 4 * x_raw.numel(), lambda: _lib.check(
         lib.mstg_conv2d_dgrad_bsums(C.byref(d), _p(dy), _p(w), _p(dx), _p(x_raw), _p(x_stats), _p(sums), _p(ws), ws.numel() * 4, packed,
                                     _stream()), "mstg_conv2d_dgrad_bsums"), _conv_detail("dgrad+bsums", d))
     return sums
@@ -473,7 +481,7 @@ class ConvStatsFn(torch.autograd.Function):
         d = make_desc(N, H, W, Cin, Ho, Wo, Cout, k, stride, pad, dil, transposed)
         ws, packed = _cached_ws((w, b), "fwd_norm", _dkey(d, 0), lib.mstg_conv2d_fwd_norm_workspace_bytes(C.byref(d)), x.device)
         fl, by = _conv_cost(d)
-        _timed(_kernel_name(d, 0).replace(", 0>", ", 1>"), fl, by, lambda: _lib.check(  # the STATS instantiation
+        _timed(_kernel_name(d, 3), fl, by, lambda: _lib.check(  # the STATS instantiation
             lib.mstg_conv2d_fwd_norm_cached(C.byref(d), _p(x), None, _p(w), _p(b), _p(y), _p(stats), _p(ws), ws.numel() * 4, packed,
                                             _stream()), "mstg_conv2d_fwd_norm"), _conv_detail("fwd", d))
         ctx.cfg, ctx.dims, ctx.has_bias = (k, stride, pad, dil, transposed, 0, 0, ACT_NONE), (N, H, W, Cin, Ho, Wo, Cout), b is not None
@@ -522,7 +530,7 @@ class MSFusionFn(torch.autograd.Function):
         d = make_desc(N, H, W, Cn, Ho, Wo, Cout, k, stride, pad, dil)
         ws2, packed = _cached_ws((w, b), "fwd_norm", _dkey(d, 0), lib.mstg_conv2d_fwd_norm_workspace_bytes(C.byref(d)), cat.device)
         fl, by = _conv_cost(d)
-        _timed(_kernel_name(d, 0).replace(", 0>", ", 1>"), fl, by, lambda: _lib.check(
+        _timed(_kernel_name(d, 3), fl, by, lambda: _lib.check(
             lib.mstg_conv2d_fwd_norm_cached(C.byref(d), _p(cat), _p(stats), _p(w), _p(b), _p(y), _p(ystats), _p(ws2), ws2.numel() * 4,
                                             packed, _stream()), "mstg_conv2d_fwd_norm"), _conv_detail("fwd", d))
         ctx.dims, ctx.has_bias, ctx.prefs, ctx.cfg = (N, H, W, Cn, Cout), b is not None, (w, b), tuple(cfg)
@@ -607,13 +615,13 @@ class MSBranchesFn(torch.autograd.Function):
         y = torch.empty((N, H, W, 4 * c4), dtype=torch.float32, device=x.device)
         lib = _lib.load()
         if os.environ.get("MSTG_MS_UNFUSED", "0") != "1" and bool(lib.mstg_msblock_fused_supported(ch)) and 4 * c4 == ch:
-            # (H >= 16: smaller maps go to another kernel, which packs the filter differently)
-            wsb, packed = _cached_ws(tuple(wb), "ms_fwd", (ch, H >= 16), lib.mstg_msblock_fwd_workspace_bytes(ch), x.device)
+            # the pack's layout belongs to the kernel, and the library chooses the kernel by more than the shape
+            sym = lib.mstg_msblock_kernel_name(0, N, H, W, ch, int(all(b.data_ptr() % 16 == 0 for b in bs)))
+            wsb, packed = _cached_ws(tuple(wb), "ms_fwd", sym, lib.mstg_msblock_fwd_workspace_bytes(ch), x.device)
             wb_ptrs = []
             for j in range(4):
                 wb_ptrs += [_p(ws[j]), _p(bs[j])]
-            fwd4 = ch == 16 and H >= 16 and os.environ.get("MSTG_MS_FWD4", "1") != "0"
-            _timed("ms_fwd4_kernel" if fwd4 else f"ms_fwd_kernel<{ch}>", 2.0 * N * H * W * ch * c4 * 28, 4.0 * (2 * N * H * W * ch),
+            _timed(sym.decode(), 2.0 * N * H * W * ch * c4 * 28, 4.0 * (2 * N * H * W * ch),
                    lambda: _lib.check(lib.mstg_msblock_fwd_cached(_p(x), *wb_ptrs, _p(y), N, H, W, ch, _p(wsb), wsb.numel() * 4, packed,
                                                                   _stream()), "mstg_msblock_fwd"), f"ms-fwd N{N} {H}x{W} ch{ch}")
         else:
@@ -639,8 +647,9 @@ class MSBranchesFn(torch.autograd.Function):
         fused = os.environ.get("MSTG_MS_UNFUSED", "0") != "1" and bool(lib.mstg_msblock_fused_supported(ch)) and 4 * c4 == ch
         grads = []
         if fused and dx is not None:  # dx of all four branches in one pass over dy, written once
-            wsd, packed = _cached_ws(tuple(ctx.prefs[0::2]), "ms_dgrad", (ch,), lib.mstg_msblock_dgrad_workspace_bytes(ch), x.device)
-            _timed(f"ms_dgrad_kernel<{ch}>", 2.0 * N * H * W * ch * c4 * 28, 4.0 * (2 * N * H * W * ch),
+            sym = lib.mstg_msblock_kernel_name(1, N, H, W, ch, 1)
+            wsd, packed = _cached_ws(tuple(ctx.prefs[0::2]), "ms_dgrad", sym, lib.mstg_msblock_dgrad_workspace_bytes(ch), x.device)
+            _timed(sym.decode(), 2.0 * N * H * W * ch * c4 * 28, 4.0 * (2 * N * H * W * ch),
                    lambda: _lib.check(lib.mstg_msblock_dgrad_cached(_p(dy), *[_p(t) for t in ws], _p(dres), _p(dx), N, H, W, ch, _p(wsd),
                                                                     wsd.numel() * 4, packed, _stream()), "mstg_msblock_dgrad"),
                    f"ms-dgrad N{N} {H}x{W} ch{ch}")
@@ -663,8 +672,7 @@ class MSBranchesFn(torch.autograd.Function):
             slots = [_grad_slot(p) for p in ctx.prefs]
             direct = all(t is not None for t in slots)
             outs = slots if direct else grads
-            sym = "wgrad_msp_kernel" if ch <= 32 and os.environ.get("MSTG_MS_WGRAD_PACKED", "1") != "0" else "wgrad_ms_kernel"
-            _timed(f"{sym}<{ch}>", 2.0 * N * H * W * ch * c4 * 28, 4.0 * (2 * N * H * W * ch),
+            _timed(_ms_kernel_name(2, N, H, W, ch), 2.0 * N * H * W * ch * c4 * 28, 4.0 * (2 * N * H * W * ch),
                    lambda: _lib.check(lib.mstg_msblock_wgrad(_p(x), _p(dy), *[_p(t) for t in outs], int(direct), N, H, W, ch, _p(wsb),
                                                              wsb.numel() * 4, _stream()), "mstg_msblock_wgrad"),
                    f"ms-wgrad N{N} {H}x{W} ch{ch}")
@@ -803,15 +811,6 @@ class BatchNormActFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------------------
 # window attention core
 # ----------------------------------------------------------------------------------------------------------
-def _attn_core_symbol(direction, Cn):
-    """Kernel symbol attention.hip launches for this width (for the timing table only)."""
-    if Cn <= 32 or (Cn <= 64 and os.environ.get("MSTG_ATTN_BLK64", "1") == "0"):
-        return f"attn_core_{direction}_kernel<{16 if Cn <= 16 else (32 if Cn <= 32 else 64)}>"
-    if Cn <= 64 or os.environ.get("MSTG_ATTN_BLK4", "1") == "0":
-        return f"attn_core_{direction}_blk_kernel<{64 if Cn <= 64 else (128 if Cn <= 128 else 256)}>"
-    return f"attn_core_{direction}_blk4_kernel<{128 if Cn <= 128 else 256}>"
-
-
 class WindowAttnCoreFn(torch.autograd.Function):
     """o = attn(q^, k^) v per 4x4 window; qkv NHWC (N,H,W,3C) -> o NHWC (N,H,W,C)."""
 
@@ -821,7 +820,7 @@ class WindowAttnCoreFn(torch.autograd.Function):
         N, H, W, C3 = qkv.shape
         Cn = C3 // 3
         o = torch.empty((N, H, W, Cn), dtype=torch.float32, device=qkv.device)
-        _timed(_attn_core_symbol('fwd', Cn), 4 * Cn * Cn * N * H * W, 4 * 4 * Cn * N * H * W, lambda: _lib.check(
+        _timed(_attn_kernel_name(False, 0, Cn), 4 * Cn * Cn * N * H * W, 4 * 4 * Cn * N * H * W, lambda: _lib.check(
             _lib.load().mstg_window_attn_core_fwd(_p(qkv), _p(o), N, H, W, Cn, _stream()), "mstg_window_attn_core_fwd"), detail=f"attn-core N{N} {H}x{W} C{Cn}")
         ctx.save_for_backward(qkv)
         return o
@@ -833,7 +832,7 @@ class WindowAttnCoreFn(torch.autograd.Function):
         N, H, W, C3 = qkv.shape
         dqkv = torch.empty_like(qkv)
         Cn = C3 // 3
-        _timed(_attn_core_symbol('bwd', Cn), 8 * Cn * Cn * N * H * W, 4 * 7 * Cn * N * H * W, lambda: _lib.check(
+        _timed(_attn_kernel_name(False, 1, Cn), 8 * Cn * Cn * N * H * W, 4 * 7 * Cn * N * H * W, lambda: _lib.check(
             _lib.load().mstg_window_attn_core_bwd(_p(qkv), _p(do), _p(dqkv), N, H, W, Cn, _stream()), "mstg_window_attn_core_bwd"), detail=f"attn-core N{N} {H}x{W} C{Cn}")
         return dqkv
 
@@ -874,12 +873,6 @@ def _attn_grad_dst(prefs, like):
     return [torch.empty_like(t) for t in like], False
 
 
-def _attn_fused_symbol(direction, Cn, norm):
-    """Kernel symbol attention_reg.hip launches for this width (for the timing table only)."""
-    stem = "attn_big" if Cn > 32 or (Cn == 32 and os.environ.get("MSTG_ATTN_BIG32") == "1") else "attn_reg"
-    return f"{stem}_{direction}_kernel<{Cn}, {'true' if norm else 'false'}>"
-
-
 class LocalAttentionFusedFn(torch.autograd.Function):
     """Whole LocalAttention (qkv 1x1 conv -> window attention -> proj 1x1 conv) in one kernel per direction, C = 16 / 32 / 64.
     x, y: NHWC (N,H,W,C); wqkv (3C,C,1,1), wproj (C,C,1,1) as stored by the reference."""
@@ -890,7 +883,7 @@ class LocalAttentionFusedFn(torch.autograd.Function):
         wqkv, bqkv, wproj, bproj = (_req(t, "attention parameter") for t in (wqkv, bqkv, wproj, bproj))
         N, H, W, Cn = x.shape
         y = torch.empty_like(x)
-        _timed(_attn_fused_symbol("fwd", Cn, False), 12 * Cn * Cn * N * H * W, 4 * 2 * Cn * N * H * W, lambda: _lib.check(
+        _timed(_attn_kernel_name(True, 0, Cn), 12 * Cn * Cn * N * H * W, 4 * 2 * Cn * N * H * W, lambda: _lib.check(
             _lib.load().mstg_window_attn_fwd(_p(x), _p(wqkv), _p(bqkv), _p(wproj), _p(bproj), _p(y), N, H, W, Cn, _stream()),
             "mstg_window_attn_fwd"))
         ctx.prefs = (wqkv, bqkv, wproj, bproj)
@@ -906,7 +899,7 @@ class LocalAttentionFusedFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         outs, direct = _attn_grad_dst(ctx.prefs, (wqkv, bqkv, wproj, bproj))
         ws = _ws(lib.mstg_window_attn_bwd_workspace_bytes(N, H, W, Cn), x.device)
-        _timed(_attn_fused_symbol("bwd", Cn, False), 24 * Cn * Cn * N * H * W, 4 * 3 * Cn * N * H * W, lambda: _lib.check(
+        _timed(_attn_kernel_name(True, 1, Cn), 24 * Cn * Cn * N * H * W, 4 * 3 * Cn * N * H * W, lambda: _lib.check(
             lib.mstg_window_attn_bwd_direct(_p(x), _p(wqkv), _p(bqkv), _p(wproj), _p(bproj), _p(dy), _p(dx), *[_p(t) for t in outs],
                                             int(direct), N, H, W, Cn, _p(ws), ws.numel() * 4, _stream()), "mstg_window_attn_bwd"))
         return (dx, *((None,) * 4 if direct else outs))
@@ -930,7 +923,7 @@ class NormLocalAttentionFn(torch.autograd.Function):
             _timed("norm_partial_kernel<false>", 0, 4 * x.numel(), lambda: _lib.check(
                 lib.mstg_norm_stats(_p(x), _p(stats), N, H * W, Cn, _p(ws), ws.numel() * 4, _stream()), "mstg_norm_stats"))
         y = torch.empty_like(x)
-        _timed(_attn_fused_symbol("fwd", Cn, True), 12 * Cn * Cn * N * H * W, 4 * 2 * Cn * N * H * W, lambda: _lib.check(
+        _timed(_attn_kernel_name(True, 0, Cn, True), 12 * Cn * Cn * N * H * W, 4 * 2 * Cn * N * H * W, lambda: _lib.check(
             lib.mstg_window_attn_norm_fwd(_p(x), _p(stats), _p(wqkv), _p(bqkv), _p(wproj), _p(bproj), _p(y), N, H, W, Cn, _stream()),
             "mstg_window_attn_norm_fwd"))
         ctx.prefs = (wqkv, bqkv, wproj, bproj)
@@ -948,7 +941,7 @@ class NormLocalAttentionFn(torch.autograd.Function):
         S = lib.mstg_window_attn_norm_sums_split()
         sums = torch.empty((N, S, 2, Cn), dtype=torch.float32, device=x.device)
         ws = _ws(lib.mstg_window_attn_norm_bwd_workspace_bytes(N, H, W, Cn), x.device)
-        _timed(_attn_fused_symbol("bwd", Cn, True), 24 * Cn * Cn * N * H * W, 4 * 3 * Cn * N * H * W, lambda: _lib.check(
+        _timed(_attn_kernel_name(True, 1, Cn, True), 24 * Cn * Cn * N * H * W, 4 * 3 * Cn * N * H * W, lambda: _lib.check(
             lib.mstg_window_attn_norm_bwd_direct(_p(x), _p(stats), _p(wqkv), _p(bqkv), _p(wproj), _p(bproj), _p(dy), _p(dz),
                                                  *[_p(t) for t in outs], int(direct), _p(sums), N, H, W, Cn, _p(ws), ws.numel() * 4,
                                                  _stream()), "mstg_window_attn_norm_bwd"))

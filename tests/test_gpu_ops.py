@@ -360,6 +360,75 @@ def test_kernel_name_is_the_launched_kernel(env, monkeypatch):
     assert not wrong, wrong
 
 
+def _fused_routes():
+    import importlib.util
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("dump_fused_routes", os.path.join(root, "tools", "dump_fused_routes.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    return tool, json.load(open(os.path.join(root, "tests", "golden", "fused_routes.json")))
+
+
+FUSED_ROUTES, FUSED_GOLD = _fused_routes()
+
+
+@pytest.mark.parametrize("setting", FUSED_ROUTES.SETTINGS)
+def test_fused_kernel_name_is_the_launched_kernel(setting, monkeypatch):
+    """mstg_msblock_kernel_name / mstg_window_attn_kernel_name report, for each pass of every case of tools/dump_fused_routes.py, a
+    symbol the pass's call through ops really launches -- ops labels the call with it -- and the call launches exactly the symbols,
+    in order, that the commit before the routing was gathered launched (tests/golden/fused_routes.json): no route moved.  Results
+    are not compared here (the parity tests do that)."""
+    from mstg_hip import ops
+    for kv in setting.split(",") if setting != "default" else []:
+        monkeypatch.setenv(*kv.split("="))
+    ops.refresh_env()
+    try:
+        for case, family, shape in FUSED_ROUTES.cases():
+            want = FUSED_GOLD[setting].get(case, FUSED_GOLD["default"][case])["launches"]
+            got = FUSED_ROUTES.run_case(family, shape)
+            names = FUSED_ROUTES.names(family, shape)
+            if not FUSED_ROUTES.supported(family, shape):
+                assert got == [] and want == [] and set(names) == {""}, (case, names)
+                continue
+            assert [syms for _, syms in got] == want, (case, got)
+            for ps, (label, syms) in enumerate(got):
+                assert label == names[ps] and names[ps] in syms, (case, ps, label, names[ps], syms)
+    finally:
+        monkeypatch.undo()
+        ops.refresh_env()
+
+
+def test_ms_fwd_pack_follows_the_route(monkeypatch):
+    """A MultiScaleBlock that owns its weights keeps the forward's filter pack between calls.  The pack's layout belongs to the
+    kernel the library routes the call to, so a pack written for one route must never reach another: default route, MSTG_MS_FWD4=0,
+    default again on the same parameters, each bit for bit what the same route computes with the pack cache off."""
+    from mstg_hip import ops
+    N, H, W, ch = 1, 16, 16, 16
+    x = rnd((N, H, W, ch), 1).to(DEV)
+    wb = []
+    for j, (k, _, _) in enumerate(ops.MSBranchesFn.GEOM):
+        wb += [torch.nn.Parameter(rnd((ch // 4, ch, k, k), 10 + j, 0.2).to(DEV)), torch.nn.Parameter(rnd((ch // 4,), 20 + j, 0.3).to(DEV))]
+
+    def run(fwd4, cache):
+        monkeypatch.undo()
+        if fwd4 is not None:
+            monkeypatch.setenv("MSTG_MS_FWD4", fwd4)
+        if not cache:
+            monkeypatch.setenv("MSTG_NO_PACK_CACHE", "1")
+        ops.refresh_env()
+        with torch.no_grad():
+            return ops.MSBranchesFn.apply(x, *wb)[0].clone()
+    try:
+        got = [run(fwd4, True) for fwd4 in (None, "0", None)]
+        want = [run(fwd4, False) for fwd4 in (None, "0", None)]
+    finally:
+        monkeypatch.undo()
+        ops.refresh_env()
+    for step, (g, w) in enumerate(zip(got, want)):
+        assert torch.equal(g, w), f"run {step}: the cached pack gave another result than a fresh pack"
+
+
 NORM_CASES = [(2, 16, 24, 8, 1), (1, 64, 64, 16, 1), (3, 7, 9, 32, 2), (2, 4, 4, 64, 2), (1, 128, 128, 16, 1), (2, 2, 2, 64, 2),
               (2, 16, 16, 4, 0), (1, 32, 32, 128, 1),
               # small batches of large maps: more than 32 partial rows per image, added once by the grouped statistics / sums kernels
