@@ -1848,7 +1848,7 @@ def equalize_luma_u8(img_u8: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     out = torch.empty_like(x)
     nbytes = lib.mstg_equalize_luma_workspace_bytes(N, H, W)  # 0 for a bad shape: the call below names what is wrong
-    ws = torch.empty(max(nbytes // 4 + 1, 1), dtype=torch.int32, device=x.device)
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=x.device)  # the query counts whole ints: not a byte of slack
     _lib.check(lib.mstg_equalize_luma_u8(_p(x), N, H, W, _p(out), _p(ws), ws.numel() * 4, _stream()), "mstg_equalize_luma_u8")
     return out[0] if single else out
 

@@ -10,7 +10,7 @@ alignment assumption).  Both alignments run for every case.
 
 Shapes are the smallest of each table that still reach ragged tiles, several images per wave and the fall-back routes; nothing that
 captures a graph is wrapped.  The fp16 files allocate their workspaces with torch.empty, so they count as outputs: ``workspaces``
-is asserted only for the families that go through ops._ws.
+is asserted only for the families that go through ops._ws.  The 8-bit image side has its own file, test_gpu_memory_contract_image.py.
 """
 import types
 
