@@ -115,6 +115,24 @@ int mstg_msblock_dgrad_cached(const float* dy, const float* w1, const float* w2,
                               float* dx, int N, int H, int W, int CH, void* workspace, size_t workspace_bytes, int workspace_packed,
                               void* stream);
 
+/* Grouped launches.  G <= mstg_conv2d_group_max() (4) forwards -- or input gradients -- of ONE descriptor, each with its own source,
+ * destination, filter and bias, as one launch chain: one pack launch for the G filters, one main launch whose grid is G copies of the
+ * single launch's (the persistent kernels split their occupancy-sized grid among the groups).  d describes one group (d->N images);
+ * route, tile shape, pack layout and per-image summation order are the single launch's, so group k's result is bit for bit what
+ * mstg_conv2d_fwd / _dgrad gives for (x[k], w[k], bias[k]).  The pointer tables live on the host; bias: NULL, or G pointers all
+ * null or all non-null.  d->accumulate is not supported.  Workspace: mstg_conv2d_grouped_workspace_bytes(d, G) = G times the
+ * per-group query (rounded up to 16 bytes), never cached.  Taught: igemm_light / igemm_heavy, conv_p32_kernel without an epilogue,
+ * conv_co1_kernel, conv_img_dgrad_kernel and the two pack kernels; every other route (the stream kernel, the 7x7 image stem, the packed
+ * <= 4-channel heads) returns MSTG_E_UNSUPPORTED and launches nothing -- the caller then makes G plain calls.
+ * mstg_conv2d_grouped_kernel_name: the main kernel of pass 0 (forward) / 1 (dgrad) as a profiler prints it, "" where unsupported. */
+int mstg_conv2d_group_max(void);
+size_t mstg_conv2d_grouped_workspace_bytes(const mstg_conv_desc* d, int G);
+int mstg_conv2d_fwd_grouped(const mstg_conv_desc* d, int G, const float* const* x, const float* const* w, const float* const* bias,
+                            float* const* y, void* workspace, size_t workspace_bytes, void* stream);
+int mstg_conv2d_dgrad_grouped(const mstg_conv_desc* d, int G, const float* const* dy, const float* const* w, float* const* dx,
+                              void* workspace, size_t workspace_bytes, void* stream);
+const char* mstg_conv2d_grouped_kernel_name(const mstg_conv_desc* d, int pass);
+
 /* name of the kernel a pass (0 forward, 1 dgrad, 2 wgrad; 3 forward with the statistics epilogue of mstg_conv2d_fwd_norm, 4 dgrad with
  * the backward-sums epilogue of mstg_conv2d_dgrad_bsums) of this layer launches, as a profiler prints it (for reports and pack keys) */
 const char* mstg_conv2d_kernel_name(const mstg_conv_desc* d, int pass);
@@ -165,6 +183,15 @@ int mstg_norm_act_fwd(const float* x, const float* residual /*nullable*/, float*
 int mstg_norm_act_bwd(const float* x, const float* stats, const float* dy, float* dx, int N, int HW, int C, int act,
                       int batch_stats, const float* gamma, const float* beta, float* dgamma, float* dbeta,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* InstanceNorm (batch_stats = 0) over N = G * plan_N images with the plan of a batch of plan_N: the row split per image is a function
+ * of the batch size, so a pass over G groups at once would split every image differently from the G passes it replaces.  These run all
+ * N images with the launch geometry, partial rows and summation order of a plan_N-image call (both branches: split <= 32, and the
+ * statistics / sums launch above it); per image the results are bit for bit those of mstg_norm_act_fwd / _bwd on its own group. */
+size_t mstg_norm_workspace_bytes_plan(int N, int plan_N, int HW, int C);
+int mstg_norm_act_fwd_plan(const float* x, const float* residual /*nullable*/, float* y, float* stats /* [N][C][2] */, int N, int plan_N,
+                           int HW, int C, int act, void* workspace, size_t workspace_bytes, void* stream);
+int mstg_norm_act_bwd_plan(const float* x, const float* stats, const float* dy, float* dx, int N, int plan_N, int HW, int C, int act,
+                           void* workspace, size_t workspace_bytes, void* stream);
 /* The two halves on their own, for a norm whose neighbours do the other half (mstg_window_attn_norm_*): statistics only
  * (stats[n][c] = {mean, rstd}, bit-identical to what mstg_norm_act_fwd stores), and the backward's apply pass given
  * sums[n][s][2][C]: rows that add up, per (image, channel), to sum(dy * act') and sum(dy * act' * x^) (InstanceNorm only). */

@@ -350,3 +350,53 @@ class EnhancedDiscriminator(nn.Module):
             for mod in (self.structure_head[0], self.structure_head[3]):
                 mod.__dict__.pop("_mstg_sn_fresh", None)
         return score, st
+
+    def can_group(self, inputs):
+        """Whether forward_grouped may fold the forwards into one pass (else it runs them in sequence): train mode with the grouped
+        spectral norm, both heads computed, 2 .. mstg_conv2d_group_max() inputs of one shape; MSTG_D_GROUPED=0 switches it off."""
+        if not (self.training and self._sn_grouped and 2 <= len(inputs) <= ops.conv_group_max()):
+            return False
+        if (os.environ.get("MSTG_D_GROUPED", "1") == "0" or os.environ.get("MSTG_SN_GROUP", "1") == "0"
+                or os.environ.get("MSTG_D_SKIP_DEAD_HEADS", "0") == "1"):
+            return False
+        x0 = inputs[0]
+        return all(x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and x.shape == x0.shape for x in inputs)
+
+    def forward_grouped(self, inputs, needs_grad=None, sets=None):
+        """[self(x) for x in inputs] -- k forwards in the reference's sequence, each with its own spectral-norm power iteration --
+        as one pass over the k * N images.  The iterations depend on weight_orig / weight_u / weight_v alone, so the k normalised
+        filter sets are produced first (u and v end where k sequential forwards leave them, and self.<conv>.weight is the last
+        set); image group i then reads filter set sets[i] (default i: input i is the i-th forward of the sequence; another order
+        only changes in which order autograd sums the gradients of an image tensor passed more than once -- it takes them in input
+        order).  needs_grad[i] False = that forward ran under torch.no_grad(): its outputs carry no graph and it takes no part in
+        the backward.  Returns [(score, structure)] per input, bit for bit what the sequential forwards return; they are what
+        runs when can_group() says no."""
+        k = len(inputs)
+        needs_grad = [True] * k if needs_grad is None else list(needs_grad)
+        sets = list(range(k)) if sets is None else list(sets)
+        if sorted(sets) != list(range(k)) or len(needs_grad) != k:
+            raise RuntimeError("EnhancedDiscriminator.forward_grouped: sets must be a permutation of range(len(inputs))")
+        if not self.can_group(inputs):
+            out = [None] * k
+            for j in range(k):  # the j-th forward of the sequence
+                i = sets.index(j)
+                with torch.enable_grad() if needs_grad[i] else torch.no_grad():
+                    out[i] = self(inputs[i])
+            return out
+        convs = self._sn_convs()
+        weight_sets = []
+        for _ in range(k):
+            ops.spectral_norm_group(convs)
+            weight_sets.append([m.weight for m in convs])
+        for m in convs:
+            m.__dict__.pop("_mstg_sn_fresh", None)  # no module hook runs in the grouped pass
+        xs = [x if g else x.detach() for x, g in zip(inputs, needs_grad)]
+        wsel = [weight_sets[sets[i]] if needs_grad[i] else [w.detach() for w in weight_sets[sets[i]]] for i in range(k)]
+        res = ops.discriminator_grouped(xs, wsel, [m.bias for m in convs])
+        N = inputs[0].shape[0]
+        out = []
+        for i, (sc, st) in enumerate(res):
+            if not needs_grad[i]:
+                sc, st = sc.detach(), st.detach()
+            out.append((sc.view(N, 1, 1, 1).squeeze(), st.permute(0, 3, 1, 2)))
+        return out

@@ -198,14 +198,22 @@ class EnhancedCycleGAN:
         # ---- discriminator update (reference :67-85)
         self.d_optimizer.zero_grad(set_to_none=True)
         fork()
+        # Each discriminator's forwards of a phase as ONE pass over their images (EnhancedDiscriminator.forward_grouped): the forwards
+        # differ only in the spectral-norm power iteration each takes first, and those depend on the weights alone.  Same launches per
+        # image, same results bit for bit, a half / a third of the launches.  MSTG_D_GROUPED=0 (and whatever can_group() names) keeps
+        # the sequence below.
+        def d_scores(D, real, fake):
+            if D.can_group((real, fake)):
+                (real_score, _), (fake_score, _) = D.forward_grouped((real, fake))
+            else:
+                real_score, _ = D(real, outputs="score")  # the structure head's output is discarded here (:67-85)
+                fake_score, _ = D(fake, outputs="score")
+            return ops.mse_to_const(real_score, 1.0), ops.mse_to_const(fake_score, 0.0)
+
         with on(sC):
-            real_A_score, _ = D_A(real_A, outputs="score")  # the structure head's output is discarded here (:67-85)
-            fake_A_score, _ = D_A(fake_A.detach(), outputs="score")
-            dA_real, dA_fake = ops.mse_to_const(real_A_score, 1.0), ops.mse_to_const(fake_A_score, 0.0)
+            dA_real, dA_fake = d_scores(D_A, real_A, fake_A.detach())
         with on(sD):
-            real_B_score, _ = D_B(real_B, outputs="score")
-            fake_B_score, _ = D_B(fake_B.detach(), outputs="score")
-            dB_real, dB_fake = ops.mse_to_const(real_B_score, 1.0), ops.mse_to_const(fake_B_score, 0.0)
+            dB_real, dB_fake = d_scores(D_B, real_B, fake_B.detach())
         join(dA_real, dA_fake, dB_real, dB_fake)
         # (dA_real + dB_real) * 0.5 + (dA_fake + dB_fake) * 0.5 (:72-81) as one weighted sum (one launch each way)
         d_loss = ops.weighted_sum((dA_real, dB_real, dA_fake, dB_fake), (0.5, 0.5, 0.5, 0.5))
@@ -253,24 +261,33 @@ class EnhancedCycleGAN:
             if two:
                 sC.wait_stream(upd)
                 sD.wait_stream(upd)
-            with on(sD):
-                fake_B_score, _ = D_B(fake_B, outputs="score")  # its structure output is overwritten two lines down (:110-113)
-                gB = ops.mse_to_const(fake_B_score, 1.0)
+
+            def g_terms(D, real, fake):
+                """(adversarial term, structure term) of one discriminator: its three forwards [fake with grad, real under no_grad,
+                fake with grad] of the reference's sequence"""
+                if D.can_group((fake, real, fake)):
+                    # The fake image is passed twice and autograd adds the two input gradients in input order.  The sequence's
+                    # graph delivers the THIRD forward's share first (its nodes are the younger ones), so the third forward's
+                    # filter set goes with the first input: the image's gradient -- these two shares and the reconstruction's -- is
+                    # then summed in the order it is summed without grouping.  The real images take no part in the backward.
+                    (_, fake_struct), (fake_score, _), (_, real_struct) = D.forward_grouped((fake, fake, real), needs_grad=(True, True, False),
+                                                                                            sets=(2, 0, 1))
+                    return ops.mse_to_const(fake_score, 1.0), ops.l1_loss(real_struct, fake_struct)
+                fake_score, _ = D(fake, outputs="score")  # its structure output is overwritten two lines down (:110-113)
+                g_adv = ops.mse_to_const(fake_score, 1.0)
                 with torch.no_grad():
-                    _, real_B_struct = D_B(real_B, outputs="struct")
-                _, fake_B_struct = D_B(fake_B, outputs="struct")
-                sB_l = ops.l1_loss(real_B_struct, fake_B_struct)
+                    _, real_struct = D(real, outputs="struct")
+                _, fake_struct = D(fake, outputs="struct")
+                return g_adv, ops.l1_loss(real_struct, fake_struct)
+
+            with on(sD):
+                gB, sB_l = g_terms(D_B, real_B, fake_B)
             if not recon_first:
                 with on(sB):
                     recon_A = G_BA(fake_B)
                     cA = ops.l1_loss(recon_A, real_A)
             with on(sC):
-                fake_A_score, _ = D_A(fake_A, outputs="score")
-                gA = ops.mse_to_const(fake_A_score, 1.0)
-                with torch.no_grad():
-                    _, real_A_struct = D_A(real_A, outputs="struct")
-                _, fake_A_struct = D_A(fake_A, outputs="struct")
-                sA_l = ops.l1_loss(real_A_struct, fake_A_struct)
+                gA, sA_l = g_terms(D_A, real_A, fake_A)
             join(gA, gB, cA, cB, sA_l, sB_l)
             # g + cycle * lambda + identity * lambda + structure * lambda (:95-118): the total as ONE weighted sum over the eight terms
             # (one launch forward, one backward); the four reported components come out of the same launch, without a graph

@@ -82,6 +82,14 @@ SIGNATURES = {
     "mstg_norm_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_norm_act_fwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
     "mstg_norm_act_bwd": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _vp, _sz, _vp]),
+    "mstg_norm_workspace_bytes_plan": (_sz, [_i, _i, _i, _i]),
+    "mstg_norm_act_fwd_plan": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mstg_norm_act_bwd_plan": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mstg_conv2d_group_max": (_i, []),
+    "mstg_conv2d_grouped_workspace_bytes": (_sz, [_dp, _i]),
+    "mstg_conv2d_fwd_grouped": (_i, [_dp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_conv2d_dgrad_grouped": (_i, [_dp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mstg_conv2d_grouped_kernel_name": (C.c_char_p, [_dp, _i]),
     "mstg_window_attn_core_fwd": (_i, [_fp, _fp, _i, _i, _i, _i, _vp]),
     "mstg_window_attn_core_bwd": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "mstg_window_attn_ws_supported": (_i, [_i, _i]),

@@ -49,7 +49,8 @@ template <int V> __host__ __device__ constexpr int ckp_heavy_of() { return V == 
 // ---- filter pre-pack ------------------------------------------------------------------------------------------------
 // wp[cls][chunk][tap][co (padded to CoP)][ci (CK)] : exactly the order the main kernels stage into LDS, so staging is a
 // run of 16-byte copies with no index arithmetic on the filter's own (OIHW / IOHW, flipped, parity-class) layout.
-__global__ void pack_filter_kernel(const IGemmArgs a, float* __restrict__ wp, int CK, int CoP, int nchunks, int ncls) {
+__device__ __forceinline__ void pack_filter_body(const IGemmArgs& a, const float* __restrict__ w, float* __restrict__ wp, int CK, int CoP,
+                                                 int nchunks, int ncls) {
     const int total = ncls * nchunks * a.ntaps * CoP * CK;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int ci = idx % CK;
@@ -71,8 +72,19 @@ __global__ void pack_filter_kernel(const IGemmArgs a, float* __restrict__ wp, in
             widx = a.flip ? (a.ntaps - 1 - t) : t;
         }
         const int cr = chunk * CK + ci;
-        wp[idx] = (ok && oc < a.Co && cr < a.Cr) ? a.w[(size_t)oc * a.w_so + (size_t)cr * a.w_sr + widx] : 0.f;
+        wp[idx] = (ok && oc < a.Co && cr < a.Cr) ? w[(size_t)oc * a.w_so + (size_t)cr * a.w_sr + widx] : 0.f;
     }
+}
+
+__global__ void pack_filter_kernel(const IGemmArgs a, float* __restrict__ wp, int CK, int CoP, int nchunks, int ncls) {
+    pack_filter_body(a, a.w, wp, CK, CoP, nchunks, ncls);
+}
+
+// the filters of a grouped launch in one (ConvGroups, igemm_args.h): blockIdx.y = group, packed into ws + group * ws_stride floats
+__global__ void pack_filter_grouped_kernel(const IGemmArgs a, const ConvGroups gs, float* __restrict__ ws, size_t ws_stride, int CK, int CoP,
+                                           int nchunks, int ncls) {
+    const int grp = blockIdx.y;
+    pack_filter_body(a, group_pick(gs.w, grp), ws + (size_t)grp * ws_stride, CK, CoP, nchunks, ncls);
 }
 
 // tap t -> LDS offset of its first pixel inside the patch
@@ -140,196 +152,33 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& a, const f32x4 (
 // =====================================================================================================================
 template <int V, int NFW, int PF>
 __global__ __launch_bounds__(256) void igemm_light_kernel(const IGemmArgs a, const float* __restrict__ wp, const int CoP) {
-    constexpr int CK = 4 * V, CKP = ckp_of<V>(), BN = 16 * NFW, TH = 4 * PF;
-    typedef typename Frag<V>::T frag_t;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* patch = smem;
-    float* wl = smem + ((a.PH * a.PW * CKP + 3) & ~3);
-    int* tapo = reinterpret_cast<int*>(wl + (a.wglob ? 0 : a.TG * BN * CKP));  // LDS offset of every tap inside the patch
+#define IG_BX blockIdx.x
+#define IG_NBX gridDim.x
+#include "igemm_light_body.h"
+#undef IG_BX
+#undef IG_NBX
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
-    const int tile = xcd_swizzle(blockIdx.x, gridDim.x);
-    const int tx0 = tile % a.tiles_x, ty0 = (tile / a.tiles_x) % a.tiles_y, n = tile / (a.tiles_x * a.tiles_y);
-    const int co0 = blockIdx.y * BN;
-    const int cls = blockIdx.z, pa = cls >> 1, pb = cls & 1;
-    const int s = a.phase ? 1 : a.stride;
-    const int y0 = a.phase ? ty0 * TH - 1 : ty0 * TH * s - a.pad;
-    // dpack: tiles advance by 13 output columns; the 16 accumulator columns start 3 pixels to their left
-    const int x0 = a.phase ? tx0 * TILE_W - 1 : (a.dpack ? tx0 * 13 - 3 - a.pad : tx0 * TILE_W * s - a.pad);
-    const int nchunks = (a.Cr + CK - 1) / CK;
-    const unsigned m_pw = magic_u32(a.PW);
-    MSTG_STAMP(0)
-    if (tid < a.ntaps) tapo[tid] = tap_patch_offset(a, tid, pa, pb, CKP);  // visible after the first barrier below
+// One group's pointers put into its copy of the gather (grouped launches: ConvGroups, igemm_args.h); gs.w = the groups' PACKED filters
+__device__ __forceinline__ IGemmArgs igemm_group_args(const IGemmArgs& a0, const ConvGroups& gs, int grp) {
+    IGemmArgs a = a0;
+    a.x = group_pick(gs.x, grp);
+    a.y = group_pick(gs.y, grp);
+    a.bias = group_pick(gs.bias, grp);
+    return a;
+}
 
-    f32x4 acc[NFW][PF];
-#pragma unroll
-    for (int wf = 0; wf < NFW; ++wf)
-#pragma unroll
-        for (int pf = 0; pf < PF; ++pf) acc[wf][pf] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int chunk = 0; chunk < nchunks; ++chunk) {
-        if (chunk) __syncthreads();
-        // ---- stage the source patch (halo included, zero outside the image) -------------------------------------
-        if (a.x_nchw) {  // 3-channel image tensor, V == 1: channel 3 of the k-slot group is zero
-            stage_window_c4(a.x + ((size_t)n * a.x_ctot + a.x_coff) * a.H * a.W, patch, a.PH, a.PW, m_pw, y0, x0, a.H, a.W, (unsigned)a.W, 1u,
-                            (unsigned)(a.H * a.W), a.Cr, tid);
-        } else if (((a.x_ctot | a.x_coff | a.Cr) & 3) == 0) {
-            stage_window(a.x + (size_t)n * a.H * a.W * a.x_ctot + a.x_coff + chunk * CK, patch, a.PH, a.PW, V, m_pw, 0xFFFFFFFFu / V + 1u, y0,
-                         x0, a.H, a.W, a.x_ctot, min(V, (a.Cr - chunk * CK) >> 2), CKP, tid);
-        } else {
-            for (int pr = wave; pr < a.PH; pr += 4) {
-                const int iy = y0 + pr;
-                for (int e = lane; e < a.PW * V; e += 64) {
-                    const int pc = e / V, q = e % V;
-                    const int ix = x0 + pc;
-                    const bool inb = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                    const int c0 = chunk * CK + 4 * q;
-                    if (inb && c0 < a.Cr) {
-                        const float* src = a.x + (((size_t)n * a.H + iy) * a.W + ix) * a.x_ctot + a.x_coff + c0;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c)
-                            if (c0 + c < a.Cr) v[c] = src[c];
-                    }
-                    *reinterpret_cast<f32x4*>(&patch[(pr * a.PW + pc) * CKP + 4 * q]) = v;
-                }
-            }
-        }
-        MSTG_STAMP(1)
-        if (a.wglob) {
-            // ---- filter fragments from L2: no filter slice in LDS, no second barrier; tap t+2's fragment is in flight --------------
-            __syncthreads();
-            const float* wb = wp + ((size_t)((cls * nchunks + chunk) * a.ntaps) * CoP + co0 + i) * CK + V * g;
-            const int wts = CoP * CK;  // floats between consecutive taps
-            const int bbase0 = ((PF * wave) * s * a.PW + i * s) * CKP + V * g, bstep = s * a.PW * CKP;
-            frag_t a0[NFW], a1[NFW], a2[NFW], bf[PF], bfn[PF];
-#pragma unroll
-            for (int wf = 0; wf < NFW; ++wf) {
-                a0[wf] = *reinterpret_cast<const frag_t*>(wb + 16 * wf * CK);
-                a1[wf] = *reinterpret_cast<const frag_t*>(wb + min(1, a.ntaps - 1) * wts + 16 * wf * CK);
-            }
-            {
-                const int po = tapo[0];
-#pragma unroll
-                for (int pf = 0; pf < PF; ++pf) bf[pf] = *reinterpret_cast<const frag_t*>(&patch[bbase0 + pf * bstep + po]);
-            }
-            for (int tl = 0; tl < a.ntaps; ++tl) {
-                const int t2 = min(tl + 2, a.ntaps - 1), t1 = min(tl + 1, a.ntaps - 1);
-#pragma unroll
-                for (int wf = 0; wf < NFW; ++wf) a2[wf] = *reinterpret_cast<const frag_t*>(wb + t2 * wts + 16 * wf * CK);
-                const int po = tapo[t1];
-#pragma unroll
-                for (int pf = 0; pf < PF; ++pf) bfn[pf] = *reinterpret_cast<const frag_t*>(&patch[bbase0 + pf * bstep + po]);
-#pragma unroll
-                for (int j = 0; j < V; ++j)
-#pragma unroll
-                    for (int wf = 0; wf < NFW; ++wf)
-#pragma unroll
-                        for (int pf = 0; pf < PF; ++pf)
-                            acc[wf][pf] = mfma16(frag_get<V>(a0[wf], j), frag_get<V>(bf[pf], j), acc[wf][pf]);
-#pragma unroll
-                for (int wf = 0; wf < NFW; ++wf) { a0[wf] = a1[wf]; a1[wf] = a2[wf]; }
-#pragma unroll
-                for (int pf = 0; pf < PF; ++pf) bf[pf] = bfn[pf];
-            }
-            continue;
-        }
-        for (int t0 = 0; t0 < a.ntaps; t0 += a.TG) {
-            __syncthreads();  // patch staged / previous tap group consumed
-            MSTG_STAMP(2)
-            const int tn = min(a.TG, a.ntaps - t0);
-            // ---- stage this tap group's filter slice: 16-byte copies out of the packed filter ---------------------
-            const float* base = wp + ((size_t)((cls * nchunks + chunk) * a.ntaps + t0) * CoP + co0) * CK;
-            for (int e0 = 0; e0 < tn * BN * V; e0 += 1024) {
-                f32x4 wv[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int e = min(e0 + 256 * k + tid, tn * BN * V - 1);
-                    const int row = e / V, q = e % V, tl = row / BN, col = row % BN;
-                    wv[k] = *reinterpret_cast<const f32x4*>(base + (unsigned)((tl * CoP + col) * CK + 4 * q));
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int e = e0 + 256 * k + tid;
-                    if (e < tn * BN * V) *reinterpret_cast<f32x4*>(&wl[(e / V) * CKP + 4 * (e % V)]) = wv[k];
-                }
-            }
-            MSTG_STAMP(3)
-            __syncthreads();
-            MSTG_STAMP(4)
-            // ---- MFMA over the group's taps -------------------------------------------------------------------------
-            // fragments of tap tl+1 are read while the MFMAs of tap tl run
-            const int bbase0 = ((PF * wave) * s * a.PW + i * s) * CKP + V * g, bstep = s * a.PW * CKP;
-            frag_t af[NFW], bf[PF], afn[NFW], bfn[PF];
-            {
-                const int po = tapo[t0];
-#pragma unroll
-                for (int wf = 0; wf < NFW; ++wf) af[wf] = *reinterpret_cast<const frag_t*>(&wl[(16 * wf + i) * CKP + V * g]);
-#pragma unroll
-                for (int pf = 0; pf < PF; ++pf) bf[pf] = *reinterpret_cast<const frag_t*>(&patch[bbase0 + pf * bstep + po]);
-            }
-            for (int tl = 0; tl < ((a.dbg & 1) ? 1 : tn); ++tl) {
-                const int tnx = min(tl + 1, tn - 1);
-                const int po = tapo[t0 + tnx];
-#pragma unroll
-                for (int wf = 0; wf < NFW; ++wf) afn[wf] = *reinterpret_cast<const frag_t*>(&wl[(tnx * BN + 16 * wf + i) * CKP + V * g]);
-#pragma unroll
-                for (int pf = 0; pf < PF; ++pf) bfn[pf] = *reinterpret_cast<const frag_t*>(&patch[bbase0 + pf * bstep + po]);
-#pragma unroll
-                for (int j = 0; j < V; ++j)
-#pragma unroll
-                    for (int wf = 0; wf < NFW; ++wf)
-#pragma unroll
-                        for (int pf = 0; pf < PF; ++pf)
-                            acc[wf][pf] = mfma16(frag_get<V>(af[wf], j), frag_get<V>(bf[pf], j), acc[wf][pf]);
-#pragma unroll
-                for (int wf = 0; wf < NFW; ++wf) af[wf] = afn[wf];
-#pragma unroll
-                for (int pf = 0; pf < PF; ++pf) bf[pf] = bfn[pf];
-            }
-        }
-    }
-    MSTG_STAMP(5)
-    if (!a.dpack) {
-        igemm_epilogue<NFW, PF>(a, acc, n, ty0, tx0, co0, pa, pb, wave, i, g);
-        MSTG_STAMP(6)
-        return;
-    }
-    // ---- dpack epilogue.  Accumulator row 4*delta + c of pixel column p is a partial sum of output column p + delta:
-    //      y[q][c] = sum_delta D[delta][q - delta].  Exchange through LDS, then lanes (q < 13, pf) finish 13 columns. ---------
-    __syncthreads();  // everybody is done with the filter / patch tiles: reuse the front of LDS
-    float* comb = smem + wave * (256 * PF);  // [pf][delta][p][4]
-#pragma unroll
-    for (int pf = 0; pf < PF; ++pf) *reinterpret_cast<f32x4*>(&comb[((pf * 4 + g) * 16 + i) * 4]) = acc[0][pf];
-    __syncthreads();
-    if (g < PF && i < 13) {
-        const int pf = g;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int d = 0; d < 4; ++d) v += *reinterpret_cast<const f32x4*>(&comb[((pf * 4 + d) * 16 + i + 3 - d) * 4]);
-        const int oy = ty0 * TH + PF * wave + pf, ox = tx0 * 13 + i;
-        if (oy < a.Gh && ox < a.Gw) {
-            if (!a.y_nchw && a.Co == 4 && ((a.y_ctot | a.y_coff) & 3) == 0) {  // a whole 4-channel slice: one 16-byte store
-                float* p = a.y + (((size_t)n * a.Ho + oy) * a.Wo + ox) * a.y_ctot + a.y_coff;
-                if (a.bias) v += *reinterpret_cast<const f32x4*>(a.bias);
-                if (a.accumulate) v += *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = apply_act(v[e], a.act);
-                *reinterpret_cast<f32x4*>(p) = v;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (e >= a.Co) continue;
-                    float* p = a.y_nchw ? a.y + (((size_t)n * a.y_ctot + a.y_coff + e) * a.Ho + oy) * a.Wo + ox
-                                        : a.y + (((size_t)n * a.Ho + oy) * a.Wo + ox) * a.y_ctot + a.y_coff + e;
-                    float val = v[e] + (a.bias ? a.bias[e] : 0.f);
-                    if (a.accumulate) val += *p;
-                    *p = apply_act(val, a.act);
-                }
-            }
-        }
-    }
-    MSTG_STAMP(6)
+// G copies of igemm_light_kernel's grid side by side along x: group = blockIdx.x / bpg, bpg = one group's tiles
+template <int V, int NFW, int PF>
+__global__ __launch_bounds__(256) void igemm_light_grouped_kernel(const IGemmArgs a0, const ConvGroups gs, const int CoP) {
+    const int grp = (int)blockIdx.x / gs.bpg, bx = (int)blockIdx.x - grp * gs.bpg;
+    const IGemmArgs a = igemm_group_args(a0, gs, grp);
+    const float* __restrict__ wp = group_pick(gs.w, grp);
+#define IG_BX bx
+#define IG_NBX gs.bpg
+#include "igemm_light_body.h"
+#undef IG_BX
+#undef IG_NBX
 }
 
 // =====================================================================================================================
@@ -637,200 +486,24 @@ constexpr int NWQ = 5;   // filter float4 slots per thread
 
 template <int V, int NFW, int SRC>
 __global__ __launch_bounds__(256) void igemm_heavy_kernel(const IGemmArgs a, const float* __restrict__ wp, const int CoP) {
-    constexpr int CK = 4 * V, CKP = ckp_heavy_of<V>(), BN = 16 * NFW;
-    typedef typename Frag<V>::T frag_t;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int PSZ = (a.PH * a.PW * CKP + 3) & ~3, WSZ = a.TG * BN * CKP;
+#define IG_BX blockIdx.x
+#define IG_NBX gridDim.x
+#include "igemm_heavy_body.h"
+#undef IG_BX
+#undef IG_NBX
+}
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
-    const int co0 = blockIdx.y * BN;
-    const int cls = blockIdx.z, pa = cls >> 1, pb = cls & 1;
-    const int s = a.phase ? 1 : a.stride;
-    const int nchunks = (a.Cr + CK - 1) / CK;
-    const int ngroups = (a.ntaps + a.TG - 1) / a.TG;
-    const int ntiles = a.N * a.tiles_x * a.tiles_y;
-    const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int total = my_tiles * nchunks * ngroups;
-    const int npatch = a.PH * a.PW * V;
-
-    // per-thread slot descriptors (tile independent).  patch: LDS float offset, row, col, quad; unused slots read pixel 0.
-    int p_lds[NPQ], p_rc[NPQ];
-#pragma unroll
-    for (int j = 0; j < NPQ; ++j) {
-        const int e = tid + 256 * j;
-        const bool used = e < npatch;
-        const int ee = used ? e : 0;
-        const int pr = ee / (a.PW * V), rem = ee % (a.PW * V), pc = rem / V, q = rem % V;
-        p_lds[j] = used ? (pr * a.PW + pc) * CKP + 4 * q : -1;
-        p_rc[j] = pr | (pc << 8) | (q << 16);
-    }
-    int w_src[NWQ], w_lds[NWQ];  // filter: offset inside the stage's packed slice (tap-local), LDS float offset, or -1
-#pragma unroll
-    for (int j = 0; j < NWQ; ++j) {
-        const int e = tid + 256 * j, row = e / V, q = e % V, tl = row / BN, col = row % BN;
-        const bool used = tl < a.TG;
-        w_src[j] = used ? (tl * CoP + col) * CK + 4 * q : 0;
-        w_lds[j] = used ? row * CKP + 4 * q : -1;
-    }
-
-    // two cursors over (tile sequence number, chunk, tap group): cur = stage being computed, nxt = stage being loaded
-    int c_seq = 0, c_chunk = 0, c_tg = 0, c_tx0, c_ty0, c_n;
-    int n_seq = 0, n_chunk = 0, n_tg = 0, n_tx0, n_ty0, n_n;
-    {
-        const int tile = xcd_swizzle((int)blockIdx.x, ntiles);
-        c_tx0 = n_tx0 = tile % a.tiles_x;
-        c_ty0 = n_ty0 = (tile / a.tiles_x) % a.tiles_y;
-        c_n = n_n = tile / (a.tiles_x * a.tiles_y);
-    }
-
-    f32x4 preg[NPQ], wreg[NWQ];
-
-#define IG_LOAD_STAGE()                                                                                                     \
-    {                                                                                                                       \
-        if (n_tg == 0) {                                                                                                    \
-            const int y0 = a.phase ? n_ty0 * TILE_H - 1 : n_ty0 * TILE_H * s - a.pad;                                       \
-            const int x0 = a.phase ? n_tx0 * TILE_W - 1 : n_tx0 * TILE_W * s - a.pad;                                       \
-            _Pragma("unroll") for (int j = 0; j < NPQ; ++j) {                                                               \
-                const int iy = min(max(y0 + (p_rc[j] & 255), 0), a.H - 1), ix = min(max(x0 + ((p_rc[j] >> 8) & 255), 0), a.W - 1); \
-                if (SRC == 2) {                                                                                             \
-                    const size_t cs = (size_t)a.H * a.W;                                                                    \
-                    const float* src = a.x + (((size_t)n_n * a.x_ctot + a.x_coff) * a.H + iy) * a.W + ix;                   \
-                    preg[j][0] = src[0];                                                                                    \
-                    preg[j][1] = src[(a.Cr > 1 ? 1 : 0) * cs];                                                              \
-                    preg[j][2] = src[(a.Cr > 2 ? 2 : 0) * cs];                                                              \
-                    preg[j][3] = src[(a.Cr > 3 ? 3 : 0) * cs];                                                              \
-                } else if (SRC == 0) {                                                                                      \
-                    const int c0 = min(n_chunk * CK + 4 * (p_rc[j] >> 16), a.Cr - 4);                                       \
-                    preg[j] = *reinterpret_cast<const f32x4*>(a.x + (((size_t)n_n * a.H + iy) * a.W + ix) * a.x_ctot + a.x_coff + c0); \
-                } else {                                                                                                    \
-                    const int c0 = min(n_chunk * CK + 4 * (p_rc[j] >> 16), a.Cr - 1), rem = a.Cr - 1 - c0;                  \
-                    const float* src = a.x + (((size_t)n_n * a.H + iy) * a.W + ix) * a.x_ctot + a.x_coff + c0;              \
-                    preg[j][0] = src[0];                                                                                    \
-                    preg[j][1] = src[min(1, rem)];                                                                          \
-                    preg[j][2] = src[min(2, rem)];                                                                          \
-                    preg[j][3] = src[min(3, rem)];                                                                          \
-                }                                                                                                           \
-            }                                                                                                               \
-        }                                                                                                                   \
-        {                                                                                                                   \
-            const int t0 = n_tg * a.TG, tlast = a.ntaps - 1 - t0;                                                           \
-            const float* base = wp + ((size_t)((cls * nchunks + n_chunk) * a.ntaps + t0) * CoP + co0) * CK;                 \
-            const int lim = tlast * CoP * CK;  /* rows of taps beyond the filter are clamped to its last tap */             \
-            _Pragma("unroll") for (int j = 0; j < NWQ; ++j) {                                                               \
-                const int off = w_src[j] > lim + (CoP - 1) * CK + CK - 4 ? 0 : w_src[j];                                    \
-                wreg[j] = *reinterpret_cast<const f32x4*>(base + off);                                                      \
-            }                                                                                                               \
-        }                                                                                                                   \
-    }
-
-#define IG_STORE_STAGE(KBUF)                                                                                                \
-    {                                                                                                                       \
-        if (n_tg == 0) {                                                                                                    \
-            float* patch = smem + ((n_seq * nchunks + n_chunk) & 1) * PSZ;                                                  \
-            const int y0 = a.phase ? n_ty0 * TILE_H - 1 : n_ty0 * TILE_H * s - a.pad;                                       \
-            const int x0 = a.phase ? n_tx0 * TILE_W - 1 : n_tx0 * TILE_W * s - a.pad;                                       \
-            _Pragma("unroll") for (int j = 0; j < NPQ; ++j) {                                                               \
-                if (p_lds[j] >= 0) {                                                                                        \
-                    const int iy = y0 + (p_rc[j] & 255), ix = x0 + ((p_rc[j] >> 8) & 255);                                  \
-                    const bool inb = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;                          \
-                    const int c0 = SRC == 2 ? 0 : n_chunk * CK + 4 * (p_rc[j] >> 16);                                       \
-                    const int nreal = inb ? a.Cr - c0 : 0;                                                                  \
-                    f32x4 v = preg[j];                                                                                      \
-                    v[0] = nreal > 0 ? v[0] : 0.f;                                                                          \
-                    v[1] = nreal > 1 ? v[1] : 0.f;                                                                          \
-                    v[2] = nreal > 2 ? v[2] : 0.f;                                                                          \
-                    v[3] = nreal > 3 ? v[3] : 0.f;                                                                          \
-                    *reinterpret_cast<f32x4*>(&patch[p_lds[j]]) = v;                                                        \
-                }                                                                                                           \
-            }                                                                                                               \
-        }                                                                                                                   \
-        {                                                                                                                   \
-            float* wl = smem + 2 * PSZ + (KBUF)*WSZ;                                                                        \
-            const int tn = min(a.TG, a.ntaps - n_tg * a.TG);                                                                \
-            _Pragma("unroll") for (int j = 0; j < NWQ; ++j) {                                                               \
-                if (w_lds[j] >= 0 && w_lds[j] < tn * BN * CKP) *reinterpret_cast<f32x4*>(&wl[w_lds[j]]) = wreg[j];          \
-            }                                                                                                               \
-        }                                                                                                                   \
-    }
-
-#define IG_ADVANCE(P)                                                                                                       \
-    {                                                                                                                       \
-        if (++P##_tg == ngroups) {                                                                                          \
-            P##_tg = 0;                                                                                                     \
-            if (++P##_chunk == nchunks) {                                                                                   \
-                P##_chunk = 0;                                                                                              \
-                ++P##_seq;                                                                                                  \
-                if (P##_seq < my_tiles) {                                                                                   \
-                    const int tile = xcd_swizzle((int)blockIdx.x + P##_seq * (int)gridDim.x, ntiles);                       \
-                    P##_tx0 = tile % a.tiles_x;                                                                             \
-                    P##_ty0 = (tile / a.tiles_x) % a.tiles_y;                                                               \
-                    P##_n = tile / (a.tiles_x * a.tiles_y);                                                                 \
-                }                                                                                                           \
-            }                                                                                                               \
-        }                                                                                                                   \
-    }
-
-    if (total > 0) {
-        IG_LOAD_STAGE();
-        IG_STORE_STAGE(0);
-        IG_ADVANCE(n);
-    }
-    __syncthreads();
-
-    f32x4 acc[NFW][2];
-    for (int k = 0; k < total; ++k) {
-        const bool more = k + 1 < total;
-        if (more) IG_LOAD_STAGE();  // in flight during the MFMAs below
-        const float* wl = smem + 2 * PSZ + (k & 1) * WSZ;
-        const float* patch = smem + ((c_seq * nchunks + c_chunk) & 1) * PSZ;
-        if (c_chunk == 0 && c_tg == 0) {
-#pragma unroll
-            for (int wf = 0; wf < NFW; ++wf)
-#pragma unroll
-                for (int pf = 0; pf < 2; ++pf) acc[wf][pf] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        // ---- MFMA over the group's taps; the fragments of tap t+1 are read from LDS while tap t's MFMAs issue ------
-        const int t0 = c_tg * a.TG, tn = min(a.TG, a.ntaps - t0);
-        const int brow0 = ((2 * wave) * s * a.PW + i * s) * CKP + V * g, brow1 = brow0 + s * a.PW * CKP;
-        const int arow = i * CKP + V * g;
-        frag_t af[NFW], bf[2], afn[NFW], bfn[2];
-        {
-            const int po = tap_patch_offset(a, t0, pa, pb, CKP);
-#pragma unroll
-            for (int wf = 0; wf < NFW; ++wf) af[wf] = *reinterpret_cast<const frag_t*>(&wl[16 * wf * CKP + arow]);
-            bf[0] = *reinterpret_cast<const frag_t*>(&patch[brow0 + po]);
-            bf[1] = *reinterpret_cast<const frag_t*>(&patch[brow1 + po]);
-        }
-        for (int tl = 0; tl < tn; ++tl) {
-            const int tnext = min(tl + 1, tn - 1);
-            const int po = tap_patch_offset(a, t0 + tnext, pa, pb, CKP);
-#pragma unroll
-            for (int wf = 0; wf < NFW; ++wf) afn[wf] = *reinterpret_cast<const frag_t*>(&wl[(tnext * BN + 16 * wf) * CKP + arow]);
-            bfn[0] = *reinterpret_cast<const frag_t*>(&patch[brow0 + po]);
-            bfn[1] = *reinterpret_cast<const frag_t*>(&patch[brow1 + po]);
-#pragma unroll
-            for (int j = 0; j < V; ++j)
-#pragma unroll
-                for (int wf = 0; wf < NFW; ++wf)
-#pragma unroll
-                    for (int pf = 0; pf < 2; ++pf)
-                        acc[wf][pf] = mfma16(frag_get<V>(af[wf], j), frag_get<V>(bf[pf], j), acc[wf][pf]);
-#pragma unroll
-            for (int wf = 0; wf < NFW; ++wf) af[wf] = afn[wf];
-            bf[0] = bfn[0];
-            bf[1] = bfn[1];
-        }
-        if (c_chunk == nchunks - 1 && c_tg == ngroups - 1) igemm_epilogue<NFW>(a, acc, c_n, c_ty0, c_tx0, co0, pa, pb, wave, i, g);
-        if (more) {
-            IG_STORE_STAGE((k + 1) & 1);
-            IG_ADVANCE(n);
-        }
-        IG_ADVANCE(c);
-        __syncthreads();
-    }
-#undef IG_LOAD_STAGE
-#undef IG_STORE_STAGE
-#undef IG_ADVANCE
+// G copies of igemm_heavy_kernel side by side along x: the persistent workgroups of the grid are split among the groups, bpg each
+template <int V, int NFW, int SRC>
+__global__ __launch_bounds__(256) void igemm_heavy_grouped_kernel(const IGemmArgs a0, const ConvGroups gs, const int CoP) {
+    const int grp = (int)blockIdx.x / gs.bpg, bx = (int)blockIdx.x - grp * gs.bpg;
+    const IGemmArgs a = igemm_group_args(a0, gs, grp);
+    const float* __restrict__ wp = group_pick(gs.w, grp);
+#define IG_BX bx
+#define IG_NBX gs.bpg
+#include "igemm_heavy_body.h"
+#undef IG_BX
+#undef IG_NBX
 }
 
 struct IGemmPlan {
@@ -1106,6 +779,83 @@ int launch_igemm(IGemmArgs& a, void* workspace, size_t workspace_bytes, hipStrea
     return fail_arg(MSTG_E_UNSUPPORTED, "conv: no kernel variant");
 }
 
+// ---- grouped launches: G copies of the launch planned for ONE group in one grid (ConvGroups, igemm_args.h) ----------------------------
+template <int V, int NFW, int PF>
+static int launch_light_grouped_t(IGemmArgs& a, const IGemmPlan& p, ConvGroups gs, hipStream_t st) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_light_grouped_kernel<V, NFW, PF>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(igemm_light_grouped)");
+        attr_set = true;
+    }
+    const long ntiles = (long)a.N * a.tiles_x * a.tiles_y;
+    if (ntiles * gs.G >= (1L << 31)) return fail_arg(MSTG_E_UNSUPPORTED, "conv grouped: grid too large");
+    gs.bpg = (int)ntiles;
+    dim3 grid((unsigned)(ntiles * gs.G), p.CoP / p.BN, p.ncls);
+    MSTG_LAUNCH((igemm_light_grouped_kernel<V, NFW, PF>), grid, dim3(256), p.lds, st, a, gs, p.CoP);
+    MSTG_CHECK_LAUNCH("igemm_light_grouped_kernel");
+    return MSTG_OK;
+}
+
+template <int V, int NFW, int SRC>
+static int launch_heavy_grouped_t(IGemmArgs& a, const IGemmPlan& p, ConvGroups gs, hipStream_t st) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_heavy_grouped_kernel<V, NFW, SRC>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return fail_launch(e, "hipFuncSetAttribute(igemm_heavy_grouped)");
+        attr_set = true;
+    }
+    // the persistent workgroups of launch_heavy_t, split among the groups: a multiple of 8 each, at least 8, at most the group's tiles
+    const int ntiles = a.N * a.tiles_x * a.tiles_y, ny = p.CoP / p.BN, nz = p.ncls;
+    int per_cu = p.lds <= 80 * 1024 ? 2 : 1;
+    { const char* e = env_get(ENV_HEAVY_PER_CU); if (e) per_cu = atoi(e); }
+    int gx = ((256 * per_cu) / (ny * nz)) / gs.G;
+    gx = gx < 8 ? 8 : (gx & ~7);
+    if (gx > ntiles) gx = ntiles;
+    gs.bpg = gx;
+    dim3 grid(gx * gs.G, ny, nz);
+    MSTG_LAUNCH((igemm_heavy_grouped_kernel<V, NFW, SRC>), grid, dim3(256), p.lds, st, a, gs, p.CoP);
+    MSTG_CHECK_LAUNCH("igemm_heavy_grouped_kernel");
+    return MSTG_OK;
+}
+
+// a: one group's gather, tiled for the plan; its x / y / w / bias are group 0's (the routing reads which of them are null).
+// gs: every group's pointers, w and bias the modules' own; group k's workspace = ws_stride bytes at workspace + k * ws_stride.
+// MSTG_E_UNSUPPORTED where the routed kernel takes one group per launch (the stream kernel, the 7x7 image stem, the packed heads).
+int launch_igemm_grouped(IGemmArgs& a, ConvGroups gs, void* workspace, size_t ws_stride, hipStream_t st) {
+    IGemmRoute r = route_igemm(a);
+    if (r.kind == IG_IMG_DGRAD) return launch_img_dgrad_grouped(a, gs, st);
+    if (r.kind == IG_P32) return launch_p32_grouped(a, r.p32, gs, workspace, ws_stride, st);
+    if (r.kind == IG_NONE) return r.rc;
+    a.dbg = 0;
+    IGemmPlan& p = r.plan;
+    if (p.stream) return fail_arg(MSTG_E_UNSUPPORTED, "conv grouped: the stream kernel takes one group per launch");
+    if (!workspace || ws_stride < p.ws_bytes || (ws_stride & 15)) return fail_arg(MSTG_E_WORKSPACE, "conv grouped: workspace too small for the packed filters");
+    {
+        const int npack = p.ncls * p.nchunks * a.ntaps * p.CoP * p.CK;
+        const int nb = cdiv(npack, 256) > 256 ? 256 : cdiv(npack, 256);
+        MSTG_LAUNCH(pack_filter_grouped_kernel, dim3(nb, gs.G), dim3(256), 0, st, a, gs, (float*)workspace, ws_stride / 4, p.CK, p.CoP, p.nchunks,
+                    p.ncls);
+        MSTG_CHECK_LAUNCH("pack_filter_grouped_kernel");
+    }
+    for (int k = 0; k < gs.G; ++k) gs.w[k] = (const float*)((const char*)workspace + (size_t)k * ws_stride);  // the main kernel reads the packs
+#define MSTG_DISPATCH(VV, NN)                                                                       \
+    if (p.V == VV && p.nfw == NN) {                                                                 \
+        if (!p.heavy && p.pf == 4) return launch_light_grouped_t<VV, NN, 4>(a, p, gs, st);          \
+        if (!p.heavy) return launch_light_grouped_t<VV, NN, 2>(a, p, gs, st);                       \
+        if (p.src == 0) return launch_heavy_grouped_t<VV, NN, 0>(a, p, gs, st);                     \
+        if (p.src == 1) return launch_heavy_grouped_t<VV, NN, 1>(a, p, gs, st);                     \
+        if (VV == 1 && p.src == 2) return launch_heavy_grouped_t<1, NN, 2>(a, p, gs, st);           \
+    }
+    MSTG_DISPATCH(1, 1) MSTG_DISPATCH(1, 2) MSTG_DISPATCH(1, 4)
+    MSTG_DISPATCH(2, 1) MSTG_DISPATCH(2, 2) MSTG_DISPATCH(2, 4)
+    MSTG_DISPATCH(4, 1) MSTG_DISPATCH(4, 2) MSTG_DISPATCH(4, 4)
+#undef MSTG_DISPATCH
+    return fail_arg(MSTG_E_UNSUPPORTED, "conv: no kernel variant");
+}
+
 int check_desc(const mstg_conv_desc* d) {
     if (!d) return fail_arg(MSTG_E_BADARG, "conv: null descriptor");
     if (d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->KH <= 0 || d->KW <= 0 || d->stride <= 0 ||
@@ -1297,6 +1047,66 @@ extern "C" int mstg_conv2d_dgrad_cached(const mstg_conv_desc* d, const float* dy
                                         size_t workspace_bytes, int workspace_packed, void* stream) {
     PackedScope scope(workspace_packed);
     return mstg_conv2d_dgrad(d, dy, w, dx, workspace, workspace_bytes, stream);
+}
+
+// ---- grouped entry points: G launches of one descriptor, each with its own tensors and filter, as one launch chain -------------------
+static size_t group_ws_stride(const mstg_conv_desc* d) { return (mstg_conv2d_workspace_bytes(d) + 15) & ~(size_t)15; }
+
+extern "C" int mstg_conv2d_group_max(void) { return CONV_GROUP_MAX; }
+
+extern "C" size_t mstg_conv2d_grouped_workspace_bytes(const mstg_conv_desc* d, int G) {
+    if (G < 1 || G > CONV_GROUP_MAX) return 0;
+    return (size_t)G * group_ws_stride(d);
+}
+
+static int conv_grouped(const mstg_conv_desc* d, int pass, int G, const float* const* src, const float* const* w, const float* const* bias,
+                        float* const* dst, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_desc(d)) return rc;
+    if (G < 1 || G > CONV_GROUP_MAX) return fail_arg(MSTG_E_BADARG, "conv grouped: 1 <= G <= mstg_conv2d_group_max()");
+    if (!src || !w || !dst) return fail_arg(MSTG_E_BADARG, "conv grouped: null pointer table");
+    if (d->accumulate) return fail_arg(MSTG_E_UNSUPPORTED, "conv grouped: accumulate is a single-launch option");
+    ConvGroups gs{};
+    gs.G = G;
+    for (int k = 0; k < G; ++k) {
+        if (!src[k] || !w[k] || !dst[k]) return fail_arg(MSTG_E_BADARG, "conv grouped: null pointer");
+        if (bias && (bias[k] == nullptr) != (bias[0] == nullptr)) return fail_arg(MSTG_E_BADARG, "conv grouped: bias for all groups or for none");
+        gs.x[k] = src[k]; gs.y[k] = dst[k]; gs.w[k] = w[k]; gs.bias[k] = bias ? bias[k] : nullptr;
+    }
+    IGemmArgs a{};
+    if (pass == 0) fill_fwd_args(d, a);
+    else if (int rc = fill_dgrad_args(d, a)) return rc;
+    a.x = gs.x[0]; a.y = gs.y[0]; a.w = gs.w[0]; a.bias = gs.bias[0];
+    const size_t stride = group_ws_stride(d);
+    if (workspace_bytes < (size_t)G * stride) return fail_arg(MSTG_E_WORKSPACE, "conv grouped: workspace smaller than mstg_conv2d_grouped_workspace_bytes()");
+    return launch_igemm_grouped(a, gs, workspace, stride, (hipStream_t)stream);
+}
+
+extern "C" int mstg_conv2d_fwd_grouped(const mstg_conv_desc* d, int G, const float* const* x, const float* const* w, const float* const* bias,
+                                       float* const* y, void* workspace, size_t workspace_bytes, void* stream) {
+    return conv_grouped(d, 0, G, x, w, bias, y, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mstg_conv2d_dgrad_grouped(const mstg_conv_desc* d, int G, const float* const* dy, const float* const* w, float* const* dx,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+    return conv_grouped(d, 1, G, dy, w, nullptr, dx, workspace, workspace_bytes, stream);
+}
+
+// the kernel a grouped forward (0) / dgrad (1) launches, "" where the layer's kernel takes one group per launch (MSTG_E_UNSUPPORTED)
+extern "C" const char* mstg_conv2d_grouped_kernel_name(const mstg_conv_desc* d, int pass) {
+    static thread_local char name[64];
+    IGemmArgs a{};
+    if (check_desc(d) || d->accumulate) return "";
+    if (pass == 0) fill_fwd_args(d, a);
+    else if (pass != 1 || fill_dgrad_args(d, a)) return "";
+    const IGemmRoute r = route_igemm(a);
+    const IGemmPlan& p = r.plan;
+    if (r.kind == IG_NONE) return "";
+    if (r.kind == IG_P32) return p32_grouped_kernel_name(r.p32);
+    if (r.kind == IG_IMG_DGRAD) snprintf(name, sizeof(name), "conv_img_dgrad_grouped_kernel<%d>", a.Co);
+    else if (p.stream) return "";
+    else if (p.heavy) snprintf(name, sizeof(name), "igemm_heavy_grouped_kernel<%d, %d, %d>", p.V, p.nfw, p.src);
+    else snprintf(name, sizeof(name), "igemm_light_grouped_kernel<%d, %d, %d>", p.V, p.nfw, p.pf);
+    return name;
 }
 
 // kernel symbol (as rocprofv3 prints it, without namespace/arguments) a forward (0) / dgrad (1) call would launch; 3 / 4: the same two

@@ -17,9 +17,10 @@ constexpr int IMG_T = 16;  // taps of the 4x4 filter
 
 // input gradient: dy NHWC slice (N, Ho, Wo, Cr) of a tensor with x_ctot channels -> dx NCHW (N, CI, 2 Ho, 2 Wo).
 // Image row y takes filter rows ky with y = 2 oy - 1 + ky: rows 2q and 2q+1 of block q read dy rows q-1 (ky 3), q (ky 1 | 2), q+1 (ky 0).
+// bx / nbx: this workgroup's index and the workgroup count of its launch (of its group's copy in a grouped launch)
 template <int CI>
-__global__ __launch_bounds__(256) void conv_img_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx,
-                                                             int N, int Ho, int Wo, int Cr, int x_ctot, int x_coff, int w_so, int w_sr) {
+__device__ __forceinline__ void conv_img_dgrad_body(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx, int N,
+                                                    int Ho, int Wo, int Cr, int x_ctot, int x_coff, int w_so, int w_sr, int bx, int nbx) {
     extern __shared__ __attribute__((aligned(16))) float wl[];  // [tap][ci][Cr]
     const int tid = threadIdx.x;
     for (int e = tid; e < IMG_T * CI * Cr; e += 256) {
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void conv_img_dgrad_kernel(const float* __rest
     const long total = (long)N * Ho * Wo;
     const int H = 2 * Ho, W = 2 * Wo;
     const size_t plane = (size_t)H * W;
-    for (long idx = (long)blockIdx.x * 256 + tid; idx < total; idx += (long)gridDim.x * 256) {
+    for (long idx = (long)bx * 256 + tid; idx < total; idx += (long)nbx * 256) {
         const int qx = (int)(idx % Wo), qy = (int)((idx / Wo) % Ho), n = (int)(idx / ((long)Wo * Ho));
         float acc[2][2][CI];
 #pragma unroll
@@ -81,6 +82,21 @@ __global__ __launch_bounds__(256) void conv_img_dgrad_kernel(const float* __rest
     }
 }
 
+template <int CI>
+__global__ __launch_bounds__(256) void conv_img_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ w, float* __restrict__ dx,
+                                                             int N, int Ho, int Wo, int Cr, int x_ctot, int x_coff, int w_so, int w_sr) {
+    conv_img_dgrad_body<CI>(dy, w, dx, N, Ho, Wo, Cr, x_ctot, x_coff, w_so, w_sr, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// G copies of the launch above in one grid (ConvGroups, igemm_args.h): group = blockIdx.x / bpg
+template <int CI>
+__global__ __launch_bounds__(256) void conv_img_dgrad_grouped_kernel(const ConvGroups gs, int N, int Ho, int Wo, int Cr, int x_ctot, int x_coff,
+                                                                     int w_so, int w_sr) {
+    const int grp = (int)blockIdx.x / gs.bpg, bx = (int)blockIdx.x - grp * gs.bpg;
+    conv_img_dgrad_body<CI>(group_pick(gs.x, grp), group_pick(gs.w, grp), group_pick(gs.y, grp), N, Ho, Wo, Cr, x_ctot, x_coff, w_so, w_sr, bx,
+                            gs.bpg);
+}
+
 static bool img_on() {
     const char* e = env_get(ENV_CONV_IMG);
     return !(e && e[0] == '0');
@@ -114,6 +130,21 @@ int launch_img_dgrad(const IGemmArgs& a, hipStream_t st) {
     else MSTG_IMG_DGRAD(1);
 #undef MSTG_IMG_DGRAD
     MSTG_CHECK_LAUNCH("conv_img_dgrad_kernel");
+    return MSTG_OK;
+}
+
+int launch_img_dgrad_grouped(const IGemmArgs& a, ConvGroups gs, hipStream_t st) {
+    const long total = (long)a.N * a.H * a.W;  // one group's share: the grid of launch_img_dgrad, once per group
+    const size_t lds = (size_t)IMG_T * a.Co * a.Cr * sizeof(float);
+    gs.bpg = (int)img_grid(total);
+    const dim3 grid((unsigned)(gs.bpg * gs.G));
+#define MSTG_IMG_DGRAD(CI_)                                                                                                      \
+    MSTG_LAUNCH(conv_img_dgrad_grouped_kernel<CI_>, grid, dim3(256), lds, st, gs, a.N, a.H, a.W, a.Cr, a.x_ctot, a.x_coff, a.w_so, a.w_sr)
+    if (a.Co == 3) MSTG_IMG_DGRAD(3);
+    else if (a.Co == 2) MSTG_IMG_DGRAD(2);
+    else MSTG_IMG_DGRAD(1);
+#undef MSTG_IMG_DGRAD
+    MSTG_CHECK_LAUNCH("conv_img_dgrad_grouped_kernel");
     return MSTG_OK;
 }
 

@@ -42,8 +42,8 @@ struct P32Args {
 };
 
 // ---- filter pack: PyTorch layout (through the gather's strides) -> MFMA A-fragment order ---------------------------------------
-__global__ void p32_pack_kernel(const P32Plan p, const float* __restrict__ w, const float* __restrict__ bias, int w_so, int w_sr,
-                                int Cout, int Cin, float* __restrict__ wpk, float* __restrict__ bpk) {
+__device__ __forceinline__ void p32_pack_body(const P32Plan& p, const float* __restrict__ w, const float* __restrict__ bias, int w_so, int w_sr,
+                                              int Cout, int Cin, float* __restrict__ wpk, float* __restrict__ bpk) {
     const int total = p.nsteps * p.NF * 64 * 4;
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
         const int j = e & 3, lane = (e >> 2) & 63, sf = e >> 8, f = sf % p.NF, s = sf / p.NF;
@@ -53,6 +53,20 @@ __global__ void p32_pack_kernel(const P32Plan p, const float* __restrict__ w, co
         wpk[e] = v;
     }
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < 16 * p.NF; c += gridDim.x * blockDim.x) bpk[c] = (bias && c < Cout) ? bias[c] : 0.f;
+}
+
+__global__ void p32_pack_kernel(const P32Plan p, const float* __restrict__ w, const float* __restrict__ bias, int w_so, int w_sr,
+                                int Cout, int Cin, float* __restrict__ wpk, float* __restrict__ bpk) {
+    p32_pack_body(p, w, bias, w_so, w_sr, Cout, Cin, wpk, bpk);
+}
+
+// the filters of a grouped launch in one: blockIdx.y = group, whose workspace (bias block, then the packed filter) starts at
+// ws + group * ws_stride floats
+__global__ void p32_pack_grouped_kernel(const P32Plan p, const ConvGroups gs, int w_so, int w_sr, int Cout, int Cin, float* __restrict__ ws,
+                                        size_t ws_stride) {
+    const int grp = blockIdx.y;
+    float* base = ws + (size_t)grp * ws_stride;
+    p32_pack_body(p, group_pick(gs.w, grp), group_pick(gs.bias, grp), w_so, w_sr, Cout, Cin, base + 64, base);
 }
 
 template <int NPF>
@@ -101,243 +115,29 @@ __device__ __forceinline__ void p32_fetch(const P32Args& a, const P32Plan& p, in
 // reductions that norm backward needs (norm_partial_kernel<true> read f and dz once more for them).
 template <int RPW, int NF, int NPF, bool WLDS, int STATS>
 __global__ __launch_bounds__(256) void conv_p32_kernel(const P32Args a, const P32Plan p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int TH = 4 * RPW;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nl = lane & 15, g = lane >> 4;
-    const int ntile = a.tiles_x * a.tiles_y, total_tiles = a.N * ntile, G = gridDim.x;
-    unsigned char* wl = smem + P32_TABLE_BYTES;
-    unsigned char* patch = wl + (WLDS ? (size_t)p.nsteps * NF * 1024 : 0);
-    if (tid < P32_MAX_STEPS) {
-        reinterpret_cast<unsigned*>(smem)[tid] = p.koff[tid];
-    } else if (tid < P32_MAX_STEPS + P32_MAX_SEG) {
-        const int c = tid - P32_MAX_STEPS;
-        int* e = reinterpret_cast<int*>(smem + 4 * P32_MAX_STEPS + 16 * c);
-        e[0] = p.seg[c].s0; e[1] = p.seg[c].s1; e[2] = p.seg[c].oy; e[3] = p.seg[c].ox;
-    }
-    if (WLDS) {
-        const int nchunk = p.nsteps * NF * 64;
-        for (int e = tid; e < nchunk; e += 256) reinterpret_cast<f32x4*>(wl)[e] = reinterpret_cast<const f32x4*>(a.wpk)[e];
-    }
-    const f32x4* wglob = reinterpret_cast<const f32x4*>(a.wpk) + lane;  // static address spaces: no flat loads
-    const unsigned char* wlds_lane = wl + 16 * lane;
-    const int nseg = p.nseg, up = p.up;
-    unsigned base[RPW];
-#pragma unroll
-    for (int r = 0; r < RPW; ++r) base[r] = (unsigned)(((RPW * wv + r) * p.stride * p.PW + nl * p.stride) * p.pixstride + 16 * g);
-    f32x4 b4[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) b4[f] = *reinterpret_cast<const f32x4*>(a.bias + 16 * f + 4 * g);
+#define P32_BX blockIdx.x
+#define P32_NWG gridDim.x
+#include "conv_p32_body.h"
+#undef P32_BX
+#undef P32_NWG
+}
 
-    // what a thread stages is the same for every tile: element k of thread tid = channel quad o of patch pixel (r, c)
-    const int quads = a.Cin >> 2, o = tid & (quads - 1), sh = quads == 4 ? 2 : (quads == 8 ? 3 : 4);
-    unsigned rel[NPF], vmask = 0;
-    {
-        const int total = p.PH * p.PW * quads;
-#pragma unroll
-        for (int k = 0; k < NPF; ++k) {
-            const int e = 256 * k + tid, pix = e >> sh;
-            const int r = (int)__umulhi((unsigned)pix, p.m_pw), c = pix - r * p.PW;
-            if (e < total) vmask |= 1u << k;
-            rel[k] = (unsigned)(((r * a.W + c) * a.Cin + 4 * o) * 4);
-        }
-    }
-    float ssum[STATS ? NF : 1][4], ssq[STATS ? NF : 1][4];
-#pragma unroll
-    for (int f = 0; f < (STATS ? NF : 1); ++f)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ssum[f][q] = ssq[f][q] = 0.f;
-    const int lb = STATS ? xcd_swizzle((int)blockIdx.x, G) : (int)blockIdx.x;  // logical index of this workgroup's tile range (below)
-    auto flush_stats = [&](int n_img) {  // between tiles only (the scratch aliases the patch); ends with a barrier
-        float* red = reinterpret_cast<float*>(patch);  // [4 waves][2][16 * NF]
-#pragma unroll
-        for (int f = 0; f < (STATS ? NF : 1); ++f)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float s1 = row16_sum(ssum[f][q]), s2 = row16_sum(ssq[f][q]);
-                if (nl == 0) {
-                    red[(wv * 2 + 0) * 16 * NF + 16 * f + 4 * g + q] = s1;
-                    red[(wv * 2 + 1) * 16 * NF + 16 * f + 4 * g + q] = s2;
-                }
-                ssum[f][q] = ssq[f][q] = 0.f;
-            }
-        __syncthreads();
-        if (tid < 2 * 16 * NF)
-            a.partial[((size_t)n_img * G + lb) * 2 * 16 * NF + tid] = red[tid] + red[2 * 16 * NF + tid] + red[4 * 16 * NF + tid] + red[6 * 16 * NF + tid];
-        __syncthreads();
-    };
-    int cur_n = -1;
-    f32x4 amu[STATS == 2 ? NF : 1], ars[STATS == 2 ? NF : 1];  // STATS == 2: (mean, rstd) of the lane's output channels, image cur_n
-    float nsc[4], nnb[4];  // in_stats: (rstd, mean) of this thread's channel quad of image cur_in
-    int cur_in = -1;
-    const size_t out_row = (size_t)(up ? 2 : 1) * a.Wo * a.Cout * 4;  // bytes between this wave's consecutive rows
-    P32Regs<NPF> R;
-    int it = 0;
-    // STATS: a workgroup takes a CONTIGUOUS range of tiles, so that an image is covered by a few workgroups and the statistics
-    // finalize reads a few rows per image (with the strided order every workgroup touches every image: a row per pair, a memset and a
-    // finalize that cost what the statistics pass they replace costs); otherwise the strided, XCD-contiguous order
-    // ... and the ranges are dealt XCD-aware: workgroups b and b + 8 share an XCD (and its L2), so the logical range index is the
-    // XCD-contiguous renumbering of the block index -- the ranges one L2 serves at a time are then neighbours (shared halo rows)
-    const int chunk = STATS ? (total_tiles + G - 1) / G : 0;
-    const int t_end = STATS ? min(total_tiles, (lb + 1) * chunk) : total_tiles;
-    auto tile_of = [&](int i) { return STATS ? lb * chunk + i : p32_tile(i, blockIdx.x, G); };
-    int t = tile_of(it);
-    if (t < t_end) p32_fetch<NPF>(a, p, t, TH, tid, rel, vmask, R);
-    while (t < t_end) {
-        const int n = ntile == 1 ? t : (int)__umulhi((unsigned)t, p.m_ntile), tt = t - n * ntile;
-        const int ty = a.tiles_x == 1 ? tt : (int)__umulhi((unsigned)tt, p.m_tx), tx = tt - ty * a.tiles_x;
-        const int gy0 = ty * TH, gx0 = tx * P32_TW;
-        if (STATS && n != cur_n) {
-            if (cur_n >= 0) flush_stats(cur_n);
-            cur_n = n;
-            if (STATS == 2) {
-#pragma unroll
-                for (int f = 0; f < (STATS == 2 ? NF : 1); ++f) {
-                    const float* st = a.aux_stats + ((size_t)n * a.Cout + 16 * f + 4 * g) * 2;
-                    const f32x4 s0 = *reinterpret_cast<const f32x4*>(st), s1_ = *reinterpret_cast<const f32x4*>(st + 4);
-                    amu[f] = f32x4{s0[0], s0[2], s1_[0], s1_[2]};
-                    ars[f] = f32x4{s0[1], s0[3], s1_[1], s1_[3]};
-                }
-            }
-        }
-        if (a.in_stats && n != cur_in) {
-            const float* st = a.in_stats + ((size_t)n * a.Cin + 4 * o) * 2;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { nsc[c] = st[2 * c + 1]; nnb[c] = st[2 * c]; }
-            cur_in = n;
-        }
-#pragma unroll
-        for (int k = 0; k < NPF; ++k)
-            if (((vmask >> k) & 1) && !(a.dbg & 8)) {
-                f32x4 w = R.v[k];
-                if (a.in_stats) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) w[c] = fmaxf((w[c] - nnb[c]) * nsc[c], 0.f);  // norm_apply_kernel's arithmetic, bit for bit
-                }
-                if (!((R.okmask >> k) & 1)) w = f32x4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<f32x4*>(patch + (unsigned)(((256 * k + tid) >> sh) * p.pixstride + 16 * o)) = w;
-            }
-        __syncthreads();
-        const int tnext = tile_of(it + 1);
-        if (tnext < t_end && !(a.dbg & 4)) p32_fetch<NPF>(a, p, tnext, TH, tid, rel, vmask, R);
-
-        for (int sg = 0; sg < nseg; ++sg) {
-            const int4 ci = *reinterpret_cast<const int4*>(smem + 4 * P32_MAX_STEPS + 16 * sg);
-            const int s0 = __builtin_amdgcn_readfirstlane(ci.x), s1 = __builtin_amdgcn_readfirstlane(ci.y);
-            const int oyc = __builtin_amdgcn_readfirstlane(ci.z), oxc = __builtin_amdgcn_readfirstlane(ci.w);
-            f32x4 acc[RPW][NF];
-            // STATS == 2: the raw tensor at the pixels this segment will store, in flight behind the whole K loop
-            const int mul = up ? 2 : 1;
-            const bool full_tile = gy0 + TH <= a.Gh && gx0 + P32_TW <= a.Gw && (a.Cout & 15) == 0;
-            const size_t ybyte = ((((size_t)n * a.Ho + gy0 * mul + oyc) * a.Wo + gx0 * mul + oxc) * a.Cout) * 4;
-            const unsigned out_off0 = (unsigned)(((RPW * wv * mul) * a.Wo + nl * mul) * a.Cout + 4 * g) * 4u;
-            f32x4 av[STATS == 2 ? RPW : 1][STATS == 2 ? NF : 1];
-            if (STATS == 2 && full_tile && !(a.dbg & 2)) {
-                const char* abase = reinterpret_cast<const char*>(a.aux) + ybyte;
-#pragma unroll
-                for (int r = 0; r < RPW; ++r)
-#pragma unroll
-                    for (int f = 0; f < NF; ++f) av[STATS == 2 ? r : 0][STATS == 2 ? f : 0] = *reinterpret_cast<const f32x4*>(abase + r * out_row + out_off0 + 64 * f);
-            }
-            auto load_ko = [&](int s) -> unsigned { return reinterpret_cast<const unsigned*>(smem)[s]; };
-            auto load_ops = [&](unsigned ko, int s, f32x4 (&bf)[RPW], f32x4 (&af)[NF]) {
-#pragma unroll
-                for (int r = 0; r < RPW; ++r) bf[r] = *reinterpret_cast<const f32x4*>(patch + base[r] + ko);
-#pragma unroll
-                for (int f = 0; f < NF; ++f) {
-                    if (WLDS) af[f] = *reinterpret_cast<const f32x4*>(wlds_lane + (size_t)(s * NF + f) * 1024);
-                    else af[f] = wglob[(size_t)(s * NF + f) * 64];
-                }
-            };
-            auto mma_step = [&](const f32x4 (&bf)[RPW], const f32x4 (&af)[NF], auto from_bias) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int f = 0; f < NF; ++f)
-#pragma unroll
-                        for (int r = 0; r < RPW; ++r)
-                            acc[r][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[f][j], bf[r][j],
-                                                                             (decltype(from_bias)::value && j == 0) ? b4[f] : acc[r][f], 0, 0, 0);
-            };
-            auto clip = [&](int s) { return s < s1 ? s : s1 - 1; };  // past the end: re-read the last step (loaded, never used)
-            f32x4 bA[RPW], aA[NF], bB[RPW], aB[NF];
-            unsigned k0 = load_ko(s0), k1 = load_ko(clip(s0 + 1));
-            load_ops(k0, s0, bA, aA);
-            k0 = load_ko(clip(s0 + 2));
-            load_ops(k1, clip(s0 + 1), bB, aB);
-            mma_step(bA, aA, P32True{});  // accumulators start from the bias (the MFMA's C operand)
-            int s = s0 + 1;  // invariant: B holds the operands of step s (if s < s1), k0 the offset of step s + 1
-            if (a.dbg & 1) s = s1;  // experiments (MSTG_P32_DBG): 1 one K-step only, 2 no stores, 4 no patch fetch, 8 no patch commit
-            for (; s + 1 < s1; s += 2) {
-                k1 = load_ko(clip(s + 2));
-                load_ops(k0, s + 1, bA, aA);
-                mma_step(bB, aB, P32False{});
-                k0 = load_ko(clip(s + 3));
-                load_ops(k1, clip(s + 2), bB, aB);
-                mma_step(bA, aA, P32False{});
-            }
-            if (s < s1) mma_step(bB, aB, P32False{});
-            // ---- epilogue of this class: lane holds output channels 16f + 4g + {0..3} of compute-grid pixel (gy, gx0 + nl) --------
-            if (a.dbg & 2) continue;
-            if (full_tile) {
-                char* ybase = reinterpret_cast<char*>(a.y) + ybyte;
-#pragma unroll
-                for (int r = 0; r < RPW; ++r)
-#pragma unroll
-                    for (int f = 0; f < NF; ++f) {
-                        if (STATS == 1) {
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) { const float dv = acc[r][f][q] - b4[f][q]; ssum[f][q] += dv; ssq[f][q] += dv * dv; }  // pivot = the channel's bias
-                        }
-                        *reinterpret_cast<f32x4*>(ybase + r * out_row + out_off0 + 64 * f) = acc[r][f];
-                    }
-                if (STATS == 2) {
-#pragma unroll
-                    for (int r = 0; r < RPW; ++r)
-#pragma unroll
-                        for (int f = 0; f < NF; ++f) {
-                            const f32x4 xh = (av[STATS == 2 ? r : 0][STATS == 2 ? f : 0] - amu[STATS == 2 ? f : 0]) * ars[STATS == 2 ? f : 0];  // norm_partial_kernel<true>'s arithmetic
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const float gg = xh[q] > 0.f ? acc[r][f][q] : 0.f;
-                                ssum[f][q] += gg;
-                                ssq[f][q] += gg * xh[q];
-                            }
-                        }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < RPW; ++r) {
-                    const int gy = gy0 + RPW * wv + r, gx = gx0 + nl;
-                    if (gy < a.Gh && gx < a.Gw) {
-                        const int oy = gy * mul + oyc, ox = gx * mul + oxc;
-#pragma unroll
-                        for (int f = 0; f < NF; ++f)
-                            if (16 * f + 4 * g < a.Cout) {
-                                const size_t oe = (((size_t)n * a.Ho + oy) * a.Wo + ox) * a.Cout + 16 * f + 4 * g;
-                                if (STATS == 1) {
-#pragma unroll
-                                    for (int q = 0; q < 4; ++q) { const float dv = acc[r][f][q] - b4[f][q]; ssum[f][q] += dv; ssq[f][q] += dv * dv; }  // pivot = the channel's bias
-                                }
-                                if (STATS == 2) {
-                                    const f32x4 xh = (*reinterpret_cast<const f32x4*>(a.aux + oe) - amu[STATS == 2 ? f : 0]) * ars[STATS == 2 ? f : 0];
-#pragma unroll
-                                    for (int q = 0; q < 4; ++q) {
-                                        const float gg = xh[q] > 0.f ? acc[r][f][q] : 0.f;
-                                        ssum[f][q] += gg;
-                                        ssq[f][q] += gg * xh[q];
-                                    }
-                                }
-                                *reinterpret_cast<f32x4*>(a.y + oe) = acc[r][f];
-                            }
-                    }
-                }
-            }
-        }
-        __syncthreads();  // every wave is done with the patch
-        ++it;
-        t = tnext;
-    }
-    if (STATS && cur_n >= 0) flush_stats(cur_n);
+// G copies of conv_p32_kernel<.., 0> in one grid (ConvGroups, igemm_args.h): the occupancy-sized grid is split among the groups, each
+// share a multiple of eight persistent workgroups that walk the group's tiles as the whole grid walks them in a single launch.
+template <int RPW, int NF, int NPF, bool WLDS>
+__global__ __launch_bounds__(256) void conv_p32_grouped_kernel(const P32Args a0, const P32Plan p, const ConvGroups gs) {
+    constexpr int STATS = 0;
+    const int grp = (int)blockIdx.x / gs.bpg, bx = (int)blockIdx.x - grp * gs.bpg;
+    P32Args a = a0;
+    a.x = group_pick(gs.x, grp);
+    a.y = group_pick(gs.y, grp);
+    a.wpk = group_pick(gs.w, grp);
+    a.bias = group_pick(gs.bias, grp);
+#define P32_BX bx
+#define P32_NWG gs.bpg
+#include "conv_p32_body.h"
+#undef P32_BX
+#undef P32_NWG
 }
 
 // partial [N][G][2][CP] -> stats [N][C][2] = (mean, rstd); one workgroup per image, double accumulation, fixed order
@@ -778,9 +578,9 @@ static int launch_p32d(const IGemmArgs& g, const P32Route& r, void* workspace, s
 // workgroup owns one output row, thread (ox, tap) takes the dot product over the channels of its tap (filter transposed into
 // LDS), and the taps are summed in a fixed order: ~2000 multiply-adds per output, a few microseconds.
 // -------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void conv_co1_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                       float* __restrict__ y, int H, int W, int Cr, int Ho, int Wo, int KH, int KW, int pad,
-                                                       int w_sr) {
+__device__ __forceinline__ void conv_co1_body(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                              float* __restrict__ y, int H, int W, int Cr, int Ho, int Wo, int KH, int KW, int pad, int w_sr,
+                                              int oy, int n) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int T = KH * KW, tid = threadIdx.x;
     float* wl = sm;            // [T][Cr]
@@ -790,7 +590,6 @@ __global__ __launch_bounds__(256) void conv_co1_kernel(const float* __restrict__
         wl[e] = w[(size_t)ci * w_sr + t];
     }
     __syncthreads();
-    const int oy = blockIdx.x, n = blockIdx.y;
     const int per = 256 / T, t = tid % T, slot = tid / T, ky = t / KW, kx = t - ky * KW;
     const float b = bias ? bias[0] : 0.f;
     for (int ox0 = 0; ox0 < Wo; ox0 += per) {
@@ -815,6 +614,20 @@ __global__ __launch_bounds__(256) void conv_co1_kernel(const float* __restrict__
     }
 }
 
+__global__ __launch_bounds__(256) void conv_co1_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                       float* __restrict__ y, int H, int W, int Cr, int Ho, int Wo, int KH, int KW, int pad,
+                                                       int w_sr) {
+    conv_co1_body(x, w, bias, y, H, W, Cr, Ho, Wo, KH, KW, pad, w_sr, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// G copies of the launch above in one grid: blockIdx.y = group * N + image of the group (ConvGroups, igemm_args.h; bpg = N)
+__global__ __launch_bounds__(256) void conv_co1_grouped_kernel(const ConvGroups gs, int H, int W, int Cr, int Ho, int Wo, int KH, int KW, int pad,
+                                                               int w_sr) {
+    const int grp = (int)blockIdx.y / gs.bpg, n = (int)blockIdx.y - grp * gs.bpg;
+    conv_co1_body(group_pick(gs.x, grp), group_pick(gs.w, grp), group_pick(gs.bias, grp), group_pick(gs.y, grp), H, W, Cr, Ho, Wo, KH, KW, pad,
+                  w_sr, (int)blockIdx.x, n);
+}
+
 static bool co1_eligible(const IGemmArgs& a) {
     return a.Co == 1 && a.y_ctot == 1 && a.y_coff == 0 && !a.x_nchw && a.x_coff == 0 && a.x_ctot == a.Cr && (a.Cr & 3) == 0 && a.Cr >= 16 &&
            a.stride == 1 && a.dil == 1 && !a.phase && !a.flip && !a.accumulate && a.act == MSTG_ACT_NONE && a.KH * a.KW <= 16 &&
@@ -826,6 +639,15 @@ static int launch_co1(const IGemmArgs& a, hipStream_t st) {
     MSTG_LAUNCH(conv_co1_kernel, dim3(a.Ho, a.N), dim3(256), lds, st, a.x, a.w, a.bias, a.y, a.H, a.W, a.Cr, a.Ho, a.Wo, a.KH, a.KW,
                        a.pad, a.w_sr);
     MSTG_CHECK_LAUNCH("conv_co1_kernel");
+    return MSTG_OK;
+}
+
+static int launch_co1_grouped(const IGemmArgs& a, ConvGroups gs, hipStream_t st) {
+    if ((long)a.N * gs.G > 65535) return fail_arg(MSTG_E_UNSUPPORTED, "conv_co1 grouped: more than 65535 images in one grid");
+    const size_t lds = (size_t)(a.KH * a.KW * a.Cr + 256) * sizeof(float);
+    gs.bpg = a.N;  // no packed filter: the kernel transposes the module's own (gs.w)
+    MSTG_LAUNCH(conv_co1_grouped_kernel, dim3(a.Ho, a.N * gs.G), dim3(256), lds, st, gs, a.H, a.W, a.Cr, a.Ho, a.Wo, a.KH, a.KW, a.pad, a.w_sr);
+    MSTG_CHECK_LAUNCH("conv_co1_grouped_kernel");
     return MSTG_OK;
 }
 
@@ -1079,6 +901,77 @@ int launch_p32(const IGemmArgs& g, const P32Route& r, const float* in_stats, flo
     MSTG_P32_CASE(1, 4) MSTG_P32_CASE(2, 4)
 #undef MSTG_P32_CASE
     return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32: no kernel variant");
+}
+
+// ---- grouped launches (mstg_conv2d_fwd_grouped / _dgrad_grouped): P32_CO1 and P32_GENERIC without an epilogue ---------------------
+template <int RPW, int NF, int NPF>
+static int p32_launch_grouped_t(P32Args& a, const P32Plan& p, ConvGroups gs, size_t lds, long tiles, hipStream_t st) {
+    auto kern = p.wlds ? conv_p32_grouped_kernel<RPW, NF, NPF, true> : conv_p32_grouped_kernel<RPW, NF, NPF, false>;
+    static OccCache occ_tab[2];
+    int c_occ = persistent_occupancy(occ_tab[p.wlds ? 1 : 0], reinterpret_cast<const void*>(kern), lds);
+    { const char* e = env_get(ENV_P32_OCC); if (e && atoi(e) >= 1 && atoi(e) < c_occ) c_occ = atoi(e); }
+    // the occupancy-sized grid, split among the groups: a multiple of eight workgroups each (p32_tile's XCD order), at least eight
+    long share = ((256L * c_occ) / gs.G) & ~7L;
+    if (share < 8) share = 8;
+    if (share > tiles) share = (tiles + 7) & ~7L;
+    gs.bpg = (int)share;
+    MSTG_LAUNCH(kern, dim3((unsigned)(share * gs.G)), dim3(256), lds, st, a, p, gs);
+    MSTG_CHECK_LAUNCH("conv_p32_grouped_kernel");
+    return MSTG_OK;
+}
+
+template <int RPW, int NF>
+static int p32_launch_grouped_npf(P32Args& a, const P32Plan& p, const ConvGroups& gs, size_t lds, long tiles, hipStream_t st) {
+    const int regs = p32_npf_regs(p);
+    if (regs == 6) return p32_launch_grouped_t<RPW, NF, 6>(a, p, gs, lds, tiles, st);
+    if (regs == 8) return p32_launch_grouped_t<RPW, NF, 8>(a, p, gs, lds, tiles, st);
+    return p32_launch_grouped_t<RPW, NF, 12>(a, p, gs, lds, tiles, st);
+}
+
+// g: one group's gather (g.x / g.y / g.w / g.bias unused); gs: the groups' pointers, w and bias the modules' own; group k's workspace
+// is the ws_stride bytes (a multiple of 16, >= r.pack_bytes) at workspace + k * ws_stride
+int launch_p32_grouped(const IGemmArgs& g, const P32Route& r, ConvGroups gs, void* workspace, size_t ws_stride, hipStream_t st) {
+    if (r.kind == P32_CO1) return launch_co1_grouped(g, gs, st);
+    if (r.kind != P32_GENERIC) return fail_arg(MSTG_E_UNSUPPORTED, "conv grouped: this layer's kernel takes one group per launch");
+    P32Plan p = r.plan;
+    if (!workspace || ws_stride < r.pack_bytes || (ws_stride & 15)) return fail_arg(MSTG_E_WORKSPACE, "conv_p32 grouped: workspace too small for the packed filters");
+    P32Args a;
+    a.in_stats = nullptr; a.aux = nullptr; a.aux_stats = nullptr; a.partial = nullptr;
+    a.x = nullptr; a.y = nullptr; a.bias = nullptr; a.wpk = nullptr;  // per group: ConvGroups
+    a.N = g.N; a.H = g.H; a.W = g.W; a.Cin = g.Cr; a.Ho = g.Ho; a.Wo = g.Wo; a.Cout = g.Co;
+    a.Gh = p.up ? g.H : g.Ho;
+    a.Gw = p.up ? g.W : g.Wo;
+    a.tiles_y = cdiv(a.Gh, p.TH);
+    a.tiles_x = cdiv(a.Gw, P32_TW);
+    { const char* e = env_get(ENV_P32_DBG); a.dbg = e ? atoi(e) : 0; }
+    const long tiles = (long)a.N * a.tiles_x * a.tiles_y;
+    if ((unsigned long long)(tiles + 4096) * (unsigned long long)(a.tiles_x * a.tiles_y) >= (1ull << 32) || (size_t)g.H * g.W * g.Cr * 4 >= (1ull << 32))
+        return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32: tensor too large for the 32-bit tile / offset arithmetic");
+    p.m_ntile = magic_u32((unsigned)(a.tiles_x * a.tiles_y));
+    p.m_tx = magic_u32((unsigned)a.tiles_x);
+    MSTG_PACK_LAUNCH(p32_pack_grouped_kernel, dim3(32, gs.G), dim3(256), 0, st, p, gs, g.w_so, g.w_sr, g.Co, g.Cr, (float*)workspace, ws_stride / 4);
+    MSTG_CHECK_LAUNCH("p32_pack_grouped_kernel");
+    for (int k = 0; k < gs.G; ++k) {  // the main kernel reads what the pack wrote
+        gs.bias[k] = (const float*)((const char*)workspace + (size_t)k * ws_stride);
+        gs.w[k] = gs.bias[k] + 64;
+    }
+    size_t lds = P32_TABLE_BYTES + (size_t)p.PH * p.PW * p.pixstride + (p.wlds ? (size_t)p.nsteps * p.NF * 1024 : 0);
+    lds = (lds + 15) & ~(size_t)15;
+#define MSTG_P32_CASE(R_, F_) if (p.TH == 4 * R_ && p.NF == F_) return p32_launch_grouped_npf<R_, F_>(a, p, gs, lds, tiles, st);
+    MSTG_P32_CASE(1, 1) MSTG_P32_CASE(2, 1) MSTG_P32_CASE(4, 1)
+    MSTG_P32_CASE(1, 2) MSTG_P32_CASE(2, 2) MSTG_P32_CASE(4, 2)
+    MSTG_P32_CASE(1, 4) MSTG_P32_CASE(2, 4)
+#undef MSTG_P32_CASE
+    return fail_arg(MSTG_E_UNSUPPORTED, "conv_p32: no kernel variant");
+}
+
+const char* p32_grouped_kernel_name(const P32Route& r) {
+    static thread_local char name[64];
+    if (r.kind == P32_CO1) return "conv_co1_grouped_kernel";
+    if (r.kind != P32_GENERIC) return "";
+    snprintf(name, sizeof(name), "conv_p32_grouped_kernel<%d, %d, %d, %s>", r.plan.TH / 4, r.plan.NF, p32_npf_regs(r.plan),
+             r.plan.wlds ? "true" : "false");
+    return name;
 }
 
 const char* p32_kernel_name(const P32Route& r, int stats) {

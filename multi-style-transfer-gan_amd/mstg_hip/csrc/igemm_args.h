@@ -30,6 +30,23 @@ struct IGemmArgs {
     int dpack, tapsx;  // <= 4 output channels: rows of the MFMA tile = (pixel shift delta, channel), see igemm_light_kernel
 };
 
+// Grouped launch (mstg_conv2d_fwd_grouped / _dgrad_grouped): G copies of one planned launch in one grid, each with its own source,
+// destination, filter and bias.  Workgroup bx of the grid's x dimension belongs to group bx / bpg and is workgroup bx % bpg of that
+// group's copy; everything else (tiles, channel blocks, parity classes) is the single-group plan.
+constexpr int CONV_GROUP_MAX = 4;
+struct ConvGroups {
+    const float* x[CONV_GROUP_MAX];
+    float* y[CONV_GROUP_MAX];
+    const float* w[CONV_GROUP_MAX];     // the module's filter (pack kernels) or the group's packed filter (main kernels)
+    const float* bias[CONV_GROUP_MAX];
+    int G, bpg;
+};
+// pointer of group g: a select chain over direct kernel arguments (an indexed load would hide the address space from the compiler)
+template <typename T>
+__host__ __device__ __forceinline__ T group_pick(const T (&p)[CONV_GROUP_MAX], int g) {
+    return g == 0 ? p[0] : (g == 1 ? p[1] : (g == 2 ? p[2] : p[3]));
+}
+
 // conv_p32.hip: persistent, software-pipelined kernel for the 4x4 stride-2 family (Conv2d k4 s2 p1, ConvTranspose2d k4 s2 p1 and
 // their input gradients) and 1x1 convolutions at 16 / 32 / 64 channels, plus three special-case kernels
 constexpr int P32_MAX_STEPS = 64;
@@ -78,9 +95,14 @@ P32Route p32_route(const IGemmArgs& a);
 int launch_p32(const IGemmArgs& a, const P32Route& r, const float* in_stats, float* out_stats, const float* aux, const float* aux_stats,
                void* workspace, size_t workspace_bytes, hipStream_t st);
 const char* p32_kernel_name(const P32Route& r, int stats);  // stats: the generic kernel's STATS argument (0 = no epilogue)
+// Grouped launch of P32_CO1 / P32_GENERIC (no epilogue): a = one group's gather, gs = the groups' pointers (w, bias: the modules' own),
+// group k's workspace = ws_stride bytes at workspace + k * ws_stride.  MSTG_E_UNSUPPORTED for the other kinds.
+int launch_p32_grouped(const IGemmArgs& a, const P32Route& r, ConvGroups gs, void* workspace, size_t ws_stride, hipStream_t st);
+const char* p32_grouped_kernel_name(const P32Route& r);  // "" where launch_p32_grouped does not run
 
 // conv_img.hip: input gradient of the discriminator's image-side layer, Conv2d(3, C, 4, 2, 1) on the NCHW image, on the vector pipe
 bool img_dgrad_eligible(const IGemmArgs& a);
 int launch_img_dgrad(const IGemmArgs& a, hipStream_t st);
+int launch_img_dgrad_grouped(const IGemmArgs& a, ConvGroups gs, hipStream_t st);  // gs.x = dy, gs.y = dx, gs.w = the modules' filters
 
 }  // namespace mstg

@@ -353,21 +353,31 @@ static int norm_check(int N, int HW, int C) {
 
 using namespace mstg;
 
-extern "C" size_t mstg_norm_workspace_bytes(int N, int HW, int C) {
-    if (N <= 0 || HW <= 0 || C <= 0) return 0;
-    const NormGeom g = norm_geom(N, HW, C);
+// N images laid out by the row split norm_geom gives a batch of plan_N (the plain entry points: plan_N = N)
+static NormGeom norm_geom_plan(int N, int plan_N, int HW, int C) {
+    NormGeom g = norm_geom(plan_N, HW, C);
+    g.N = N;
+    return g;
+}
+
+static size_t norm_ws_bytes(int N, int plan_N, int HW, int C) {
+    if (N <= 0 || plan_N <= 0 || HW <= 0 || C <= 0) return 0;
+    const NormGeom g = norm_geom_plan(N, plan_N, HW, C);
     return ((size_t)N * g.split * 2 * C + (size_t)N * 2 * C) * sizeof(float);  // partial rows + one summed row per image
 }
 
-extern "C" int mstg_norm_act_fwd(const float* x, const float* residual, float* y, float* stats, int N, int HW, int C, int act,
-                                 int batch_stats, const float* gamma, const float* beta, float* running_mean,
-                                 float* running_var, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" size_t mstg_norm_workspace_bytes(int N, int HW, int C) { return norm_ws_bytes(N, N, HW, C); }
+extern "C" size_t mstg_norm_workspace_bytes_plan(int N, int plan_N, int HW, int C) { return norm_ws_bytes(N, plan_N, HW, C); }
+
+static int norm_act_fwd_impl(const float* x, const float* residual, float* y, float* stats, int N, int plan_N, int HW, int C, int act,
+                             int batch_stats, const float* gamma, const float* beta, float* running_mean,
+                             float* running_var, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = norm_check(N, HW, C)) return rc;
     if (!x || !y || !stats || !workspace) return fail_arg(MSTG_E_BADARG, "norm_fwd: null pointer");
     if (batch_stats && (!gamma || !beta || !running_mean || !running_var)) return fail_arg(MSTG_E_BADARG, "norm_fwd: batch norm needs gamma/beta/running stats");
     if (act == MSTG_ACT_TANH) return fail_arg(MSTG_E_UNSUPPORTED, "norm_fwd: tanh epilogue not supported");
-    const NormGeom g = norm_geom(N, HW, C);
-    if (workspace_bytes < mstg_norm_workspace_bytes(N, HW, C)) return fail_arg(MSTG_E_WORKSPACE, "norm_fwd: workspace too small");
+    const NormGeom g = norm_geom_plan(N, plan_N, HW, C);
+    if (workspace_bytes < norm_ws_bytes(N, plan_N, HW, C)) return fail_arg(MSTG_E_WORKSPACE, "norm_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int rows = 256 / (C / 4);
     dim3 grid(g.split, N);
@@ -394,15 +404,31 @@ extern "C" int mstg_norm_act_fwd(const float* x, const float* residual, float* y
     return MSTG_OK;
 }
 
-extern "C" int mstg_norm_act_bwd(const float* x, const float* stats, const float* dy, float* dx, int N, int HW, int C, int act,
-                                 int batch_stats, const float* gamma, const float* beta, float* dgamma, float* dbeta,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int mstg_norm_act_fwd(const float* x, const float* residual, float* y, float* stats, int N, int HW, int C, int act,
+                                 int batch_stats, const float* gamma, const float* beta, float* running_mean,
+                                 float* running_var, void* workspace, size_t workspace_bytes, void* stream) {
+    return norm_act_fwd_impl(x, residual, y, stats, N, N, HW, C, act, batch_stats, gamma, beta, running_mean, running_var, workspace,
+                             workspace_bytes, stream);
+}
+
+// InstanceNorm over N = G * plan_N images with the row split of a batch of plan_N: every image gets the launch geometry, the partial
+// rows and the summation order it gets in a call of its own group of plan_N images, so the results are those calls', bit for bit
+extern "C" int mstg_norm_act_fwd_plan(const float* x, const float* residual, float* y, float* stats, int N, int plan_N, int HW, int C,
+                                      int act, void* workspace, size_t workspace_bytes, void* stream) {
+    if (plan_N <= 0) return fail_arg(MSTG_E_BADARG, "norm_fwd_plan: plan_N must be positive");
+    return norm_act_fwd_impl(x, residual, y, stats, N, plan_N, HW, C, act, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                             stream);
+}
+
+static int norm_act_bwd_impl(const float* x, const float* stats, const float* dy, float* dx, int N, int plan_N, int HW, int C, int act,
+                             int batch_stats, const float* gamma, const float* beta, float* dgamma, float* dbeta,
+                             void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = norm_check(N, HW, C)) return rc;
     if (!x || !stats || !dy || !dx || !workspace) return fail_arg(MSTG_E_BADARG, "norm_bwd: null pointer");
     if (batch_stats == 1 && (!gamma || !beta || !dgamma || !dbeta)) return fail_arg(MSTG_E_BADARG, "norm_bwd: batch norm needs gamma/beta/dgamma/dbeta");
     if (batch_stats == 2) return fail_arg(MSTG_E_UNSUPPORTED, "norm_bwd: eval-mode batch norm backward not implemented");
-    const NormGeom g = norm_geom(N, HW, C);
-    if (workspace_bytes < mstg_norm_workspace_bytes(N, HW, C)) return fail_arg(MSTG_E_WORKSPACE, "norm_bwd: workspace too small");
+    const NormGeom g = norm_geom_plan(N, plan_N, HW, C);
+    if (workspace_bytes < norm_ws_bytes(N, plan_N, HW, C)) return fail_arg(MSTG_E_WORKSPACE, "norm_bwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     const int rows = 256 / (C / 4);
     dim3 grid(g.split, N);
@@ -425,6 +451,18 @@ extern "C" int mstg_norm_act_bwd(const float* x, const float* stats, const float
                        batch_stats, g.split);
     MSTG_CHECK_LAUNCH("norm_apply_kernel<bwd>");
     return MSTG_OK;
+}
+
+extern "C" int mstg_norm_act_bwd(const float* x, const float* stats, const float* dy, float* dx, int N, int HW, int C, int act,
+                                 int batch_stats, const float* gamma, const float* beta, float* dgamma, float* dbeta,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    return norm_act_bwd_impl(x, stats, dy, dx, N, N, HW, C, act, batch_stats, gamma, beta, dgamma, dbeta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mstg_norm_act_bwd_plan(const float* x, const float* stats, const float* dy, float* dx, int N, int plan_N, int HW, int C,
+                                      int act, void* workspace, size_t workspace_bytes, void* stream) {
+    if (plan_N <= 0) return fail_arg(MSTG_E_BADARG, "norm_bwd_plan: plan_N must be positive");
+    return norm_act_bwd_impl(x, stats, dy, dx, N, plan_N, HW, C, act, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 // InstanceNorm statistics only: stats[n][c] = (mean, rstd).  For a norm whose consumer normalises while it loads

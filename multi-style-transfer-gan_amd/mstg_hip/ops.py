@@ -1356,6 +1356,247 @@ def spectral_norm_group(modules) -> None:
 
 
 # ----------------------------------------------------------------------------------------------------------
+# Grouped passes: G forwards of one layer, each with its own tensors and filter, as one launch chain
+# ----------------------------------------------------------------------------------------------------------
+def conv_group_max() -> int:
+    return int(_lib.load().mstg_conv2d_group_max())
+
+
+def _conv_grouped(pass_: int, d: ConvDesc, srcs, ws, bs, dsts) -> None:
+    """pass_ 0: dsts[g] = conv(srcs[g], ws[g]) + bs[g]; pass_ 1: dsts[g] = input gradient from srcs[g] = dy.  One grouped launch chain
+    (mstg_conv2d_fwd_grouped / _dgrad_grouped) where the layer's kernel has been taught the group index, else the G plain launches it
+    stands for: the same kernels, plans and arithmetic either way.  Every tensor is contiguous (slices of a batched buffer are)."""
+    lib = _lib.load()
+    G = len(srcs)
+    name = lib.mstg_conv2d_grouped_kernel_name(C.byref(d), pass_) if 1 < G <= lib.mstg_conv2d_group_max() else b""
+    if not name:
+        for g in range(G):
+            if pass_ == 0:
+                conv_fwd_raw(d, srcs[g], ws[g], None if bs is None else bs[g], dsts[g])
+            else:
+                conv_dgrad_raw(d, srcs[g], ws[g], dsts[g])
+        return
+    fl, by = _conv_cost(d)
+    wk = _ws(lib.mstg_conv2d_grouped_workspace_bytes(C.byref(d), G), srcs[0].device)
+    if pass_ == 0:
+        call = lambda: _lib.check(lib.mstg_conv2d_fwd_grouped(  # noqa: E731
+            C.byref(d), G, _ptr_array(srcs), _ptr_array(ws), None if bs is None or bs[0] is None else _ptr_array(bs), _ptr_array(dsts),
+            _p(wk), wk.numel() * 4, _stream()), "mstg_conv2d_fwd_grouped")
+    else:
+        call = lambda: _lib.check(lib.mstg_conv2d_dgrad_grouped(  # noqa: E731
+            C.byref(d), G, _ptr_array(srcs), _ptr_array(ws), _ptr_array(dsts), _p(wk), wk.numel() * 4, _stream()), "mstg_conv2d_dgrad_grouped")
+    _timed(name.decode(), G * fl, G * by, call, _conv_detail(("fwd" if pass_ == 0 else "dgrad") + f" x{G}", d))
+
+
+def norm_fwd_plan_raw(x, act, plan_N):
+    """act(InstanceNorm(x)) over x = (G * plan_N, H, W, C) with the row split of a plan_N-image call -> (y, stats)"""
+    lib = _lib.load()
+    N, H, W, Cn = x.shape
+    y = torch.empty_like(x)
+    stats = torch.empty((N, Cn, 2), dtype=torch.float32, device=x.device)
+    ws = _ws(lib.mstg_norm_workspace_bytes_plan(N, plan_N, H * W, Cn), x.device)
+    _timed("norm_apply_kernel<false>", 0, 4 * x.numel() * 2, lambda: _lib.check(
+        lib.mstg_norm_act_fwd_plan(_p(x), None, _p(y), _p(stats), N, plan_N, H * W, Cn, act, _p(ws), ws.numel() * 4, _stream()),
+        "mstg_norm_act_fwd_plan"))
+    return y, stats
+
+
+def norm_bwd_plan_raw(x, stats, dy, dx, act, plan_N) -> None:
+    lib = _lib.load()
+    N, H, W, Cn = x.shape
+    ws = _ws(lib.mstg_norm_workspace_bytes_plan(N, plan_N, H * W, Cn), x.device)
+    _timed("norm_apply_kernel<true>", 0, 4 * x.numel() * 3, lambda: _lib.check(
+        lib.mstg_norm_act_bwd_plan(_p(x), _p(stats), _p(dy), _p(dx), N, plan_N, H * W, Cn, act, _p(ws), ws.numel() * 4, _stream()),
+        "mstg_norm_act_bwd_plan"))
+
+
+def _runs(groups):
+    """[(first position, first group, count)] of the maximal runs of consecutive group numbers in the sorted list `groups`"""
+    out = []
+    for pos, g in enumerate(groups):
+        if out and out[-1][1] + out[-1][2] == g:
+            out[-1] = (out[-1][0], out[-1][1], out[-1][2] + 1)
+        else:
+            out.append((pos, g, 1))
+    return out
+
+
+class DiscriminatorGroupedFn(torch.autograd.Function):
+    """G forwards of one EnhancedDiscriminator (enhanced_generator.py:230-274), group g with its own image tensor and its own set of
+    seven normalised filters, as ONE pass over G * N images: apply(G, N, x_0 .. x_{G-1}, then per group its seven filters, then per
+    group the seven biases) -> (score_0, struct_0, score_1, struct_1, ...), score_g (N, 1) and struct_g (N, h, w, 1) NHWC.
+
+    Every op of the discriminator is per sample and the batch index is outermost in NHWC, so image range g of the batched activations
+    is exactly what forward g alone computes: the convolutions run as grouped launches planned for N images (_conv_grouped), the
+    norms with the row split of an N-image batch (norm_fwd_plan_raw), pooling and activations per image / per element.  The backward
+    is written out here instead of being left to per-op autograd nodes because liveness is per GROUP: a group whose outputs got no
+    gradient, or whose inputs need none, takes no part in it, and each head runs backward only on the groups whose output of that
+    head was used -- what the separate forwards' graphs do.  Per group the launches, plans and summation orders are those of
+    ConvFn / InstNormActFn / SpatialMeanFn, so results and gradients are bit for bit the sequential ones.  Weight and bias
+    gradients come back per group (wgrad on the group's slice), for autograd to hand to each filter set's SpectralNormGroupFn."""
+
+    LAYERS = ((4, 2, 1), (4, 2, 1), (4, 2, 1), (4, 2, 1), (4, 1, 1), (3, 1, 1), (4, 1, 1))  # (k, stride, pad): main 0 2 5 8, score, struct 0 3
+
+    @staticmethod
+    def forward(ctx, G, N, *tensors):
+        xs = [_req(t, "discriminator input") for t in tensors[:G]]
+        wts = [[_req(t, "discriminator filter") for t in tensors[G + 7 * g:G + 7 * g + 7]] for g in range(G)]
+        bss = [[_req(t, "discriminator bias") for t in tensors[8 * G + 7 * g:8 * G + 7 * g + 7]] for g in range(G)]
+        dev = xs[0].device
+        _, _, H, W = xs[0].shape
+        L = DiscriminatorGroupedFn.LAYERS
+
+        def conv(li, src, Hi, Wi, x_nchw=0, act=ACT_NONE):
+            k, s, p = L[li]
+            Cout, Cin = wts[0][li].shape[0], wts[0][li].shape[1]
+            Ho, Wo = conv_out_hw(Hi, Wi, k, s, p, 1, False)
+            if Ho <= 0 or Wo <= 0:
+                raise RuntimeError(f"mstg_hip conv: input {Hi}x{Wi} too small for kernel {k} (stride {s}, pad {p}, dil 1)")
+            y = torch.empty((G * N, Ho, Wo, Cout), dtype=torch.float32, device=dev)
+            d = make_desc(N, Hi, Wi, Cin, Ho, Wo, Cout, k, s, p, 1, 0, x_nchw, 0, act=act)
+            srcs = src if isinstance(src, list) else [src[g * N:(g + 1) * N] for g in range(G)]
+            _conv_grouped(0, d, srcs, [wts[g][li] for g in range(G)], [bss[g][li] for g in range(G)], [y[g * N:(g + 1) * N] for g in range(G)])
+            return y, Ho, Wo
+
+        h0, Hc, Wc = conv(0, xs, H, W, x_nchw=1, act=ACT_LEAKY02)
+        acts, raws, stats = [h0], [], []
+        for li in (1, 2, 3):
+            r, Hc, Wc = conv(li, acts[-1], Hc, Wc)
+            y, st = norm_fwd_plan_raw(r, ACT_LEAKY02, N)
+            raws.append(r), stats.append(st), acts.append(y)
+        h3 = acts[-1]
+        sc_map, Hs, Ws = conv(4, h3, Hc, Wc)
+        score = torch.empty((G * N, 1), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().mstg_segment_mean_fwd(_p(sc_map), G * N, Hs * Ws, 1, _p(score), _stream()), "mstg_segment_mean_fwd")
+        rs, _, _ = conv(5, h3, Hc, Wc)
+        s_act, s_stats = norm_fwd_plan_raw(rs, ACT_LEAKY02, N)
+        st_map, Ht, Wt = conv(6, s_act, Hc, Wc)
+        ctx.G, ctx.N, ctx.dims = G, N, (H, W, Hc, Wc, Hs, Ws, Ht, Wt)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*xs, *[w for g in range(G) for w in wts[g]], *acts, *raws, *stats, rs, s_act, s_stats)
+        outs = []
+        for g in range(G):
+            outs += [score[g * N:(g + 1) * N], st_map[g * N:(g + 1) * N]]
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        G, N = ctx.G, ctx.N
+        H, W, Hc, Wc, Hs, Ws, Ht, Wt = ctx.dims
+        sv = ctx.saved_tensors
+        xs, wflat = sv[:G], sv[G:8 * G]
+        wts = [wflat[7 * g:7 * g + 7] for g in range(G)]
+        acts, raws, stats = sv[8 * G:8 * G + 4], sv[8 * G + 4:8 * G + 7], sv[8 * G + 7:8 * G + 10]
+        rs, s_act, s_stats = sv[8 * G + 10:8 * G + 13]
+        dev = xs[0].device
+        L = DiscriminatorGroupedFn.LAYERS
+        need_x = [ctx.needs_input_grad[2 + g] for g in range(G)]
+        need_w = [ctx.needs_input_grad[2 + G + 7 * g] for g in range(G)]
+        d_sc = [grads[2 * g] for g in range(G)]
+        d_st = [grads[2 * g + 1] for g in range(G)]
+        live = [g for g in range(G) if (need_x[g] or need_w[g]) and (d_sc[g] is not None or d_st[g] is not None)]
+        out = [None] * (2 + 15 * G)
+        if not live:
+            return tuple(out)
+        pos = {g: i for i, g in enumerate(live)}
+
+        def rows(t, i):  # image range i of a batched tensor
+            return t[i * N:(i + 1) * N]
+
+        def gw_slot(g, li):
+            return 2 + G + 7 * g + li
+
+        def gb_slot(g, li):
+            return 2 + 8 * G + 7 * g + li
+
+        def conv_bwd(li, groups, x_of, dy_of, dx_of, Hi, Wi, x_nchw=0):
+            """input gradients of layer li for `groups` in one grouped launch (dx_of(g) None: that group wants none), weight and
+            bias gradients per group on its own slice (ConvFn.backward's launches)"""
+            k, s, p = L[li]
+            Cout, Cin = wts[0][li].shape[0], wts[0][li].shape[1]
+            Ho, Wo = conv_out_hw(Hi, Wi, k, s, p, 1, False)
+            d = make_desc(N, Hi, Wi, Cin, Ho, Wo, Cout, k, s, p, 1, 0, x_nchw, 0)
+            gx = [g for g in groups if dx_of(g) is not None]
+            if gx:
+                _conv_grouped(1, d, [dy_of(g) for g in gx], [wts[g][li] for g in gx], None, [dx_of(g) for g in gx])
+            for g in groups:
+                if need_w[g]:
+                    dw = torch.empty_like(wts[g][li])
+                    db = torch.empty(Cout, dtype=torch.float32, device=dev)
+                    conv_wgrad_raw(d, x_of(g), dy_of(g), dw, db)
+                    out[gw_slot(g, li)], out[gb_slot(g, li)] = dw, db
+
+        def norm_bwd(groups, x_raw, st, dy, dx):
+            """x_raw / st are indexed by group, dy / dx by position in `live`; one launch per run of consecutive groups"""
+            for p0, g0, cnt in _runs(groups):
+                i0 = pos[g0]
+                norm_bwd_plan_raw(x_raw[g0 * N:(g0 + cnt) * N], st[g0 * N:(g0 + cnt) * N], dy[i0 * N:(i0 + cnt) * N], dx[i0 * N:(i0 + cnt) * N],
+                                  ACT_LEAKY02, N)
+
+        h3 = acts[3]
+        C8 = h3.shape[3]
+        nl = len(live)
+        dh3 = torch.empty((nl * N, Hc, Wc, C8), dtype=torch.float32, device=dev)
+        # ---- structure head: conv(8C -> 1) <- LeakyReLU(InstanceNorm) <- conv(8C -> 8C)
+        g_st = [g for g in live if d_st[g] is not None]
+        if g_st:
+            dyt = {g: _req(d_st[g], "discriminator grad_output") for g in g_st}
+            ds = torch.empty((nl * N, Hc, Wc, C8), dtype=torch.float32, device=dev)
+            conv_bwd(6, g_st, lambda g: rows(s_act, g), lambda g: dyt[g], lambda g: rows(ds, pos[g]), Hc, Wc)
+            drs = torch.empty_like(ds)
+            norm_bwd(g_st, rs, s_stats, ds, drs)
+            conv_bwd(5, g_st, lambda g: rows(h3, g), lambda g: rows(drs, pos[g]), lambda g: rows(dh3, pos[g]), Hc, Wc)
+        # ---- score head: spatial mean <- conv(8C -> 1); a group with both heads live adds the two shares
+        g_sc = [g for g in live if d_sc[g] is not None]
+        if g_sc:
+            dmap = torch.empty((nl * N, Hs, Ws, 1), dtype=torch.float32, device=dev)
+            for g in g_sc:
+                dyg = _req(d_sc[g], "discriminator grad_output")
+                _lib.check(_lib.load().mstg_segment_mean_bwd(_p(dyg), N, Hs * Ws, 1, _p(rows(dmap, pos[g])), _stream()), "mstg_segment_mean_bwd")
+            both = [g for g in g_sc if d_st[g] is not None]
+            tmp = torch.empty((len(both) * N, Hc, Wc, C8), dtype=torch.float32, device=dev) if both else None
+            bpos = {g: i for i, g in enumerate(both)}
+            conv_bwd(4, g_sc, lambda g: rows(h3, g), lambda g: rows(dmap, pos[g]),
+                     lambda g: rows(tmp, bpos[g]) if g in bpos else rows(dh3, pos[g]), Hc, Wc)
+            for g in both:
+                a, b = rows(dh3, pos[g]), rows(tmp, bpos[g])
+                _lib.check(_lib.load().mstg_add(_p(a), _p(b), _p(a), a.numel(), _stream()), "mstg_add")
+        # ---- trunk: three (conv, InstanceNorm + LeakyReLU) stages, then the image-side convolution with its fused LeakyReLU
+        dh = dh3
+        sizes = [(H // 2, W // 2)]
+        for _ in range(3):
+            sizes.append((sizes[-1][0] // 2, sizes[-1][1] // 2))
+        for li in (3, 2, 1):
+            dr = torch.empty_like(dh)
+            norm_bwd(live, raws[li - 1], stats[li - 1], dh, dr)
+            Hi, Wi = sizes[li - 1]
+            prev = acts[li - 1]
+            dprev = torch.empty((nl * N,) + tuple(prev.shape[1:]), dtype=torch.float32, device=dev)
+            conv_bwd(li, live, lambda g, prev=prev: rows(prev, g), lambda g, dr=dr: rows(dr, pos[g]), lambda g, dprev=dprev: rows(dprev, pos[g]),
+                     Hi, Wi)
+            dh = dprev
+        h0 = acts[0]
+        dpre = torch.empty_like(dh)
+        for p0, g0, cnt in _runs(live):  # LeakyReLU'(pre) has the sign of y (ConvFn.backward)
+            i0 = pos[g0]
+            y_, dy_, dx_ = h0[g0 * N:(g0 + cnt) * N], dh[i0 * N:(i0 + cnt) * N], dpre[i0 * N:(i0 + cnt) * N]
+            _lib.check(_lib.load().mstg_act_bwd(_p(y_), _p(dy_), _p(dx_), dy_.numel(), ACT_LEAKY02, _stream()), "mstg_act_bwd")
+        dxs = {g: torch.empty_like(xs[g]) for g in live if need_x[g]}
+        conv_bwd(0, live, lambda g: xs[g], lambda g: rows(dpre, pos[g]), lambda g: dxs.get(g), H, W, x_nchw=1)
+        for g, t in dxs.items():
+            out[2 + g] = t
+        return tuple(out)
+
+
+def discriminator_grouped(xs, weight_sets, biases):
+    """xs: G image tensors (N, 3, H, W); weight_sets[g]: the seven normalised filters forward g reads (main 0 2 5 8, score head,
+    structure head 0 3); biases: the seven bias parameters -> [(score_g (N, 1), struct_g (N, h, w, 1))]"""
+    G, N = len(xs), xs[0].shape[0]
+    flat = DiscriminatorGroupedFn.apply(G, N, *xs, *[w for ws_ in weight_sets for w in ws_], *[b for _ in range(G) for b in biases])
+    return [(flat[2 * g], flat[2 * g + 1]) for g in range(G)]
+
+
+# ----------------------------------------------------------------------------------------------------------
 # build-defined StructuralTransformerBlock pieces (parity unpinned; see structural_transformer.py)
 # ----------------------------------------------------------------------------------------------------------
 def structure_map(img: Tensor) -> Tensor:
