@@ -482,6 +482,52 @@ int mstg_f16_train_adam(float* p, const float* g, float* m, float* v, size_t n, 
                         int step_base, const int* istate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixed-precision multi-style loss (csrc/style_f16.hip; style_loss.py precision="mixed"): the frozen VGG-topology stack, its
+ * max-pools and the Gram matrices with fp16 features in the forward and bf16 gradients in the backward, fp32 accumulation
+ * everywhere.  bf16 has fp32's exponent range, so the gradients (1e-7 and below) need no loss scale.  NHWC activations, 64-bit
+ * offsets, fixed summation order, no atomics, no split-K: two launches give the same bits, and image i of a batch equals the same
+ * image run alone.
+ * ---------------------------------------------------------------------------------------------- */
+#define MSTG_STYLE16_F16 0
+#define MSTG_STYLE16_BF16 1
+typedef struct mstg_style16_conv_desc {
+    int32_t dtype;        /* MSTG_STYLE16_F16 / _BF16: operands, the NHWC source and the NHWC destination */
+    int32_t N, H, W;      /* 3x3, stride 1, padding 1: the destination has the source's H and W; any N, H, W >= 1 */
+    int32_t Cin;          /* a multiple of 16 up to 512; 3 with src_nchw_f32 */
+    int32_t Cout;         /* a multiple of 16 up to 512; 3 with dst_nchw_f32 */
+    int32_t src_nchw_f32; /* 1: the stem reads the (N,3,H,W) fp32 image and rounds it to `dtype` while staging */
+    int32_t dst_nchw_f32; /* 1: the image gradient, written as (N,3,H,W) fp32 */
+    int32_t flip;         /* pack only. 0: w is this convolution's filter (Cout,Cin,3,3).  1: w is the filter (Cin,Cout,3,3) of the
+                           * layer whose INPUT gradient this convolution computes: read flipped and transposed */
+    int32_t relu;         /* 1: ReLU behind the bias */
+} mstg_style16_conv_desc;
+/* size of the packed filter (N, H, W are not read); 0 = unsupported, mstg_last_error() names the reason */
+size_t mstg_style16_conv_plan_bytes(const mstg_style16_conv_desc* d);
+/* the kernel variant (tile shape) a launch of d takes, e.g. "style_conv16_kernel<f16,2,4,0>" = <dtype, 64-pixel fragments rows per
+ * block / 64, 16-channel fragments per block, stem>; the launch reads the same choice.  nullptr = unsupported. */
+const char* mstg_style16_conv_kernel_name(const mstg_style16_conv_desc* d);
+/* w: fp32 (see flip), rounded once to `dtype`; bias: fp32 [Cout], nullable (zero) */
+int mstg_style16_conv_pack(const mstg_style16_conv_desc* d, const float* w, const float* bias, void* blob, size_t blob_bytes,
+                           void* stream);
+/* y = [mask > 0] * relu?(conv(x) + bias), rounded once.  mask (nullable): fp16 NHWC of the destination's shape -- the saved input
+ * activation of the layer whose input gradient this is; -0.0 and +0.0 both count as not > 0.  No mask with dst_nchw_f32. */
+int mstg_style16_conv_fwd(const mstg_style16_conv_desc* d, const void* blob, const void* x, const void* mask, void* y, void* stream);
+/* F.max_pool2d(x, 2) on fp16 NHWC, H and W even, C a multiple of 8; window order and first-maximum rule of mstg_maxpool2x2_fwd */
+int mstg_style16_maxpool_fwd(const void* x, void* y, unsigned char* idx, int N, int H, int W, int C, void* stream);
+/* dx (N,H,W,C) bf16 = dy (N,H/2,W/2,C) bf16 routed through idx; mask (nullable): fp16 (N,H,W,C), dx = 0 where mask is not > 0 */
+int mstg_style16_maxpool_bwd(const void* dy, const unsigned char* idx, const void* mask, void* dx, int N, int H, int W, int C,
+                             void* stream);
+/* G[n] = scale * F[n]^T F[n], F fp16 (N,HW,C), C a multiple of 16 up to 512, G fp32 (N,C,C); fixed-order slab reduction */
+size_t mstg_style16_gram_workspace_bytes(int N, int HW, int C);
+int mstg_style16_gram_fwd(const void* f, float* g, int N, int HW, int C, float scale, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* dF = [F > 0] * (scale * F (dG + dG^T) + incoming), rounded once to bf16.  F fp16, dG fp32, incoming (nullable) bf16 (N,HW,C).
+ * No fp16 intermediate: F is split exactly into two bf16 terms, dG + dG^T into a bf16 head and tail (three bf16 MFMA products). */
+size_t mstg_style16_gram_bwd_workspace_bytes(int N, int C);
+int mstg_style16_gram_bwd(const void* f, const float* dg, const void* incoming, void* df, int N, int HW, int C, float scale,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * fp16 inference of StructuralTransformerBlock (structural_transformer.py:55-74), csrc/infer_f16_block.hip: fp16 storage and MFMA
  * operands, fp32 accumulation / statistics / softmax, tokens (N, L, C) token-major.  Fixed summation order, no atomics: image i
  * of a batch equals the same image run alone.

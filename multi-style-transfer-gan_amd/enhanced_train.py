@@ -93,13 +93,17 @@ class EnhancedCycleGAN:
         self.style_loss = None              # optional build-defined multi-style Gram loss on G_BA's output
         self.lambda_style = 0.0
 
-    def attach_style_loss(self, style_refs, style_weights=(0.5, 0.3, 0.2), lambda_style=1.0, width_div=1, seed=1234):
+    def attach_style_loss(self, style_refs, style_weights=(0.5, 0.3, 0.2), lambda_style=1.0, width_div=1, seed=1234, precision=None):
         """BUILD-DEFINED extension (the reference has no style loss): add
         ``lambda_style * MultiStyleGramLoss(fake_A)`` to the generator objective, fake_A = G_BA(real_B) being the stylised
-        image.  ``style_refs``: sequence of (N,3,H,W) tensors in [-1,1]; targets are computed once, here."""
+        image.  ``style_refs``: sequence of (N,3,H,W) tensors in [-1,1]; targets are computed once, here.
+        ``precision``: "fp32" or "mixed" (fp16 features, bf16 gradients: style_loss.py); None reads MSTG_STYLE_PRECISION and falls
+        back to "fp32".  An unknown value raises."""
         import style_loss as sl
-        feats = sl.VGGFeatures(width_div=width_div, seed=seed).to(self.device)
-        self.style_loss = sl.MultiStyleGramLoss(feats, [r.to(self.device) for r in style_refs], style_weights)
+        if precision is None:
+            precision = os.environ.get("MSTG_STYLE_PRECISION") or "fp32"
+        feats = sl.VGGFeatures(width_div=width_div, seed=seed, precision=precision).to(self.device)
+        self.style_loss = sl.MultiStyleGramLoss(feats, [r.to(self.device) for r in style_refs], style_weights, precision=precision)
         self.lambda_style = float(lambda_style)
 
     def _build_optimizers(self):

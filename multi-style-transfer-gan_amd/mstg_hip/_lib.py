@@ -30,6 +30,15 @@ class F16PlainDesc(C.Structure):
         "kind", "N", "H", "W", "Cin", "Ho", "Wo", "Cout", "K", "src_nchw_f32", "dst_nchw", "act")]
 
 
+class Style16ConvDesc(C.Structure):
+    """mirror of mstg_style16_conv_desc"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "dtype", "N", "H", "W", "Cin", "Cout", "src_nchw_f32", "dst_nchw_f32", "flip", "relu")]
+
+
+STYLE16_F16, STYLE16_BF16 = 0, 1
+
+
 class ImgDesc(C.Structure):
     """mirror of mstg_img_desc"""
     _fields_ = ([("src", C.c_void_p)] + [(n, C.c_int32) for n in (
@@ -53,6 +62,7 @@ _vp, _fp, _sz, _i, _f = C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float
 _dp = C.POINTER(ConvDesc)
 _hp = C.POINTER(F16ConvDesc)
 _pp = C.POINTER(F16PlainDesc)
+_sp = C.POINTER(Style16ConvDesc)
 
 # name -> (restype, argtypes); the test-suite checks that every symbol declared in include/mstg_hip.h is here
 SIGNATURES = {
@@ -169,6 +179,16 @@ SIGNATURES = {
     "mstg_f16_train_bias_grad": (_i, [_vp, _sz, _i, _i, _fp, _fp, _vp, _sz, _vp]),
     "mstg_f16_train_scale_update": (_i, [_fp, _fp, _vp, _vp]),
     "mstg_f16_train_adam": (_i, [_fp, _fp, _fp, _fp, _sz, _f, _f, _f, _f, _i, _vp, _vp]),
+    "mstg_style16_conv_plan_bytes": (_sz, [_sp]),
+    "mstg_style16_conv_kernel_name": (C.c_char_p, [_sp]),
+    "mstg_style16_conv_pack": (_i, [_sp, _fp, _fp, _vp, _sz, _vp]),
+    "mstg_style16_conv_fwd": (_i, [_sp, _vp, _vp, _vp, _vp, _vp]),
+    "mstg_style16_maxpool_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mstg_style16_maxpool_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mstg_style16_gram_workspace_bytes": (_sz, [_i, _i, _i]),
+    "mstg_style16_gram_fwd": (_i, [_vp, _fp, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "mstg_style16_gram_bwd_workspace_bytes": (_sz, [_i, _i]),
+    "mstg_style16_gram_bwd": (_i, [_vp, _fp, _vp, _vp, _i, _i, _i, _f, _vp, _sz, _vp]),
     "mstg_f16_linear_plan_bytes": (_sz, [_i, _i]),
     "mstg_f16_linear_pack": (_i, [_fp, _fp, _i, _i, _vp, _sz, _vp]),
     "mstg_f16_linear_fwd": (_i, [_vp, _vp, _fp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -8,6 +8,9 @@ typedef _Float16 h16;
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 b16;
+typedef __bf16 b16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
 
 namespace mstg {
 
@@ -71,5 +74,11 @@ __device__ __forceinline__ f32x4 mfma16x16x32_f16(h16x8 a, h16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ h16x4 cvt4(f32x4 v) { return h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]}; }
+
+// bf16-in / fp32-accumulate MFMA (v_mfma_f32_16x16x32_bf16): the operand and accumulator layouts of the fp16 form.  A float -> b16
+// cast rounds to nearest even (v_cvt_pk_bf16_f32).
+__device__ __forceinline__ f32x4 mfma16x16x32_bf16(b16x8 a, b16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
 
 }  // namespace mstg
