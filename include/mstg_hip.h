@@ -554,6 +554,33 @@ int mstg_f16_token_mean(const void* x, float* out, int N, int L, int dim, void* 
 int mstg_f16_flash_attn_fwd(const void* qkv, void* out, int N, int L, int heads, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixed-precision attention of StructuralTransformerBlock for TRAINING (structural_transformer.py:70), csrc/flash_f16_train.hip;
+ * ops.flash_attention(qkv, heads, precision="mixed").  16-bit MFMA operands, fp32 accumulation, fp32 softmax, fp32 results.
+ * qkv fp32 (N, L, 3 heads D) q | k | v, scale = 1 / sqrt(D), D in {16, 32, 64}: D = 8 is refused by name (MSTG_E_UNSUPPORTED,
+ * the width in mstg_last_error()) -- mstg_flash_attn_fwd/bwd serve it.  Contract:
+ *   cast      qh = fp16(qkv), qb = bf16(qkv), round-to-nearest-even from the fp32 values; the caller keeps these, not qkv
+ *   forward   S = q_h k_h^T (fp32 accumulation); p = exp(scale (S - m)) in fp32; l sums the fp32 p; P is rounded to fp16 once for
+ *             P v_h; out = O / l (fp32); lse = scale m + ln l (fp32, (N, heads, L))
+ *   backward  dO_b = bf16(dO); S recomputed from qh, P = exp(scale S - lse) in fp32; dP = dO_b v_b^T; dV = bf16(P)^T dO_b;
+ *             delta = sum_keys P dP in fp32, from the same P and dP that dS is made of (a first sweep of the dQ kernel) -- NOT
+ *             sum_d dO out of the fp32 tensors: that sum sees other roundings of the operands than dP does, so a row of dS would
+ *             not sum to zero (with one token dq and dk come out at 3e-3 instead of 0), and the saved out is not needed;
+ *             dS = bf16(P (dP - delta)), the product in fp32, rounded once; dQ = scale dS k_b; dK = scale dS^T q_b; dqkv fp32.
+ *             bf16 has fp32's range: no loss scale, no state.
+ * Fixed summation order, no atomics: image i of a batch gives the bits of the same image run alone.
+ * Not built: 16-bit training forms of the block's Linear layers, LayerNorm and GELU (they stay on the fp32 kernels); D = 8.
+ * ---------------------------------------------------------------------------------------------- */
+/* (:70) qh fp16 and qb bf16 (N, L, 3 heads D), both from the fp32 qkv in one pass */
+int mstg_f16_attn_cast_qkv(const float* qkv, void* qh, void* qb, int N, int L, int heads, int D, void* stream);
+/* (:70) forward of the contract above from qh: out fp32 (N, L, heads D), lse fp32 (N, heads, L) */
+int mstg_f16_flash_attn_train_fwd(const void* qh, float* out, float* lse, int N, int L, int heads, int D, void* stream);
+/* (:70) backward of the contract above: dqkv fp32 (N, L, 3 heads D) = dq | dk | dv, every element written.  The caller-owned
+ * workspace holds delta (N, heads, L) fp32 and dO_b (N, L, heads D) bf16; launches: cast of dO, delta + dQ, dK/dV. */
+size_t mstg_f16_flash_attn_train_bwd_workspace_bytes(int N, int L, int heads, int D);
+int mstg_f16_flash_attn_train_bwd(const void* qh, const void* qb, const float* lse, const float* d_out, float* dqkv,
+                                  void* workspace, size_t workspace_bytes, int N, int L, int heads, int D, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Image pre/post-processing of the callers either side of the generator, on the device (8-bit RGB, HWC, 3 bytes per pixel).
  * Replaces PIL / torchvision / numpy work in MonetPhotoDataset (pretrain.py:32-57) and process_cyclegan
  * (batch_process_images.py:183-233).  Integer work: bit-exact against Pillow.

@@ -173,6 +173,19 @@ class EnhancedGenerator(nn.Module):
             m.requires_grad_(True)
         self.use_checkpointing = True
 
+    def set_attention_precision(self, precision):
+        """Attention kernels of every transformer block in training and fp32 inference: "fp32" (the default) or "mixed" (16-bit MFMA
+        operands, fp32 accumulation, softmax and results; head widths 16, 32 and 64, i.e. channels 16 / 32 / 64 -- ops.flash_attention).
+        Raises ValueError for an unknown value and RuntimeError for a head width the mixed kernels do not serve."""
+        from mstg_hip import ops
+        ops.check_attention_precision(precision)
+        blocks = [b for b in self.transformer_blocks if not getattr(b, "is_identity", False)]
+        for b in blocks:
+            ops.check_attention_precision(precision, b.dim // b.num_heads)
+        for b in blocks:
+            b.attention_precision = precision
+        return self
+
     def half_inference(self, enable: bool = True, fp16_blocks: bool = False):
         """Inference-only fast path (BASELINE config #5): fp16 storage, fp16 MFMA, fp32 accumulation / statistics / softmax.
         Under ``torch.no_grad()`` ``forward`` then runs csrc/infer_f16.hip (mstg_hip/infer.py) and returns an fp16 (N,3,H,W)

@@ -62,7 +62,10 @@ class _MeanLoss:
 
 class EnhancedCycleGAN:
     def __init__(self, pretrained_path=None, *, channels=16, num_transformer_blocks=1, device=None,
-                 gradient_checkpointing=False):
+                 gradient_checkpointing=False, attention_precision=None):
+        # attention of the transformer blocks of both generators: "fp32" or "mixed" (16-bit MFMA operands, fp32 accumulation,
+        # softmax and results: ops.flash_attention); None reads MSTG_ATTN_PRECISION and falls back to "fp32".  An unknown value raises.
+        self.attention_precision = ops.attention_precision_from_env(attention_precision)
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError("EnhancedCycleGAN (MI355X build) needs a GPU: there is no CPU path")
@@ -72,6 +75,8 @@ class EnhancedCycleGAN:
         self.G_BA = EnhancedGenerator(channels=channels, num_transformer_blocks=num_transformer_blocks).to(self.device)
         self.D_A = EnhancedDiscriminator(channels=channels).to(self.device)
         self.D_B = EnhancedDiscriminator(channels=channels).to(self.device)
+        self.G_AB.set_attention_precision(self.attention_precision)  # checkpointing recomputes with the same precision
+        self.G_BA.set_attention_precision(self.attention_precision)
         if gradient_checkpointing:  # reference :24-25 turns it on for an 8 GB-class GPU; results are identical
             self.G_AB.gradient_checkpointing_enable()
             self.G_BA.gradient_checkpointing_enable()
@@ -350,7 +355,7 @@ class EnhancedCycleGAN:
 
 
 def train(data_root, save_dir, pretrained_path=None, num_epochs=200, batch_size=1, *, channels=16, num_transformer_blocks=1,
-          datasets=None, log_every=10, save_every=20):
+          datasets=None, log_every=10, save_every=20, attention_precision=None):
     """The reference's training loop (enhanced_train.py:154-208) on the MI355X step: two ``MonetPhotoDataset`` (transform on the
     GPU, pretrain.py drop-in), zipped loaders, ``train_step`` per pair, ``save_models`` every 20 epochs.
 
@@ -360,7 +365,8 @@ def train(data_root, save_dir, pretrained_path=None, num_epochs=200, batch_size=
     losses are read back (one sync) only when they are printed."""
     from pretrain import DeviceLoader, MonetPhotoDataset, set_seed  # the drop-in module next to this file
     set_seed(42)
-    model = EnhancedCycleGAN(pretrained_path, channels=channels, num_transformer_blocks=num_transformer_blocks)
+    model = EnhancedCycleGAN(pretrained_path, channels=channels, num_transformer_blocks=num_transformer_blocks,
+                             attention_precision=attention_precision)
     if datasets is None:
         datasets = (MonetPhotoDataset(data_root, domain="A", device=model.device), MonetPhotoDataset(data_root, domain="B", device=model.device))
     monet_loader = DeviceLoader(datasets[0], batch_size=batch_size, shuffle=True, drop_last=True)

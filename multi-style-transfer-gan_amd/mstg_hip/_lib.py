@@ -196,6 +196,10 @@ SIGNATURES = {
     "mstg_f16_token_mean_workspace_bytes": (_sz, [_i, _i, _i]),
     "mstg_f16_token_mean": (_i, [_vp, _fp, _i, _i, _i, _vp, _sz, _vp]),
     "mstg_f16_flash_attn_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "mstg_f16_attn_cast_qkv": (_i, [_fp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mstg_f16_flash_attn_train_fwd": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    "mstg_f16_flash_attn_train_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mstg_f16_flash_attn_train_bwd": (_i, [_vp, _vp, _fp, _fp, _fp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "mstg_add": (_i, [_fp, _fp, _fp, _sz, _vp]),
     "mstg_weighted_sum_fwd": (_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_float), _i, _i, _fp, _vp]),
     "mstg_weighted_sum_bwd": (_i, [_fp, C.POINTER(C.c_float), _i, _fp, _vp]),

@@ -42,7 +42,11 @@ def _stale(target: str, deps) -> bool:
 # left to its heuristic the compiler then puts EVERY MFMA accumulator into AGPRs (an accvgpr copy on each side of all VALU work on
 # a chain's result) and spills ~90 VGPRs to scratch; forced to the VGPR form it uses the AGPRs as spill space and needs no scratch.
 # The other kernels of the file stay below 256 registers and compile to the same code either way.
-PER_SOURCE_FLAGS = {"attention_reg.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+# flash_f16_train.hip: every MFMA result is VALU input at once (softmax, P and dS roundings) and the loops are VALU-bound; with the
+# accumulators in AGPRs each tile pays 60-96 v_accvgpr copies, a fifth of its vector instructions (3-9 % of forward +
+# backward; that A/B was made with a one-sweep dQ kernel, before the delta sweep was added, and not repeated since).
+PER_SOURCE_FLAGS = {"attention_reg.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+                    "flash_f16_train.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def _flags() -> str:

@@ -1689,8 +1689,86 @@ class FlashAttnFn(torch.autograd.Function):
         return dqkv, None
 
 
-def flash_attention(qkv, heads):
-    return FlashAttnFn.apply(qkv, heads)
+ATTENTION_PRECISIONS = ("fp32", "mixed")
+MIXED_ATTENTION_WIDTHS = (16, 32, 64)
+
+
+def check_attention_precision(precision, head_width=None):
+    """Validate an attention precision (and, for "mixed", the head width) without touching the device."""
+    if precision not in ATTENTION_PRECISIONS:
+        raise ValueError(f"mstg_hip attention: precision must be one of {ATTENTION_PRECISIONS}, got {precision!r}")
+    if precision == "mixed" and head_width is not None and head_width not in MIXED_ATTENTION_WIDTHS:
+        raise RuntimeError(f"mstg_hip attention: precision='mixed' serves head widths {MIXED_ATTENTION_WIDTHS}, not {head_width}; "
+                           f"the fp32 kernels (precision='fp32') serve head width {head_width}")
+    return precision
+
+
+def attention_precision_from_env(precision=None):
+    """precision, or MSTG_ATTN_PRECISION when it is None, or "fp32"; validated."""
+    if precision is None:
+        precision = os.environ.get("MSTG_ATTN_PRECISION") or "fp32"
+    return check_attention_precision(precision)
+
+
+class FlashAttnMixedFn(torch.autograd.Function):
+    """FlashAttnFn on the 16-bit MFMA (csrc/flash_f16_train.hip; the contract is stated in include/mstg_hip.h): fp16 operands in
+    the forward, bf16 gradient-side operands in the backward, fp32 accumulation, softmax and results.  Saves the fp16 and bf16
+    copies of qkv and the log-sum-exp; neither qkv nor the output."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        qkv = _req(qkv, "attention qkv")
+        N, L, C3 = qkv.shape
+        dim = C3 // 3
+        D = dim // heads
+        lib = _lib.load()
+        qh = torch.empty((N, L, C3), dtype=torch.float16, device=qkv.device)
+        qb = torch.empty((N, L, C3), dtype=torch.bfloat16, device=qkv.device)
+        out = torch.empty((N, L, dim), dtype=torch.float32, device=qkv.device)
+        lse = torch.empty((N, heads, L), dtype=torch.float32, device=qkv.device)
+        detail = f"N{N} L{L} heads{heads} D{D}"
+        _timed("ft_cast_kernel", 0, 8.0 * qkv.numel(), lambda: _lib.check(
+            lib.mstg_f16_attn_cast_qkv(_p(qkv), _p(qh), _p(qb), N, L, heads, D, _stream()), "mstg_f16_attn_cast_qkv"), detail)
+        _timed(f"ft_fwd_kernel<{D}>", 4.0 * N * heads * L * L * D, 2.0 * qkv.numel() + 4.0 * out.numel(), lambda: _lib.check(
+            lib.mstg_f16_flash_attn_train_fwd(_p(qh), _p(out), _p(lse), N, L, heads, D, _stream()), "mstg_f16_flash_attn_train_fwd"),
+            detail)
+        ctx.heads = heads
+        ctx.save_for_backward(qh, qb, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        qh, qb, lse = ctx.saved_tensors
+        d_out = _req(d_out, "attention grad_output")
+        N, L, C3 = qh.shape
+        heads = ctx.heads
+        D = C3 // 3 // heads
+        lib = _lib.load()
+        dqkv = torch.empty((N, L, C3), dtype=torch.float32, device=qh.device)
+        ws = _ws(lib.mstg_f16_flash_attn_train_bwd_workspace_bytes(N, L, heads, D), qh.device)
+        # algorithmic work, as the fp32 entry books it (two L x L x D products per output, no recompute): the kernels execute about
+        # 18 N heads L^2 D MFMA FLOP, the dQ kernel forming S and dP twice; the bf16 cast of dO shows under its own symbol with none
+        half = (4.0 * N * heads * L * L * D, 2.0 * qh.numel() + 4.0 * d_out.numel())
+        _timed(f"ft_bwd_dkv_kernel<{D}>", 2 * half[0], 2 * half[1], lambda: _lib.check(
+            lib.mstg_f16_flash_attn_train_bwd(_p(qh), _p(qb), _p(lse), _p(d_out), _p(dqkv), _p(ws), ws.numel() * 4, N, L,
+                                              heads, D, _stream()), "mstg_f16_flash_attn_train_bwd"),
+            f"N{N} L{L} heads{heads} D{D}", split={f"ft_bwd_dq_kernel<{D}>": half, f"ft_bwd_dkv_kernel<{D}>": half})
+        return dqkv, None
+
+
+def flash_attention(qkv, heads, precision="fp32"):
+    """softmax(q k^T / sqrt(D)) v per head over all tokens.  precision "fp32": the fp32 MFMA kernels (the default, unchanged);
+    "mixed": 16-bit MFMA operands with fp32 accumulation, softmax and results (head widths 16, 32, 64)."""
+    check_attention_precision(precision)
+    if precision == "fp32":
+        return FlashAttnFn.apply(qkv, heads)
+    C3 = qkv.shape[-1]
+    dim = C3 // 3
+    D = dim // max(int(heads), 1)
+    if dim * 3 != C3 or D * heads != dim:
+        raise RuntimeError(f"mstg_hip flash attention: {C3} channels do not split into q|k|v x {heads} heads")
+    check_attention_precision(precision, D)
+    return FlashAttnMixedFn.apply(qkv, heads)
 
 
 class AddFn(torch.autograd.Function):

@@ -22,7 +22,9 @@ structure signal taken from the image itself:
 Everything runs on the HIP kernels: the Linear layers as 1x1 convolutions over the token grid (implicit-GEMM, with their weight
 gradients), LayerNorm + modulation, GELU and the structure map as fused element-wise kernels, attention as a flash-style fp32
 MFMA kernel that never materialises the L x L matrix (L = 4096 at 256x256, 65536 at 1024x1024).  ``structure_map`` is treated
-as a constant of the input image (no gradient flows into ``orig_input`` through it).
+as a constant of the input image (no gradient flows into ``orig_input`` through it).  ``block.attention_precision = "mixed"``
+(default ``"fp32"``; ``EnhancedGenerator.set_attention_precision``) runs the attention, forward and backward, on the 16-bit MFMA
+kernels of csrc/flash_f16_train.hip with fp32 accumulation, softmax and results; head widths 16, 32 and 64.
 """
 from __future__ import annotations
 
@@ -35,6 +37,9 @@ from mstg_hip.ops import ACT_GELU
 
 class StructuralTransformerBlock(nn.Module):
     is_identity = False
+    # "fp32" (default) or "mixed": the attention's kernels (ops.flash_attention).  A plain attribute read in forward: not a
+    # constructor argument, not in the state_dict; EnhancedGenerator.set_attention_precision sets it on every block.
+    attention_precision = "fp32"
 
     def __init__(self, dim, num_heads=4, mlp_ratio=2):
         super().__init__()
@@ -53,6 +58,7 @@ class StructuralTransformerBlock(nn.Module):
         nn.init.zeros_(self.style_mod.bias)
 
     def forward(self, x, style, orig_input):
+        ops.check_attention_precision(self.attention_precision, self.dim // self.num_heads)
         if x.dim() != 3 or x.shape[-1] != self.dim:
             raise RuntimeError(f"StructuralTransformerBlock(dim={self.dim}) got tokens of shape {tuple(x.shape)}")
         N, L, dim = x.shape
@@ -67,7 +73,7 @@ class StructuralTransformerBlock(nn.Module):
         g, b = mod[:, :dim].contiguous(), mod[:, dim:].contiguous()
         u = ops.layer_norm_mod(h, self.norm1.weight, self.norm1.bias, g, b, self.norm1.eps)
         qkv = ops.linear_tokens(u, self.qkv.weight, self.qkv.bias)
-        a = ops.flash_attention(qkv, self.num_heads)
+        a = ops.flash_attention(qkv, self.num_heads, self.attention_precision)
         h = ops.add(h, ops.linear_tokens(a, self.proj.weight, self.proj.bias))
         v = ops.layer_norm_mod(h, self.norm2.weight, self.norm2.bias, None, None, self.norm2.eps)
         m = ops.activation(ops.linear_tokens(v, self.fc1.weight, self.fc1.bias), ACT_GELU)  # GELU' needs the pre-activation
